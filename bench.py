@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - EBCC per-frame hot path on MI355X: encode + decode of a batch of synthetic ERA5-shaped frames.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,17 @@ A "step" = ebcc_encode of every frame of the batch (inputs resident in HBM; comp
 memory, zstd on host cores as in the reference) followed by ebcc_decode of those streams back into HBM.
 Workload = BASELINE.json configs[1]: 256 frames 721x1440 fp32, base_cr=30, MAX_ERROR=0.5 per GPU (weak
 scaling: frames are independent, every rank codes its own batch, no collective on the data path).
-Rank 0 prints ONE JSON line.  `value` = frames * 4 152 960 B / step time summed over ranks (round trip).
+Rank 0 prints ONE JSON line.  `value` = frames * 4 152 960 B / step time summed over ranks (round trip);
+`ms_per_step` = wall time of one timed step (the slowest rank's).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else, measured after
+the timed steps: the error bound on the timed data, per-kernel times and roofline figures (kernel timing on during the
+timed steps), host-side counters, the other workloads (--no-extras drops them) and the reference CPU codec with
+stream parity (--no-cpu-baseline drops it).
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (rank 0), as float arrays: the decoded
+fields of a fixed, seeded choice of frames and a seeded sample over the whole batch, and the size and sha256 of every
+compressed stream.  The inputs are seeded, so two builds given the same arguments can be compared file for file.
 """
 import argparse
 import ctypes
@@ -169,9 +179,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=256, help="frames per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads (config3, residual population, host API)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks, kernel / roofline / host figures, the extra workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference CPU codec")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workloads (config3, residual population, host API)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -210,7 +225,7 @@ def main():
     outs = (ctypes.c_void_p * n)()
     sizes = (ctypes.c_size_t * n)()
 
-    def step():
+    def step(keep=False):
         t0 = time.perf_counter()
         rc = lib.ebcc_hip_encode_frames(ctx, frames.data_ptr(), n, ctypes.byref(cfg), outs, sizes)
         assert rc == 0, lib.ebcc_hip_last_error()
@@ -221,9 +236,31 @@ def main():
         nbytes = sum(sizes[i] for i in range(n))
         if step.hash:                                            # (the last warm-up step only: not inside the timed region)
             step.first_hashes = [hashlib.sha256(ctypes.string_at(outs[i], sizes[i])).hexdigest() for i in range(min(n, 2))]
+        if not keep:                                             # (keep: the streams stay for dump_outputs, which frees them)
+            free_streams()
+        return t1 - t0, t2 - t1, nbytes
+
+    def free_streams():
         for i in range(n):
             lib.free_buffer(outs[i])
-        return t1 - t0, t2 - t1, nbytes
+
+    def dump_outputs(dirname):
+        """The last timed step's results as float arrays (at most ~38 MB): decoded fields of 8 seeded frames, a seeded
+        sample of 2^20 values over the whole decoded batch, and the byte count and sha256 (32 values 0..255) of every
+        compressed stream."""
+        os.makedirs(dirname, exist_ok=True)
+        rng = np.random.default_rng(20240521)
+        pick = np.sort(rng.choice(n, size=min(8, n), replace=False))
+        flat = rng.integers(0, n * H * W, size=min(1 << 20, n * H * W))
+        res = {"decoded_frame_index": pick.astype(np.float64),
+               "decoded_frames": out[torch.from_numpy(pick).to(device)].cpu().numpy(),
+               "decoded_sample": out.view(-1)[torch.from_numpy(flat).to(device)].cpu().numpy(),
+               "stream_bytes": np.array([sizes[i] for i in range(n)], np.float64),
+               "stream_sha256": np.array([list(hashlib.sha256(ctypes.string_at(outs[i], sizes[i])).digest()) for i in range(n)],
+                                         np.float32)}
+        for name, a in res.items():
+            assert a.dtype in (np.float32, np.float64), name
+            np.save(os.path.join(dirname, name + ".npy"), a)
 
     def barrier():
         torch.cuda.synchronize()
@@ -236,55 +273,63 @@ def main():
     hstats = (ctypes.c_double * 8)()
     step.hash = False
     for w in range(max(1, args.warmup)):
-        step.hash = w == max(1, args.warmup) - 1
+        step.hash = args.full and w == max(1, args.warmup) - 1   # (stream hashes for the CPU baseline's parity check)
         step()
     step.hash = False
-    lib.ebcc_hip_timing_enable(ctx, 1)
-    lib.ebcc_hip_host_stats(hstats, 1)                          # (reset)
+    if args.full:
+        lib.ebcc_hip_timing_enable(ctx, 1)
+        lib.ebcc_hip_host_stats(hstats, 1)                      # (reset)
     barrier()
-    cg0 = cgroup_cpu()
-    ru0 = os.times()
+    cg0 = cgroup_cpu() if args.full else None
+    ru0 = os.times() if args.full else None
     t0 = time.perf_counter()
     enc_t = dec_t = 0.0
     comp = 0
-    for _ in range(args.steps):
-        e, d, comp = step()
+    for k in range(args.steps):
+        e, d, comp = step(keep=bool(args.dump_outputs) and k == args.steps - 1)   # (the last step's streams: for dump_outputs)
         enc_t += e
         dec_t += d
     barrier()
     elapsed = time.perf_counter() - t0
-    ru1 = os.times()
-    cg1 = cgroup_cpu()
-    lib.ebcc_hip_timing_enable(ctx, 0)
-    lib.ebcc_hip_host_stats(hstats, 0)
-    # host side of this rank over the timed region (per step): what the entropy stage cost, what the process burnt in all
-    # its threads, and whether the container's CPU quota throttled it
+    ru1 = os.times() if args.full else None
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(args.dump_outputs)
+        free_streams()
     lib.ebcc_hip_default_encode_slices.restype = ctypes.c_int
     lib.ebcc_hip_encode_slices_for.restype = ctypes.c_int
     lib.ebcc_hip_encode_slices_for.argtypes = [ctypes.c_size_t]
     default_slices = int(lib.ebcc_hip_encode_slices_for(n))     # (what a batch of n frames runs as: the environment and the batch size decide)
-    host = {"pool_threads": lib.ebcc_hip_host_threads(default_slices),
-            "usable_cpus": int(hstats[0]), "quota_cpus": hstats[1] or None,
-            "zstd_core_s_per_step": round(hstats[2] / args.steps, 4), "zstd_wait_ms_per_step": round(hstats[3] / args.steps * 1e3, 2),
-            "zstd_MB_per_step": round(hstats[4] / args.steps / 1e6, 3),
-            "prefix_MB_per_step_decided_without_zstd": round(hstats[6] / args.steps / 1e6, 3),
-            "process_cpu_s_per_step": round(((ru1.user - ru0.user) + (ru1.system - ru0.system)) / args.steps, 4)}
-    if cg0["nr_throttled"] is not None and cg1["nr_throttled"] is not None:
-        host["cgroup"] = {"quota_cpus": cg1["quota_cpus"], "periods": cg1["nr_periods"] - cg0["nr_periods"],
-                          "throttled_periods": cg1["nr_throttled"] - cg0["nr_throttled"],
-                          "throttled_ms_per_step": round((cg1["throttled_usec"] - cg0["throttled_usec"]) / 1e3 / args.steps, 2),
-                          "cpu_s_per_step": None if cg0["usage_usec"] is None else round((cg1["usage_usec"] - cg0["usage_usec"]) / 1e6 / args.steps, 4)}
+    host = max_err = None
+    if args.full:
+        cg1 = cgroup_cpu()
+        lib.ebcc_hip_timing_enable(ctx, 0)
+        lib.ebcc_hip_host_stats(hstats, 0)
+        # host side of this rank over the timed region (per step): what the entropy stage cost, what the process burnt in all
+        # its threads, and whether the container's CPU quota throttled it
+        host = {"pool_threads": lib.ebcc_hip_host_threads(default_slices),
+                "usable_cpus": int(hstats[0]), "quota_cpus": hstats[1] or None,
+                "zstd_core_s_per_step": round(hstats[2] / args.steps, 4), "zstd_wait_ms_per_step": round(hstats[3] / args.steps * 1e3, 2),
+                "zstd_MB_per_step": round(hstats[4] / args.steps / 1e6, 3),
+                "prefix_MB_per_step_decided_without_zstd": round(hstats[6] / args.steps / 1e6, 3),
+                "process_cpu_s_per_step": round(((ru1.user - ru0.user) + (ru1.system - ru0.system)) / args.steps, 4)}
+        if cg0["nr_throttled"] is not None and cg1["nr_throttled"] is not None:
+            host["cgroup"] = {"quota_cpus": cg1["quota_cpus"], "periods": cg1["nr_periods"] - cg0["nr_periods"],
+                              "throttled_periods": cg1["nr_throttled"] - cg0["nr_throttled"],
+                              "throttled_ms_per_step": round((cg1["throttled_usec"] - cg0["throttled_usec"]) / 1e3 / args.steps, 2),
+                              "cpu_s_per_step": None if cg0["usage_usec"] is None else round((cg1["usage_usec"] - cg0["usage_usec"]) / 1e6 / args.steps, 4)}
 
-    # parity guard on the timed data: the error bound holds on every frame (size-independent property)
-    max_err = float((out - frames).abs().amax())
-    assert max_err <= MAX_ERR * 1.01 + 1e-3, max_err
+        # parity guard on the timed data: the error bound holds on every frame (size-independent property)
+        max_err = float((out - frames).abs().amax())
+        assert max_err <= MAX_ERR * 1.01 + 1e-3, max_err
 
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else device)
     hosts = [host]
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        hosts = [None] * world
-        dist.all_gather_object(hosts, host)
+        if args.full:
+            hosts = [None] * world
+            dist.all_gather_object(hosts, host)
     elapsed = float(t.item())
 
     parity_checks = []                                              # (tag, frame, sha256 of its MI355X stream) -> cpu_baseline
@@ -442,7 +487,7 @@ def main():
         quota = hosts[0]["quota_cpus"] or len(os.sched_getaffinity(0))
         share = max(1, int(quota // 8))
         cpus = sorted(os.sched_getaffinity(0))[:share]
-        base = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+        base = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"]
         out_ = {"cpus_per_rank": share, "of_quota": quota}
         for tag, cmd, env in (("pool_sized_for_8_ranks", base, dict(os.environ, LOCAL_WORLD_SIZE="8")),
                               ("confined_to_an_eighth_of_the_cpus", ["taskset", "-c", ",".join(map(str, cpus))] + base, dict(os.environ))):
@@ -460,7 +505,7 @@ def main():
 
     extras = None
     rehearsal = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = extra_workloads()
         torch.cuda.empty_cache()
         rehearsal = rehearsal_8_ranks()
@@ -469,6 +514,23 @@ def main():
         ms_step = elapsed / args.steps * 1e3
         total_frames = n * world
         value = total_frames * FRAME_BYTES / (elapsed / args.steps) / 1e9
+        slices = default_slices
+        lib.ebcc_hip_host_threads.restype = ctypes.c_int
+        line = {
+            "metric": "fp32 GB/s encode+decode, 721x1440 ERA5 frames MAX_ERROR=0.5",
+            "value": round(value, 4), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{n}-frame batch 721x1440 fp32 per GPU, base_cr=30 MAX_ERROR=0.5 (BASELINE configs[1])",
+                       "frames_per_gpu": n, "parallelism": f"frames sharded over {world} GPU(s), no collective",
+                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                       "encode_slices": slices, "host_pool_threads": lib.ebcc_hip_host_threads(slices),
+                       "host_cpus_affinity": len(os.sched_getaffinity(0))},
+            "encode_GBps": round(total_frames * FRAME_BYTES * args.steps / enc_t / 1e9, 4),
+            "decode_GBps": round(total_frames * FRAME_BYTES * args.steps / dec_t / 1e9, 4),
+            "compressed_bytes_per_frame": int(comp / n),
+        }
+    if rank == 0 and args.full:
         # dominant kernel by total time: tier-1 coding of every code-block (HIP events recorded on the launching
         # stream of each slice engine around its kernels)
         tms, launches = ctypes.c_double(), ctypes.c_long()
@@ -547,23 +609,7 @@ def main():
                         "frac": round(algo / avg_s / 1e9 / 8000.0, 6), "traffic": dec_traffic, "traffic_source": dec_src, "avg_launch_ms": round(avg_s * 1e3, 4),
                         "algorithmic_bytes_per_launch": algo, "frames_per_launch": n * args.steps / c.value,
                         "note": "a serial entropy decoder: latency- and issue-bound by nature; decode_GBps is the phase as a whole"}
-        slices = default_slices
-        lib.ebcc_hip_host_threads.restype = ctypes.c_int
-        line = {
-            "metric": "fp32 GB/s encode+decode, 721x1440 ERA5 frames MAX_ERROR=0.5",
-            "value": round(value, 4), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{n}-frame batch 721x1440 fp32 per GPU, base_cr=30 MAX_ERROR=0.5 (BASELINE configs[1])",
-                       "frames_per_gpu": n, "parallelism": f"frames sharded over {world} GPU(s), no collective",
-                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                       "encode_slices": slices, "host_pool_threads": lib.ebcc_hip_host_threads(slices),
-                       "host_cpus_affinity": len(os.sched_getaffinity(0))},
-            "encode_GBps": round(total_frames * FRAME_BYTES * args.steps / enc_t / 1e9, 4),
-            "decode_GBps": round(total_frames * FRAME_BYTES * args.steps / dec_t / 1e9, 4),
-            "compressed_bytes_per_frame": int(comp / n), "max_abs_error": round(max_err, 5),
-            "kernels": kern, "roofline": roof, "roofline_decode": roof_dec,
-        }
+        line.update({"max_abs_error": round(max_err, 5), "kernels": kern, "roofline": roof, "roofline_decode": roof_dec})
         # the host side, per rank; and the step time the host alone would allow: every rank's zstd core-seconds over the CPUs
         # the ranks share (the container's quota if there is one) - a run whose ms_per_step sits on it is bound by the host
         cpus_shared = hosts[0]["quota_cpus"] or len(os.sched_getaffinity(0))
@@ -594,6 +640,7 @@ def main():
                 line["cpu_baseline"] = cpu_baseline(host_frames, cores, checks)
             except Exception as e:                              # the baseline is a report, never a gate
                 line["cpu_baseline"] = {"error": repr(e)}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     lib.ebcc_hip_destroy(ctx)
     if world > 1:

@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 def test_two_ranks_give_one_line_with_the_whole_job_value():
     env = dict(os.environ, EBCC_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29517", os.path.join(L.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "24"]
+           "--master-port", "29517", os.path.join(L.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "24",
+           "--full"]                                               # (the gathered host figures and the error bound are --full's)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-600:], r.stderr[-1200:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -366,7 +366,7 @@ def test_env_switches_match_oracle(switch, monkeypatch):
     monkeypatch.setenv(switch, "1")
     monkeypatch.setenv("EBCC_INIT_BASE_ERROR_QUANTILE", "0.1")        # loose base layer: the switches change the streams
     L.oracle().orc_set_j2k_backend(0)
-    for frame, cfg in env_switch_cases():
+    for frame, cfg, _ in env_switch_cases(switch):
         assert api_encode(frame, cfg) == L.orc_encode(frame, cfg), switch
 
 

@@ -154,11 +154,15 @@ def test_multi_frame_chunk_extremes(name):
     assert sha(L.orc_decode(s).tobytes()) == c["decoded_sha256"]
 
 
-@pytest.mark.skipif(not os.path.exists(L.REF_SO), reason="reference build only exists in the dev container")
+_live = load("live_checks.json")
+_live_inputs = np.load(os.path.join(L.GOLDEN, "live_checks_inputs.npz"))
+
+
 def test_j2k_restatement_matches_openjpeg_live():
+    """The restated encoder against OpenJPEG 2.4.0 on small natural-looking images: the codestreams OpenJPEG wrote
+    (oracle/make_golden_live.py), and OpenJPEG itself where the oracle's backend finds the library."""
     lib = L.oracle()
-    if not hasattr(lib, "orc_opj_encode"):
-        pytest.skip("oracle built without the OpenJPEG backend")
+    live = hasattr(lib, "orc_opj_encode") and L.opj_version() == _live["openjpeg"]
 
     def enc(fn, img, cr):
         out = ctypes.c_void_p()
@@ -167,11 +171,12 @@ def test_j2k_restatement_matches_openjpeg_live():
         lib.orc_free(out)
         return s
 
-    for h, w in [(32, 32), (45, 70), (100, 130)]:
-        f = L.era5_like(h, w, h + w)
-        img = np.ascontiguousarray((((f - f.min()) / (f.max() - f.min())) * np.float32(65535)).astype(np.uint16))
-        for cr in (1.0, 4.0, 17.0, 60.0, 900.0):
-            assert enc(lib.orc_opj_encode, img, cr) == enc(lib.orc_j2k_encode, img, cr), (h, w, cr)
+    for c in _live["opj"]:
+        img = np.ascontiguousarray(_live_inputs[c["input"]])
+        s = enc(lib.orc_j2k_encode, img, c["cr"])
+        assert len(s) == c["n"] and sha(s) == c["stream_sha256"], (c["input"], c["cr"])
+        if live:
+            assert enc(lib.orc_opj_encode, img, c["cr"]) == s, (c["input"], c["cr"])
 
 
 _j2k = json.load(open(os.path.join(L.GOLDEN, "j2k_openjpeg.json")))
@@ -245,26 +250,30 @@ ENV_SWITCHES = ["EBCC_DISABLE_PURE_BASE_COMPRESSION_FALLBACK", "EBCC_DISABLE_PUR
                 "EBCC_DISABLE_MEAN_ADJUSTMENT"]
 
 
-def env_switch_cases():
-    """(frame, config) pairs that exercise both outcomes of the :838 selection (residual kept / pure base layer)."""
-    a = L.era5_like(64, 96, 21, 1.0, 0.8)
-    b = L.smooth_image(96, 64, 5) if hasattr(L, "smooth_image") else L.era5_like(96, 64, 22, 2.5, 0.2)
-    return [(a, L.make_config((1, 64, 96), base_cr=25.0, error=0.02, residual_type=L.MAX_ERROR)),
-            (a, L.make_config((1, 64, 96), base_cr=8.0, error=2e-3, residual_type=L.RELATIVE_ERROR)),
-            (np.ascontiguousarray(b, np.float32).reshape(96, 64), L.make_config((1, 96, 64), base_cr=40.0, error=0.05, residual_type=L.MAX_ERROR))]
+def env_switch_cases(switch):
+    """(frame, config, what the reference build wrote) triples that exercise both outcomes of the :838 selection
+    (residual kept / pure base layer); frames stored with the reference's streams (oracle/make_golden_live.py)."""
+    return [(np.ascontiguousarray(_live_inputs[c["input"]], np.float32),
+             L.make_config(tuple(c["shape"]), base_cr=c["base_cr"], error=c["error"], residual_type=c["mode"]), c)
+            for c in _live["env_switches"][switch]]
 
 
-@pytest.mark.skipif(not os.path.exists(L.REF_SO), reason="reference build only exists in the dev container")
 @pytest.mark.parametrize("switch", ENV_SWITCHES)
 def test_oracle_env_switches_match_reference(switch, monkeypatch):
-    """The three EBCC_DISABLE_* switches of src/ebcc_codec.c:634-649: oracle == reference build, so that the GPU
-    test of the same switches (tests/test_codec_gpu.py) can use the oracle on a box without the reference."""
-    ref = ctypes.CDLL(L.REF_SO)
-    ref.ebcc_encode.restype = ctypes.c_size_t
-    ref.ebcc_encode.argtypes = [ctypes.c_void_p, ctypes.POINTER(L.CodecConfig), L.c_void_pp]
+    """The three EBCC_DISABLE_* switches of src/ebcc_codec.c:634-649: oracle == reference build (its streams as stored,
+    and the build itself where it is present), so that the GPU test of the same switches (tests/test_codec_gpu.py) can
+    use the oracle on a box without the reference."""
+    ref = None
+    if os.path.exists(L.REF_SO):
+        ref = ctypes.CDLL(L.REF_SO)
+        ref.ebcc_encode.restype = ctypes.c_size_t
+        ref.ebcc_encode.argtypes = [ctypes.c_void_p, ctypes.POINTER(L.CodecConfig), L.c_void_pp]
     monkeypatch.setenv(switch, "1")
-    monkeypatch.setenv("EBCC_INIT_BASE_ERROR_QUANTILE", "0.1")        # loose base layer: the switches change the streams
-    for frame, cfg in env_switch_cases():
-        out = ctypes.c_void_p()
-        n = ref.ebcc_encode(np.ascontiguousarray(frame, np.float32).ctypes.data, ctypes.byref(cfg), ctypes.byref(out))
-        assert ctypes.string_at(out.value, n) == L.orc_encode(frame, cfg), switch
+    monkeypatch.setenv("EBCC_INIT_BASE_ERROR_QUANTILE", _live["env_quantile"])   # loose base layer: the switches change the streams
+    for frame, cfg, c in env_switch_cases(switch):
+        s = L.orc_encode(frame, cfg)
+        assert len(s) == c["n"] and sha(s) == c["stream_sha256"], (switch, c["input"], c["mode"])
+        if ref is not None:
+            out = ctypes.c_void_p()
+            n = ref.ebcc_encode(frame.ctypes.data, ctypes.byref(cfg), ctypes.byref(out))
+            assert ctypes.string_at(out.value, n) == s, switch

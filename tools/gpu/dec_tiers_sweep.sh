@@ -5,6 +5,6 @@ FR=$1; shift
 for F in $FR; do
   for V in "$@"; do
     echo -n "[frames $F] [$V] "
-    env ${V//+/ } timeout -k 10 300 python bench.py --frames $F --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
+    env ${V//+/ } timeout -k 10 300 python bench.py --frames $F --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
   done
 done

@@ -15,6 +15,6 @@ for V in "$@"; do
   /opt/rocm/bin/hipcc $BASE $OPT $V -c $F -o /tmp/flags_ab.o 2>/dev/null || { echo "[$V] does not build"; continue; }
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libh5z_ebcc.so $OBJS -Wl,-rpath,/opt/rocm/lib -ldl -lpthread || exit 1
   echo -n "[$F $V] "
-  (cd "$GRAFT_REPO_ROOT" && timeout -k 10 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S")
+  (cd ../.. && timeout -k 10 300 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S")
 done
 cp /tmp/libh5z_ebcc.so.keep ../libh5z_ebcc.so

@@ -4,5 +4,5 @@
 S='import json,sys; d=json.loads(sys.stdin.read()); k=d["kernels"]; print(d["ms_per_step"], d["encode_GBps"], d["decode_GBps"], {n: v["ms_avg"] for n, v in k.items()})'
 for F in "$@"; do
   echo -n "[frames $F] "
-  EBCC_HIP_SLICES=1 timeout -k 10 300 python bench.py --frames $F --steps 4 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
+  EBCC_HIP_SLICES=1 timeout -k 10 300 python bench.py --frames $F --steps 4 --warmup 2 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
 done

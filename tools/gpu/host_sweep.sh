@@ -8,6 +8,6 @@ VARS=("A=1" "$@")
 for rep in $(seq 1 $REPS); do
   for V in "${VARS[@]}"; do
     echo -n "[$V] "
-    env $V timeout -k 10 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
+    env $V timeout -k 10 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S"
   done
 done

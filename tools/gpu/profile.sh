@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof
 rm -rf $O && mkdir -p $O
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $O/trace.log 2>&1
 echo "trace rc=$?"
 grep -v "^[WEI]2026" $O/trace.log | tail -1 > $O/bench_under_rocprof.json
 f=$(find $O/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv
@@ -17,7 +17,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
   [ -n "$c" ] && python3 tools/pmc_summary.py "$c" $C 64 > $O/pmc_$C.json
   rm -rf $O/$C
 done
-python3 bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err
+python3 bench.py --steps 3 --warmup 1 --full > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-2500
 cat $O/pmc_FETCH_SIZE.json $O/pmc_WRITE_SIZE.json | head -40
 head -14 $O/kernel_stats.csv | cut -c1-160

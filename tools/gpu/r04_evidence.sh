@@ -10,7 +10,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04
 rm -rf $O && mkdir -p $O
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras > $O/trace.log 2>&1
 echo "trace rc=$?"
 grep -v "^[WEI]2026" $O/trace.log | grep '^{' | tail -1 > $O/r04_bench_under_rocprof.json
 f=$(find $O/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/r04_kernel_stats_bench.csv
@@ -22,9 +22,9 @@ mkdir -p profiles && cp $O/r04_hbm_kernels.json $O/r04_pmc_tier1.json $O/r04_ste
 SLICES=3 bash tools/gpu/timeline.sh > $O/r04_timeline_3slices.txt 2>&1; echo "timeline rc=$?"
 S='import json,sys; d=json.loads(sys.stdin.read()); h=d["host"]["ranks"][0]; print(d["ms_per_step"], d["value"], d["encode_GBps"], d["decode_GBps"], "zstd core-s", h["zstd_core_s_per_step"], "wait ms", h["zstd_wait_ms_per_step"], "throttled ms", (h.get("cgroup") or {}).get("throttled_ms_per_step"))'
 for rep in 1 2 3 4 5; do
-  timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "$S"
+  timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "$S"
 done | tee $O/r04_bench_runs.txt
-timeout -k 10 600 python3 bench.py --steps 10 --warmup 3 > $O/r04_bench_final.json 2> $O/bench_final.err
+timeout -k 10 600 python3 bench.py --steps 10 --warmup 3 --full > $O/r04_bench_final.json 2> $O/bench_final.err
 tail -c 400 $O/bench_final.err
 python3 - <<'PY'
 import json
