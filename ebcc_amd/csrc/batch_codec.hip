@@ -447,6 +447,13 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         const FrameState &t0 = ctx->h_fs[f * tiles];                   // (all tiles of a chunk carry the chunk's statistics)
         if (t0.has_nonfinite) { log_fatal("NaN or Inf found in data of frame %zu", f); return 2; }
         if (b.jf[f].overflow) { log_fatal("code-block byte slot overflow in frame %zu", f); return 1; }
+        if (searching && !t0.const_field && !std::isfinite(t0.maxv - t0.minv)) {
+            // max - min overflows: the decoded base layer is (s / 65535) * inf + min (:1130), every residual is NaN or
+            // infinite, and the reference stops on assert(dc0 >= 0 && dc0 <= MAXELEM) in spiht_encode (spiht_re.c:462)
+            log_fatal("range of frame %zu overflows float (max - min = inf)", f);
+            set_error("frame %zu: max - min overflows float", f);
+            return 1;
+        }
         jobs[f].const_field = t0.const_field != 0;
         jobs[f].minv = t0.minv;
         jobs[f].maxv = t0.maxv;
@@ -549,8 +556,7 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         pt.mark("tails + residual range");
 
         if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-        // ---- the entropy stage's state (the stage itself follows the truncation search; the frames whose search ends first
-        //      - the early group, below - enter it while the others still search).
+        // ---- the entropy stage's state (the stage itself follows the truncation search).
         //      jobs on the process-wide pool (HostPool): every slice of a batch feeds the same workers, so the host is never
         //      oversubscribed however many slices run
         std::vector<const uint8_t *> coeff_ptr(n, nullptr);             // the kept prefix of a frame in pinned host memory
@@ -703,12 +709,12 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
                 if (levels > 1) {
                     const CutSlots &cs = rc->cut;
                     const int n_slots = (int) n * ((1 << levels) - 1);
-                    launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, nullptr, rc->d_counter, rs);
+                    launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, rc->d_counter, rs);
                     int rounds = forced_rounds ? search_rounds() : (cuts_left + levels - 1) / levels + 1;
                     for (;;) {
                         for (int r = 0; r < rounds; r++) {
                             launch_prefix_synthesis_slots(d_frames, jb.DEC, rc->rb, cs, n_slots, rs);
-                            launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, nullptr, rc->d_counter, rs);
+                            launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, rc->d_counter, rs);
                         }
                         EBCC_HIP_CHECK(hipMemcpyAsync(h, d, sizeof(DevChunk) * n, hipMemcpyDeviceToHost, rs));
                         wait_stream(rs);
@@ -781,9 +787,8 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         //      ~95 % of ERA5-like frames the base layer alone wins.  So z is only worked out where it can matter: a frame
         //      whose z is PROVABLY above len2 - len1 (zstd_size_lower_bound: the literals no match can cover cost at least
         //      their entropy) takes the pure base layer without being compressed - the same decision, bytes unchanged.
-        // the kept SPIHT prefixes of the batch (but those of the early group, which left during the truncation search) in one
-        // packed download; the workers read them where they land (the staging buffer of the residual engine is not touched
-        // again before they are done)
+        // the kept SPIHT prefixes of the batch in one packed download; the workers read them where they land (the staging
+        // buffer of the residual engine is not touched again before they are done)
         std::vector<size_t> coeff_len(n, 0), coeff_off(n, 0);
         for (size_t f = 0; f < n; f++) {
             Job &j = jobs[f];
@@ -795,7 +800,7 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         std::vector<size_t> with_prefix;
         for (size_t f = 0; f < n; f++) if (jobs[f].coeffs_size > 0) with_prefix.push_back(f);
         std::vector<size_t> cand;
-        auto not_started = [&](std::vector<size_t> v) {                 // (the early group's jobs are on their way)
+        auto not_started = [&](std::vector<size_t> v) {                 // (frames already queued or decided)
             v.erase(std::remove_if(v.begin(), v.end(), [&](size_t f) { return zstate[f] != kZNone; }), v.end());
             return v;
         };
@@ -854,7 +859,7 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
                 const size_t len2 = (size_t) j.last[1].stream_bytes;
                 // z >= zfloor: len2 < zfloor + len1 implies len2 < z + len1 - the base layer alone wins (:838)
                 if (!(zfloor[f] > 0 && len2 < zfloor[f] + j.len1)) continue;
-                // (decided before a worker took it up: not queued yet, or queued - by the early group or the speculative list)
+                // (decided before a worker took it up: not queued yet, or queued on the speculative list)
                 uint8_t expect = kZNone;
                 bool struck = zstate[f].compare_exchange_strong(expect, kZSkipped);
                 if (!struck) { expect = kZQueued; struck = zstate[f].compare_exchange_strong(expect, kZSkipped); }

@@ -223,13 +223,11 @@ void launch_trunc_advance(DevChunk *chunks, FrameState *fs, unsigned long long *
 //      outcomes, statement for statement what `levels` iterations of :777-795 do: same cuts consumed in the same order,
 //      same t_lo / t_hi / best error / mean error; the probes off the path are simply not looked at.
 __global__ void k_trunc_advance_multi(DevChunk *chunks, const FrameState *fs, CutSlots cs, int n_chunks, double n_pix, int levels,
-                                      const int *rank, int *unfinished)
+                                      int *unfinished)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_chunks) return;
-    const int r = rank ? rank[f] : f;
-    if (r < 0) return;                                                   // (not in this launch: not a word of it is touched)
-    const int K = (1 << levels) - 1, v0 = r * K;
+    const int K = (1 << levels) - 1, v0 = f * K;
     DevChunk &C = chunks[f];
     if (!C.trunc_active) { for (int i = 0; i < K; i++) cs.active[v0 + i] = 0; return; }
     const double eps = 1e-8;
@@ -273,9 +271,9 @@ __global__ void k_trunc_advance_multi(DevChunk *chunks, const FrameState *fs, Cu
 }
 
 void launch_trunc_advance_multi(DevChunk *chunks, const FrameState *fs, const CutSlots &cs, int n_chunks, double n_pix, int levels,
-                                const int *rank, int *unfinished, hipStream_t s)
+                                int *unfinished, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_trunc_advance_multi, dim3(ceil_div(n_chunks, 64)), dim3(64), 0, s, chunks, fs, cs, n_chunks, n_pix, levels, rank, unfinished);
+    hipLaunchKernelGGL(k_trunc_advance_multi, dim3(ceil_div(n_chunks, 64)), dim3(64), 0, s, chunks, fs, cs, n_chunks, n_pix, levels, unfinished);
     EBCC_HIP_LAUNCH_CHECK();
 }
 

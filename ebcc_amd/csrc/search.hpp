@@ -65,9 +65,9 @@ void launch_search_advance(DevChunk *chunks, J2kFrame *jf, int *d_active, int n_
 void launch_trunc_advance(DevChunk *chunks, FrameState *fs, unsigned long long *trunc_bits, int *d_active, int n_chunks,
                           double n_pix, int *unfinished, hipStream_t s);
 // One round of the bisection with look-ahead: `levels` (1..3) iterations of :777-795 per round from the outcomes of the
-// 2^levels - 1 cuts the previous round proposed (cut slots, residual.hpp); chunk f uses slots rank[f] * K .. (rank null: f;
-// rank[f] < 0: the chunk is not part of this launch).  Writes cs.bits / active / frame_of / fs of its slots.
+// 2^levels - 1 cuts the previous round proposed (cut slots, residual.hpp); chunk f uses slots f * K .. f * K + K - 1.
+// Writes cs.bits / active / frame_of / fs of its slots.
 void launch_trunc_advance_multi(DevChunk *chunks, const FrameState *fs, const CutSlots &cs, int n_chunks, double n_pix, int levels,
-                                const int *rank, int *unfinished, hipStream_t s);
+                                int *unfinished, hipStream_t s);
 
 }  // namespace ebcc

@@ -144,23 +144,28 @@ static double probe(search_t *s, float cr)
     return feasible_fraction(s->data, s->decoded, s->n, s->target);
 }
 
-static float rate_search(search_t *s, float cr, double q_target)
+static float rate_search(search_t *s, float cr, double q_target, orc_search_trace_t *t)
 {
     float lo = cr, hi = cr;
     double q = feasible_fraction(s->data, s->decoded, s->n, s->target);
     double q0 = q;
     const double eps = 1e-8;
-    while (q < q_target && lo >= 1. / 2) { lo /= 2; q = probe(s, lo); }        /* :559-563 */
+    t->ran = 1;
+    while (q < q_target && lo >= 1. / 2) { lo /= 2; q = probe(s, lo); t->n_halve++; }          /* :559-563 */
+    const int floor_hit = q < q_target;
     q = q0;
-    while (q >= q_target && hi <= 1000) { hi *= 2; q = probe(s, hi); }         /* :565-569 */
-    if (q >= q_target) return hi;                                              /* :571-574 */
+    while (q >= q_target && hi <= 1000) { hi *= 2; q = probe(s, hi); t->n_double++; }         /* :565-569 */
+    if (q >= q_target) { t->exit = ORC_EXIT_HI_1000; t->result = hi; return hi; }             /* :571-574 */
     q = q0;
     while ((fabs(q - q_target) > eps || q == 1.0) && hi - lo > 1.) {           /* :579-588 */
         cr = (lo + hi) / 2;
         q = probe(s, cr);
+        t->n_bisect++;
         if (q < q_target) hi = cr; else lo = cr;
     }
-    probe(s, lo);                                                              /* :590 */
+    t->could_not_reach = probe(s, lo) < q_target;                              /* :590-593 */
+    t->exit = floor_hit ? ORC_EXIT_LO_FLOOR : ORC_EXIT_BISECT;
+    t->result = lo;
     return lo;
 }
 
@@ -214,6 +219,15 @@ size_t orc_ebcc_encode(const float *data, const orc_config_t *cfg, uint8_t **out
     float minv, maxv;
     min_max(data, n, &minv, &maxv);
     int const_field = minv == maxv;                                            /* :678 */
+    if (!const_field && (cfg->residual_compression_type == ORC_MAX_ERROR || cfg->residual_compression_type == ORC_RELATIVE_ERROR)
+        && isinf(maxv - minv)) {
+        /* the residual of a base layer decoded as (s / 65535) * inf + min (:1130) is NaN / inf everywhere; the reference
+         * stops on assert(dc0 >= 0 && dc0 <= MAXELEM) in spiht_encode (spiht_re.c:462).  Refused here. */
+        fprintf(stderr, "oracle: max - min overflows float\n");
+        return 0;
+    }
+    if (const_field) g_trace.residual = ORC_RES_CONST;
+    else if (cfg->residual_compression_type == ORC_NONE) g_trace.residual = ORC_RES_MODE_NONE;
 
     int mode = cfg->residual_compression_type;
     uint16_t *scaled = NULL;
@@ -250,12 +264,13 @@ size_t orc_ebcc_encode(const float *data, const orc_config_t *cfg, uint8_t **out
         float cur, best_err; int skip;
 
         if (mode != ORC_MAX_ERROR && mode != ORC_RELATIVE_ERROR) goto after_search;   /* :721 (quirk Q2) */
-        cr = rate_search(&S, cr, q_target);                                    /* :728 */
+        cr = rate_search(&S, cr, q_target, &g_trace.search[0]);               /* :728 */
         for (size_t i = 0; i < n; i++) residual[i] = data[i] - S.decoded[i];
         min_max(residual, n, &rmin, &rmax);
         cur = fmaxf(fabsf(rmin), fabsf(rmax));
         best_err = -1;
         skip = cur <= target;                                              /* :737 */
+        if (skip) g_trace.residual = ORC_RES_SKIP;
         pure_done = q_target == 1.0;                                           /* :738 */
 
         if (!skip) {
@@ -267,15 +282,17 @@ size_t orc_ebcc_encode(const float *data, const orc_config_t *cfg, uint8_t **out
             coeffs_size = coeffs_orig;
             for (size_t i = 0; i < n; i++) residual[i] = rnorm[i] * (rmax - rmin) + rmin;     /* :752 */
             cur = max_abs_error(data, S.decoded, residual, n);
-            if (cur > target) { skip = 1; need_pure = 1; }                     /* :755-759 */
+            if (cur > target) { skip = 1; need_pure = 1; g_trace.residual = ORC_RES_NEED_PURE; }   /* :755-759 */
             else { best_err = cur; mean_err = mean_error(data, S.decoded, residual, n); }
         }
         if (!skip) {
             /* truncation bisection, :765-796 */
             double hi = (double) coeffs_size * 8, lo = 112.0, best = hi;
             const double eps = 1e-8;
+            g_trace.residual = ORC_RES_TRUNC;
             while (((target - best_err) / target > eps) && (hi - lo > 8 * 4)) {
                 size_t tb = ((size_t) ceill((hi + lo) / 2 / 8)) * 8;
+                g_trace.trunc_steps++;
                 orc_spiht_decode(coeffs, tb / 8, rnorm, H, W, tb);
                 g_trace.n_spiht_decodes++;
                 for (size_t i = 0; i < n; i++) residual[i] = rnorm[i] * (rmax - rmin) + rmin;
@@ -292,7 +309,7 @@ size_t orc_ebcc_encode(const float *data, const orc_config_t *cfg, uint8_t **out
             coeffs_size = (size_t) (best / 8.);
         }
 after_search:
-        if (coeffs_size <= 16) coeffs_size = 0;                                /* :811 */
+        if (coeffs_size <= 16) { g_trace.dropped_small = coeffs_size > 0; coeffs_size = 0; }   /* :811 */
         if (coeffs_size > 0) {
             if (!zstd_load()) exit(1);
             zlen = z_bound(coeffs_size);
@@ -311,7 +328,7 @@ after_search:
                 j2k_dec(S.cs, S.cs_len, minv, maxv, &S.decoded, NULL, NULL);
                 cr = cfg->base_cr;
             }
-            rate_search(&S, cr, 1.0);                                          /* :836 */
+            rate_search(&S, cr, 1.0, &g_trace.search[1]);                      /* :836 */
             if (getenv("ORC_DUMP_DIR") && coeffs_size > 0) {                   /* study hook (tools/zstd_bound_study.py): the inputs of the :838 comparison */
                 char path[512];
                 snprintf(path, sizeof path, "%s/dump_%d_%zu.bin", getenv("ORC_DUMP_DIR"), (int) getpid(), (size_t) g_trace.n_j2k_encodes);
@@ -322,6 +339,8 @@ after_search:
                 }
             }
             if (S.cs_len < zlen + tail_len || need_pure) {
+                g_trace.fallback_smaller = S.cs_len < zlen + tail_len;
+                g_trace.fallback_required = need_pure;
                 mean_err = mean_error(data, S.decoded, NULL, n);               /* :843 */
                 zlen = 0; coeffs_size = 0;
                 free(tail);
@@ -337,6 +356,7 @@ after_search:
     free(scaled);
 
     if (!no_mean_adjust && fabs(mean_err) > 1e-18) {                           /* :864-868 */
+        g_trace.mean_adjusted = 1;
         minv += mean_err;
         maxv += mean_err;
     }

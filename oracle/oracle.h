@@ -87,11 +87,33 @@ size_t orc_ebcc_encode_chunking_compat(const float *data, const orc_config_t *co
 size_t orc_ebcc_decode_chunking(const uint8_t *data, size_t data_size, float **out);
 void   orc_free(void *p);
 
-/* trace of the last orc_ebcc_encode call (probe counts etc.) for test diagnostics */
+/* trace of the last orc_ebcc_encode call: probe counts, and which branches of the two error-bound searches
+ * (src/ebcc_codec.c:545-596, :730-854) it took.  Mirrored by tests/_lib.py:OrcTrace. */
+enum { ORC_EXIT_NONE = 0, ORC_EXIT_BISECT = 1, ORC_EXIT_HI_1000 = 2, ORC_EXIT_LO_FLOOR = 3 };
+typedef struct {
+    int ran;                       /* the search was called */
+    int n_halve, n_double, n_bisect;   /* probes of the loops at :559-563, :565-569, :579-588 */
+    int exit;                      /* ORC_EXIT_*: left at :571-574 (cr_hi > 1000, no final probe), or after the
+                                      bisection - _LO_FLOOR if the halving loop stopped at cr_lo < 1/2 while infeasible */
+    int could_not_reach;           /* the final probe (:590) is below the quantile target (:591-593 warning) */
+    float result;                  /* the returned rate */
+} orc_search_trace_t;
+
+enum { ORC_RES_NONE = 0, ORC_RES_CONST = 1, ORC_RES_MODE_NONE = 2, ORC_RES_SKIP = 3, ORC_RES_NEED_PURE = 4,
+       ORC_RES_TRUNC = 5 };
 typedef struct {
     int n_j2k_encodes, n_j2k_decodes, n_spiht_decodes;
     float final_cr;
     size_t coeffs_size, compressed_size, tail_size;
+    /* branch record */
+    orc_search_trace_t search[2];  /* [0] error-bounded search (:728), [1] pure base layer (:836) */
+    int residual;                  /* ORC_RES_*: constant field, NONE mode, base meets the bound (:737), full SPIHT misses
+                                      the target (:755-759), truncation bisection ran (:765-796) */
+    int trunc_steps;               /* cuts the truncation bisection probed */
+    int dropped_small;             /* a prefix of 1..16 bytes was dropped (:811) */
+    int fallback_smaller;          /* :838 pure base layer taken because it is smaller */
+    int fallback_required;         /* :838 pure base layer taken because the residual layer missed the target */
+    int mean_adjusted;             /* :864-868 min / max shifted by the mean error */
 } orc_trace_t;
 void orc_last_trace(orc_trace_t *t);
 

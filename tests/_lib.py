@@ -71,6 +71,7 @@ def oracle():
             f.restype = ctypes.c_size_t
             f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]
         lib.orc_free.argtypes = [ctypes.c_void_p]
+        lib.orc_last_trace.argtypes = [ctypes.c_void_p]
         lib.orc_j2k_encode.restype = ctypes.c_size_t
         lib.orc_j2k_encode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_float, c_void_pp]
         lib.orc_j2k_decode.restype = ctypes.c_size_t
@@ -132,6 +133,70 @@ def orc_encode(data, cfg, fn="orc_ebcc_encode"):
     if n == 0:
         return b""
     return _take(lib, out, n, lib.orc_free)
+
+
+class OrcSearchTrace(ctypes.Structure):
+    """orc_search_trace_t (oracle/oracle.h): one call of the rate search, src/ebcc_codec.c:545-596."""
+    _fields_ = [("ran", ctypes.c_int), ("n_halve", ctypes.c_int), ("n_double", ctypes.c_int), ("n_bisect", ctypes.c_int),
+                ("exit", ctypes.c_int), ("could_not_reach", ctypes.c_int), ("result", ctypes.c_float)]
+
+
+class OrcTrace(ctypes.Structure):
+    """orc_trace_t (oracle/oracle.h): what the last orc_ebcc_encode did."""
+    _fields_ = [
+        ("n_j2k_encodes", ctypes.c_int), ("n_j2k_decodes", ctypes.c_int), ("n_spiht_decodes", ctypes.c_int),
+        ("final_cr", ctypes.c_float),
+        ("coeffs_size", ctypes.c_size_t), ("compressed_size", ctypes.c_size_t), ("tail_size", ctypes.c_size_t),
+        ("search", OrcSearchTrace * 2),
+        ("residual", ctypes.c_int), ("trunc_steps", ctypes.c_int),
+        ("dropped_small", ctypes.c_int), ("fallback_smaller", ctypes.c_int), ("fallback_required", ctypes.c_int),
+        ("mean_adjusted", ctypes.c_int),
+    ]
+
+
+EXIT_NAMES = {0: "none", 1: "bisect", 2: "hi_1000", 3: "lo_floor"}
+RESIDUAL_NAMES = {0: "unset", 1: "const", 2: "mode_none", 3: "skip", 4: "need_pure", 5: "trunc"}
+
+
+def trace():
+    """The branch record of the last orc_encode (single frame) as a plain dict (JSON-ready)."""
+    t = OrcTrace()
+    oracle().orc_last_trace(ctypes.byref(t))
+    d = {k: getattr(t, k) for k, _ in OrcTrace._fields_ if k != "search"}
+    d["final_cr"] = float(d["final_cr"])
+    d["residual"] = RESIDUAL_NAMES[t.residual]
+    d["search"] = [{"ran": s.ran, "n_halve": s.n_halve, "n_double": s.n_double, "n_bisect": s.n_bisect,
+                    "exit": EXIT_NAMES[s.exit], "could_not_reach": s.could_not_reach, "result": float(s.result)}
+                   for s in t.search]
+    return d
+
+
+_reference = None
+
+
+def reference():
+    """The reference build (oracle/_ref/libh5z_ebcc_ref.so), or None where it was not built."""
+    global _reference
+    if _reference is None and os.path.exists(REF_SO):
+        lib = ctypes.CDLL(REF_SO)
+        lib.ebcc_encode.restype = ctypes.c_size_t
+        lib.ebcc_encode.argtypes = [ctypes.c_void_p, ctypes.POINTER(CodecConfig), c_void_pp]
+        lib.ebcc_decode.restype = ctypes.c_size_t
+        lib.ebcc_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]
+        lib.free_buffer.argtypes = [ctypes.c_void_p]
+        _reference = lib
+    return _reference
+
+
+def ref_encode(data, cfg):
+    """ebcc_encode of the reference build (b"" when it refuses the input)."""
+    lib = reference()
+    data = np.ascontiguousarray(data, np.float32)
+    out = ctypes.c_void_p()
+    n = lib.ebcc_encode(data.ctypes.data, ctypes.byref(cfg), ctypes.byref(out))
+    if n == 0:
+        return b""
+    return _take(lib, out, n, lib.free_buffer)
 
 
 def orc_decode(stream, fn="orc_ebcc_decode"):

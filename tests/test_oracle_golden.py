@@ -277,3 +277,27 @@ def test_oracle_env_switches_match_reference(switch, monkeypatch):
             out = ctypes.c_void_p()
             n = ref.ebcc_encode(frame.ctypes.data, ctypes.byref(cfg), ctypes.byref(out))
             assert ctypes.string_at(out.value, n) == s, switch
+
+
+_branches = load("search_branches.json")["cases"]
+
+
+def test_search_branch_streams():
+    """The catalogue of tests/_domains.py (value domains x error targets x start rates x quantiles): oracle streams ==
+    the reference build's as stored (oracle/make_golden_branches.py), inputs as generated when the fixture was made."""
+    from tests import _domains as D
+    L.oracle().orc_set_j2k_backend(0)
+    old = os.environ.pop("EBCC_INIT_BASE_ERROR_QUANTILE", None)
+    try:
+        for c in D.catalogue():
+            want = _branches[c.name]
+            if c.quantile is not None:
+                os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"] = c.quantile
+            x = c.field()
+            assert sha(x.tobytes()) == want["field_sha256"], c.name
+            s = L.orc_encode(x, c.config(x))
+            os.environ.pop("EBCC_INIT_BASE_ERROR_QUANTILE", None)
+            assert len(s) == want["n"] and sha(s) == want["stream_sha256"], c.name
+    finally:
+        if old is not None:
+            os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"] = old
