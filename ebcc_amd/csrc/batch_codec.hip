@@ -1,57 +1,21 @@
 // batch_codec.hip - one device batch of the frame codec (host.hpp): /root/reference/src/ebcc_codec.c:607-918 as
 // encode_batch, :1215-1320 as decode_batch / decode_tiled, with the rate search (:545-596, twice per frame) and the
-// truncation bisection (:765-796) either as host loops or as device-side state machines (search.hpp).  The host only
-// steers: per-frame scalars come back from the device after every search, every per-sample operation runs in the kernels.
+// truncation bisection (:765-796) as device-side state machines (search.hpp).  The host only steers: per-frame scalars
+// come back from the device after every search, every per-sample operation runs in the kernels.
 #include "host.hpp"
 
 namespace ebcc {
 namespace {
 
-// ================================================================================================
-// rate search of src/ebcc_codec.c:545-596 as a resumable state machine (one probe per step)
-// ================================================================================================
-struct RateSearch {
-    float lo = 0, hi = 0, cr = 0, result = 0;
-    double q = 0, q0 = 0, qt = 0;
-    int phase = 4;           // 0 halving, 1 doubling, 2 bisect, 3 final probe, 4 done
-    float pending = 0;
-    void start(float cr0, double q_init, double q_target)
-    {
-        lo = hi = cr = cr0; q = q0 = q_init; qt = q_target; phase = 0;
-    }
-    bool done() const { return phase == 4; }
-    // returns true and sets `out` if a probe at rate `out` is needed next
-    bool next(float &out)
-    {
-        for (;;) {
-            if (phase == 0) {
-                if (q < qt && lo >= 1. / 2) { lo /= 2; out = pending = lo; return true; }      // :559-563
-                q = q0; phase = 1;
-            } else if (phase == 1) {
-                if (q >= qt && hi <= 1000) { hi *= 2; out = pending = hi; return true; }       // :565-569
-                if (q >= qt) { result = hi; phase = 4; return false; }                         // :571-574
-                q = q0; phase = 2;
-            } else if (phase == 2) {
-                const double eps = 1e-8;
-                if ((std::fabs(q - qt) > eps || q == 1.0) && hi - lo > 1.) {                   // :579-588
-                    cr = (lo + hi) / 2; out = pending = cr; return true;
-                }
-                phase = 3; out = pending = lo; return true;                                    // :590
-            } else {
-                return false;
-            }
-        }
-    }
-    void feed(double quantile)
-    {
-        q = quantile;
-        if (phase == 2) { if (q < qt) hi = cr; else lo = cr; }
-        else if (phase == 3) { result = lo; phase = 4; }
-    }
-};
-
-
-struct ProbeRec { float cr = -1; unsigned long long nbad = 0; int stream_bytes = 0; double err_sum = 0; bool complete = true; };
+// rate search k's state before its first round (:545-596 entered at rate cr0 with the quantile q_init of a probe there):
+// phase 0, nothing pending, no probe asked for, no final probe yet
+DevRateSearch rate_search_start(float cr0, double q_init, double q_target)
+{
+    DevRateSearch r{};
+    r.lo = r.hi = r.cr = cr0; r.q = r.q0 = q_init; r.qt = q_target;
+    r.last.cr = -1; r.last.complete = 1;
+    return r;
+}
 
 struct Job {                     // host-side state of one frame being encoded
     bool const_field = false;
@@ -64,18 +28,11 @@ struct Job {                     // host-side state of one frame being encoded
     double t_hi = 0, t_lo = 0, t_best = 0;
     bool trunc_active = false;
     std::vector<uint8_t> tail, zbytes;
-    // rate searches: [0] error-bounded (:728), [1] pure base layer (:836).  A probe's outcome depends only on
-    // (frame, rate), so both searches share one record of the probes made so far.
-    RateSearch rs[2];
-    bool want[2] = {false, false};    // search k waits for the probe at want_cr[k]
-    float want_cr[2] = {0, 0};
-    ProbeRec last[2];                 // the final probe of search k (phase 3)
-    std::vector<ProbeRec> probes;
-    const ProbeRec *find_probe(float cr) const
-    {
-        for (const ProbeRec &r : probes) if (r.cr == cr) return &r;
-        return nullptr;
-    }
+    // rate searches: [0] error-bounded (:728), [1] pure base layer (:836), in the device's layout; rs[k].last is the probe
+    // search k's result rests on.  A probe's outcome depends only on (frame, rate), so both searches share one record of
+    // the probes made so far.
+    DevRateSearch rs[2] = {};
+    std::vector<DevProbe> probes;
 };
 
 // The base layer of a batch of chunks.  A chunk is one frame, or `tiles` frames stacked along the row axis that
@@ -143,16 +100,20 @@ struct Batch {
         for (size_t c = 0; c < n; c++) ractive[c] = active[c];
         EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_active, ractive, sizeof(int) * n, hipMemcpyHostToDevice, rs));
     }
-    // one probe of the base layer for the active chunks: rate allocation at jf[c].cr (+ decode and statistics)
-    // keep_field = false: only the statistics are wanted, jb.DEC stays what it was
-    void launch_probe(bool decode, bool keep_field = true)
+    // the layer assignment of the active chunks at rate jf[c].cr
+    void allocate()
     {
         push_jf();
         push_active();
         launch_j2k_rate(jb, (int) nt, d_active, s);
-        if (decode) launch_j2k_probe_decode(d_frames, jb, (int) nt, d_active, s, keep_field);
     }
-    void probe(bool decode, bool keep_field = true) { launch_probe(decode, keep_field); fetch_jf(); }
+    // one probe of the base layer for the active chunks: the allocation (+ decode and statistics)
+    void probe(bool decode)
+    {
+        allocate();
+        if (decode) launch_j2k_probe_decode(d_frames, jb, (int) nt, d_active, s);
+        fetch_jf();
+    }
     // codestream of the current layer assignment of the active chunks -> jobs[c].tail
     template <class Jobs>
     void collect_tails(Jobs &jobs)
@@ -200,92 +161,178 @@ struct Batch {
     }
 };
 
-// Drive rate search k (0: error-bounded :728, 1: pure base layer :836) of every frame to completion; every
-// round runs at most one probe per frame.  A search first advances through the probes already on record for its
-// frame (the other search, or the first encode, usually made them) and only asks the GPU for rates not seen yet.
-// The final probe of search 0 (:590) must leave its decode in the engine - the residual layer is computed from
-// it - so it is re-run unless the engine's last decode of the frame was at exactly that rate.
-template <class Jobs>
-void run_search(Batch &b, int k, Jobs &jobs, size_t n_pix)
-{
-    const size_t n = b.n;
-    auto needs_state = [&](const Job &j, size_t f, float cr) { return k == 0 && j.rs[0].phase == 3 && b.state_cr[f] != cr; };
-    auto feed = [&](Job &j, const ProbeRec &rec) {
-        RateSearch &rs = j.rs[k];
-        if (rs.phase == 3) j.last[k] = rec;
-        const double q = 1. - ((double) rec.nbad / (double) n_pix);                            // :512
-        if (k == 0) j.q = q;
-        rs.feed(q);
-    };
-    for (;;) {
-        bool any = false;
-        for (size_t f = 0; f < n; f++) {
-            Job &j = jobs[f];
-            b.active[f] = 0;
-            if (j.const_field) continue;
-            while (!j.want[k] && !j.rs[k].done()) {
-                float cr;
-                if (!j.rs[k].next(cr)) break;
-                const ProbeRec *rec = j.find_probe(cr);
-                if (rec && !needs_state(j, f, cr)) feed(j, *rec);
-                else { j.want[k] = true; j.want_cr[k] = cr; }
-            }
-            if (j.want[k]) { b.active[f] = 1; b.jf[f].cr = j.want_cr[k]; any = true; }
-        }
-        if (!any) break;
-        b.probe(true, k == 0);                                   // (search 1 uses the statistics only: the field of search 0 stays)
-        for (size_t f = 0; f < n; f++) {
-            if (!b.active[f]) continue;
-            Job &j = jobs[f];
-            const J2kFrame &r = b.jf[f];
-            if (k == 0) b.state_cr[f] = r.cr;
-            if (!j.find_probe(r.cr)) j.probes.push_back(ProbeRec{r.cr, r.nbad, r.stream_bytes, r.err_sum});
-            log_trace("frame %zu (search %d): cr %f 1-quantile %.1e jp2_length %d", f, k, r.cr, (double) r.nbad / (double) n_pix,
-                      r.stream_bytes);
-            feed(j, *j.find_probe(r.cr));
-            j.want[k] = false;
-        }
-    }
-    // A search that leaves through the rate > 1000 exit (:571-574) makes no final probe: its result is the last
-    // doubling step.  Take that probe's record, and for search 0 make sure its decode is in the engine.
-    bool redo = false;
-    for (size_t f = 0; f < n; f++) {
-        Job &j = jobs[f];
-        b.active[f] = 0;
-        if (j.const_field) continue;
-        if (j.last[k].cr != j.rs[k].result)
-            if (const ProbeRec *rec = j.find_probe(j.rs[k].result)) j.last[k] = *rec;
-        if (k == 0 && b.state_cr[f] != j.rs[0].result) { b.active[f] = 1; b.jf[f].cr = j.rs[0].result; redo = true; }
-    }
-    if (redo) {
-        b.probe(true);
-        for (size_t f = 0; f < n; f++)
-            if (b.active[f]) {
-                const J2kFrame &r = b.jf[f];
-                b.state_cr[f] = r.cr;
-                jobs[f].last[0] = ProbeRec{r.cr, r.nbad, r.stream_bytes, r.err_sum};
-            }
-    }
-}
-
-// The same search with its state machine on the device (search.hpp): the rounds are enqueued back to back - advance,
-// rate allocation, probe decode - without a host synchronisation in between; the host looks at the states once after
-// `rounds` of them (EBCC_HIP_SEARCH_ROUNDS, default 16: more than the usual search needs) and only enqueues more if a
-// chunk is still searching.  Same probes, same decisions, same result as run_search (EBCC_HIP_HOST_SEARCH=1 selects that).
-int search_rounds()
-{
-    if (const char *e = getenv("EBCC_HIP_SEARCH_ROUNDS")) return std::max(1, atoi(e));
-    return 16;
-}
+int search_rounds() { const char *e = getenv("EBCC_HIP_SEARCH_ROUNDS"); return e ? std::max(1, atoi(e)) : 16; }
 constexpr int kSearchAll = 0, kSearchStart = 1, kSearchFinish = 2;
-template <class Jobs>
-void device_rate_search(Batch &b, int k, Jobs &jobs, size_t n_pix, unsigned slices, int lane = 0, int part = kSearchAll)
+
+// The entropy stage of a batch (:811-817): level-22 zstd of the kept SPIHT prefixes and lower bounds of their compressed
+// sizes (zstd_size_lower_bound), as jobs on the process-wide pool (HostPool) - every slice of a batch feeds the same
+// workers, so the host is never oversubscribed however many slices run.  The workers write into the batch's jobs and
+// hold `this`: an Entropy lives inside the jobs' lifetime, stays where it is, and waits for its jobs when it goes (error
+// paths too).
+struct Entropy {
+    enum : uint8_t { kNone = 0, kQueued = 1, kRunning = 2, kSkipped = 3 };
+    using PoolBatches = std::vector<std::shared_ptr<HostPool::Batch>>;
+    std::vector<Job> &jobs;
+    const unsigned slices;
+    const int level;
+    const bool timing, trace;                                       // EBCC_HIP_PHASE_TIMING; EBCC_HIP_ZSTD_TRACE as well
+    std::vector<const uint8_t *> coeff_ptr;                         // the kept prefix of a frame in pinned host memory
+    std::unique_ptr<std::atomic<uint8_t>[]> zstate;
+    std::vector<size_t> zfloor;                                     // lower bound of z (0: none)
+    std::atomic<long long> zstd_us{0}, zstd_max_us{0}, zstd_bytes{0}, bound_us{0};    // core time, longest job, bytes
+    long long wait_us = 0;
+    PoolBatches zbatches, fbatches;                                 // level-22 jobs; lower bounds
+
+    Entropy(std::vector<Job> &j, unsigned slices_, int level_, bool timing_)
+        : jobs(j), slices(slices_), level(level_), timing(timing_), trace(timing_ && getenv("EBCC_HIP_ZSTD_TRACE")),
+          coeff_ptr(j.size(), nullptr), zstate(new std::atomic<uint8_t>[j.size()]), zfloor(j.size(), 0)
+    { for (size_t f = 0; f < j.size(); f++) zstate[f] = kNone; }
+    Entropy(const Entropy &) = delete; Entropy &operator=(const Entropy &) = delete;
+    ~Entropy() { for (PoolBatches *v : {&fbatches, &zbatches}) for (auto &b : *v) if (b) b->wait(); }
+
+    // level-22 zstd of the frames in `list`, in the order given; a frame that was decided in the meantime (kSkipped) is
+    // passed over
+    void submit_zstd(std::vector<size_t> list)
+    {
+        if (trace) fprintf(stderr, "zstd-submit batch %p jobs %zu\n", (const void *) &jobs, list.size());
+        for (size_t f : list) zstate[f] = kQueued;
+        auto order = std::make_shared<std::vector<size_t>>(std::move(list));
+        zbatches.push_back(HostPool::instance().submit(order->size(), entropy_threads(slices), [this, order](size_t i) {
+            const size_t f = (*order)[i];
+            uint8_t expect = kQueued;
+            if (!zstate[f].compare_exchange_strong(expect, kRunning)) return;
+            Job &j = jobs[f];
+            const auto z0 = std::chrono::steady_clock::now();
+            j.zbytes.resize(zstd().bound(j.coeffs_size));
+            const size_t z = zstd().compress(j.zbytes.data(), j.zbytes.size(), coeff_ptr[f], j.coeffs_size, level);
+            if ((zstd().is_error && zstd().is_error(z)) || z > j.zbytes.size()) throw std::runtime_error("ZSTD_compress failed on a residual prefix");
+            j.zbytes.resize(z);
+            const long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - z0).count();
+            if (trace) {                                                // (when each job ran, on which CPU)
+                static const auto epoch = std::chrono::steady_clock::now();
+                const long long a = std::chrono::duration_cast<std::chrono::microseconds>(z0 - epoch).count();
+                fprintf(stderr, "zstd-job batch %p bytes %zu start %lld us end %lld us cpu %d\n", (const void *) &jobs, j.coeffs_size, a, a + us, sched_getcpu());
+            }
+            zstd_us += us; zstd_bytes += (long long) j.coeffs_size;
+            long long m = zstd_max_us.load(); while (us > m && !zstd_max_us.compare_exchange_weak(m, us)) {}
+        }));
+    }
+    // the lower bounds of z for the frames in `frames`
+    void submit_floors(const std::vector<size_t> &frames)
+    {
+        auto list = std::make_shared<std::vector<size_t>>(frames);
+        fbatches.push_back(HostPool::instance().submit(list->size(), entropy_threads(slices), [this, list](size_t i) {
+            const size_t f = (*list)[i];
+            const auto z0 = std::chrono::steady_clock::now();
+            zfloor[f] = zstd_size_lower_bound(coeff_ptr[f], jobs[f].coeffs_size);
+            bound_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - z0).count();
+        }));
+    }
+    // longest first: level 22 takes ~0.2 ms per KB on one core and a batch has frames whose prefix is ten times the
+    // average - started last, such a frame alone decides when the slice can go on
+    std::vector<size_t> longest_first(std::vector<size_t> list) const
+    {
+        std::stable_sort(list.begin(), list.end(), [&](size_t a, size_t c) { return jobs[a].coeffs_size > jobs[c].coeffs_size; });
+        return list;
+    }
+    // lowest floor per byte first: the order in which the frames are likely to need their z
+    std::vector<size_t> lowest_floor_first(std::vector<size_t> list) const
+    {
+        std::stable_sort(list.begin(), list.end(), [&](size_t a, size_t c) {
+            return (double) zfloor[a] * (double) jobs[c].coeffs_size < (double) zfloor[c] * (double) jobs[a].coeffs_size; });
+        return list;
+    }
+    std::vector<size_t> not_started(std::vector<size_t> v) const   // (frames already queued or decided are dropped)
+    {
+        v.erase(std::remove_if(v.begin(), v.end(), [&](size_t f) { return zstate[f] != kNone; }), v.end());
+        return v;
+    }
+    // z >= zfloor: len2 < zfloor + len1 implies len2 < z + len1 - the base layer alone wins (:838), whatever z is
+    bool floor_decides(size_t f) const { return zfloor[f] > 0 && (size_t) jobs[f].rs[1].last.stream_bytes < zfloor[f] + jobs[f].len1; }
+    // a frame decided before a worker took it up (not queued yet, or queued on the speculative list) is not compressed
+    bool strike(size_t f)
+    {
+        uint8_t expect = kNone;
+        if (zstate[f].compare_exchange_strong(expect, kSkipped)) return true;
+        expect = kQueued;
+        return zstate[f].compare_exchange_strong(expect, kSkipped);
+    }
+    bool join(PoolBatches &v)
+    {
+        const auto w0 = std::chrono::steady_clock::now();
+        bool ok = true;
+        std::string why;
+        for (auto &b : v) if (b && !b->wait()) { ok = false; if (why.empty()) why = b->error; }
+        v.clear();
+        wait_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - w0).count();
+        if (!ok) { log_fatal("entropy stage failed: %s", why.c_str()); set_error("%s", why.c_str()); }
+        return ok;
+    }
+    bool join_floors() { return join(fbatches); }
+    bool join_all() { const bool a = join(fbatches), c = join(zbatches); return a && c; }
+    // the stage's totals (EBCC_HIP_PHASE_TIMING) and every prefix's sizes and fate (EBCC_HIP_ZSTD_TRACE)
+    void report(const std::vector<size_t> &with_prefix, long long skipped, long long skipped_bytes) const
+    {
+        if (timing) fprintf(stderr, "ebcc-mi355x zstd: %.1f ms of core time for %lld bytes, longest job %.1f ms; floors %.1f ms; %lld of %zu prefixes (%lld bytes) not compressed\n",
+                            zstd_us.load() / 1e3, zstd_bytes.load(), zstd_max_us.load() / 1e3, bound_us.load() / 1e3, skipped, with_prefix.size(), skipped_bytes);
+        host_stats().skipped_bytes += skipped_bytes;
+        if (trace)
+            for (size_t f : with_prefix) {
+                const Job &j = jobs[f];
+                const long long x = (long long) j.rs[1].last.stream_bytes - (long long) j.len1;
+                fprintf(stderr, "zstd-trace c %zu floor %zu X %lld z %zu state %d need_pure %d nbad1 %llu len1 %zu orig %zu\n", j.coeffs_size, zfloor[f], x, j.zbytes.size(), (int) zstate[f].load(), (int) j.need_pure,
+                        (unsigned long long) j.rs[0].last.nbad, j.len1, j.coeffs_orig);
+            }
+    }
+};
+
+// One call of encode_batch: the batch, the jobs of its chunks and what every phase reads.  The phases are the steps of
+// the reference's ebcc_encode in its order, each headed by the lines it restates; their host synchronisations, uploads
+// and launches are the slice schedule the codec was measured with.
+struct BatchEncode {
+    struct Gate { SliceGate *g; void release() { if (g) { g->release(); g = nullptr; } } ~Gate() { release(); } } next;   // (error paths too)
+    struct NoteOnce { PhaseNote *n; void tell() { if (n) { n->slice_done(); n = nullptr; } } ~NoteOnce() { tell(); } } gpu_phase_over;   // (every path reports once)
+    const EncodeEnv env;
+    const codec_config_t *cfg;
+    const int mode;
+    const bool searching;
+    const double q_target;
+    const bool want_pure;                                           // the pure base-layer fallback runs (:738)
+    const size_t n, n_pix;                                          // chunks, pixels of a chunk
+    const unsigned slices;
+    Batch b;
+    const bool overlap2;                                            // search #2 beside the residual layer (queue_search_2)
+    std::vector<Job> jobs;
+    PhaseTimer pt;
+    bool any_resid = false;                                         // a chunk needs the residual layer
+    bool search2_queued = false;                                    // rounds of search #2 are in flight on the second stream
+
+    BatchEncode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_, const codec_config_t *cfg_, SliceGate *next_, size_t tiles,
+                ebcc_hip_ctx *rctx, unsigned slices_, PhaseNote *note)
+        : next{next_}, gpu_phase_over{note}, cfg(cfg_), mode((int) cfg_->residual_compression_type),
+          searching(mode == MAX_ERROR || mode == RELATIVE_ERROR), q_target(1 - env.base_error_quantile),
+          want_pure(q_target != 1.0 && !env.no_fallback), n(n_), n_pix(ctx->n_pix * tiles), slices(slices_),
+          b(ctx, d_frames, n_, tiles, rctx), overlap2(want_pure && tiles == 1 && b.rc == ctx), jobs(n_) {}
+    // an error return between the two halves of search #2 must not leave its rounds in flight
+    ~BatchEncode() { if (search2_queued && b.ctx->stream2) hipStreamSynchronize(b.ctx->stream2); }
+
+    // the phases, in the reference's order
+    int analyse(); void first_probe(); void search_1(); void queue_search_2(); bool residual_layer(); void truncation_search();
+    bool entropy_and_fallback(); int assemble(uint8_t **outs, size_t *sizes);
+    void start_search_2();
+    void rate_search(int k, int lane = 0, int part = kSearchAll);
+};
+
+// Rate search k (0: error-bounded :728, 1: pure base layer :836) of every chunk with its state machine on the device
+// (search.hpp): the rounds are enqueued back to back - advance, rate allocation, probe decode - without a host
+// synchronisation in between; the host looks at the states once after `rounds` of them (EBCC_HIP_SEARCH_ROUNDS, default
+// 16: more than the usual search needs) and only enqueues more if a chunk is still searching.
+// lane 1: the search runs on the engine's second stream with its own state, counters and active mask, beside whatever
+// the first stream does (search #2 beside the residual layer).  part: enqueue the first batch of rounds only
+// (kSearchStart: no host synchronisation), or take the search up from there (kSearchFinish), or both.
+void BatchEncode::rate_search(int k, int lane, int part)
 {
-    // lane 1: the search runs on the engine's second stream with its own state, counters and active mask, beside whatever
-    // the first stream does (search #2 beside the residual layer).  part: enqueue the first batch of rounds only
-    // (kSearchStart: no host synchronisation), or take the search up from there (kSearchFinish), or both.
     ebcc_hip_ctx *ctx = b.ctx;
-    const size_t n = b.n;
     DevChunk *h = static_cast<DevChunk *>(ctx->h_search) + (size_t) lane * ctx->max_frames, *d = static_cast<DevChunk *>(ctx->d_search) + (size_t) lane * ctx->max_frames;
     int *const d_counter = ctx->d_counter + 4 * lane, *const h_counter = ctx->h_counter + 4 * lane;
     int *const d_active = lane ? ctx->d_active + ctx->max_frames : b.d_active;
@@ -321,41 +368,38 @@ void device_rate_search(Batch &b, int k, Jobs &jobs, size_t n_pix, unsigned slic
         }
     };
     if (part != kSearchFinish) {
-    for (size_t f = 0; f < n; f++) {
-        const Job &j = jobs[f];
-        DevChunk &c = h[f];
-        c.const_field = j.const_field ? 1 : 0;
-        c.state_cr = b.state_cr[f];
-        c.q = j.q;
-        c.n_probes = (int) std::min<size_t>(j.probes.size(), kMaxProbes);
-        for (int i = 0; i < c.n_probes; i++) c.probes[i] = DevProbe{j.probes[i].cr, j.probes[i].stream_bytes, j.probes[i].nbad, j.probes[i].err_sum, j.probes[i].complete ? 1 : 0, 0};
-        const RateSearch &r = j.rs[k];
-        DevRateSearch &o = c.rs[k];
-        o.lo = r.lo; o.hi = r.hi; o.cr = r.cr; o.result = r.result; o.pending = r.pending; o.phase = j.const_field ? 6 : r.phase;
-        o.q = r.q; o.q0 = r.q0; o.qt = r.qt; o.want = 0; o.want_cr = 0;
-        o.last = DevProbe{j.last[k].cr, j.last[k].stream_bytes, j.last[k].nbad, j.last[k].err_sum, 1, 0};
-    }
-    EBCC_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevChunk) * n, hipMemcpyHostToDevice, s));
-    EBCC_HIP_CHECK(hipMemsetAsync(d_counter, 0, sizeof(int) * 4, s));
-    // a round = the probe the previous advance asked for (rate allocation + decode of the active chunks), then the advance
-    // that takes it in and asks for the next one.  Speculative rate allocation: a
-    // step of the search can go two ways, so the layers of both rates it may ask for next are worked out on the engine's
-    // second stream while the first stream decodes the current probe; the advance then takes the matching one over
-    // (k_rate_publish) and the round's own k_rate only runs for the frames whose rate was not among the guesses.
-    // It shortens a slice's chain (search #1 of 256 frames in one slice: 33 -> 29 ms) at the price of two more k_rate per
-    // round; with several slices in flight the chip has no idle issue slots left to pay with (four slices: encode 7.7 GB/s
-    // without, 6.7 with) - so it is on for a batch that runs as one slice, off otherwise; EBCC_HIP_SPECULATION=1 / 0 forces it.
-    if (speculate) {
-        s2 = second_stream(ctx);
-        if (!ctx->ev_a) {
-            EBCC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_a, hipEventDisableTiming));
-            EBCC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_b, hipEventDisableTiming));
+        for (size_t f = 0; f < n; f++) {
+            const Job &j = jobs[f];
+            DevChunk &c = h[f];
+            c.const_field = j.const_field ? 1 : 0;
+            c.state_cr = b.state_cr[f];
+            c.q = j.q;
+            c.n_probes = (int) std::min<size_t>(j.probes.size(), kMaxProbes);
+            std::copy_n(j.probes.begin(), c.n_probes, c.probes);
+            c.rs[k] = j.rs[k];
+            if (j.const_field) c.rs[k].phase = 6;
         }
-        EBCC_HIP_CHECK(hipMemsetAsync(jb.cand_cr, 0xFF, sizeof(float) * 2 * b.nt, s));       // (NaN: no candidate matches)
-        EBCC_HIP_CHECK(hipMemsetAsync(jb.have_rate, 0, sizeof(int) * b.nt, s));
-    }
-    advance();
-    enqueue_rounds(search_rounds());
+        EBCC_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevChunk) * n, hipMemcpyHostToDevice, s));
+        EBCC_HIP_CHECK(hipMemsetAsync(d_counter, 0, sizeof(int) * 4, s));
+        // a round = the probe the previous advance asked for (rate allocation + decode of the active chunks), then the advance
+        // that takes it in and asks for the next one.  Speculative rate allocation: a
+        // step of the search can go two ways, so the layers of both rates it may ask for next are worked out on the engine's
+        // second stream while the first stream decodes the current probe; the advance then takes the matching one over
+        // (k_rate_publish) and the round's own k_rate only runs for the frames whose rate was not among the guesses.
+        // It shortens a slice's chain (search #1 of 256 frames in one slice: 33 -> 29 ms) at the price of two more k_rate per
+        // round; with several slices in flight the chip has no idle issue slots left to pay with (four slices: encode 7.7 GB/s
+        // without, 6.7 with) - so it is on for a batch that runs as one slice, off otherwise; EBCC_HIP_SPECULATION=1 / 0 forces it.
+        if (speculate) {
+            s2 = second_stream(ctx);
+            if (!ctx->ev_a) {
+                EBCC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_a, hipEventDisableTiming));
+                EBCC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_b, hipEventDisableTiming));
+            }
+            EBCC_HIP_CHECK(hipMemsetAsync(jb.cand_cr, 0xFF, sizeof(float) * 2 * b.nt, s));       // (NaN: no candidate matches)
+            EBCC_HIP_CHECK(hipMemsetAsync(jb.have_rate, 0, sizeof(int) * b.nt, s));
+        }
+        advance();
+        enqueue_rounds(search_rounds());
     }
     if (part == kSearchStart) return;
     if (speculate && !s2) s2 = second_stream(ctx);
@@ -379,52 +423,22 @@ void device_rate_search(Batch &b, int k, Jobs &jobs, size_t n_pix, unsigned slic
         Job &j = jobs[f];
         if (j.const_field) continue;
         const DevChunk &c = h[f];
-        const DevRateSearch &o = c.rs[k];
-        RateSearch &r = j.rs[k];
-        r.lo = o.lo; r.hi = o.hi; r.cr = o.cr; r.result = o.result; r.pending = o.pending; r.phase = 4; r.q = o.q; r.q0 = o.q0; r.qt = o.qt;
-        j.last[k] = ProbeRec{o.last.cr, o.last.nbad, o.last.stream_bytes, o.last.err_sum};
+        j.rs[k] = c.rs[k];
         if (k == 0) j.q = c.q;
-        j.probes.clear();
-        for (int i = 0; i < c.n_probes; i++) j.probes.push_back(ProbeRec{c.probes[i].cr, c.probes[i].nbad, c.probes[i].stream_bytes, c.probes[i].err_sum, c.probes[i].complete != 0});
+        j.probes.assign(c.probes, c.probes + c.n_probes);
         b.state_cr[f] = c.state_cr;
     }
     b.fetch_jf(s);                                                        // (the host mirror of the per-frame scalars follows the device again)
 }
-template <class Jobs>
-void rate_search(Batch &b, int k, Jobs &jobs, size_t n_pix, unsigned slices)
+
+
+// ---- :671-692: statistics, scaling, transform, tier-1 - once per frame.  NaN / Inf and a range that overflows float
+//      refuse the batch (2, 1); 0: the chunks are analysed, their jobs hold min / max / target
+int BatchEncode::analyse()
 {
-    const bool host_loop = getenv("EBCC_HIP_HOST_SEARCH") != nullptr;
-    if (host_loop) run_search(b, k, jobs, n_pix); else device_rate_search(b, k, jobs, n_pix, slices);
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------
-// ebcc_encode for a batch of device-resident single-frame chunks.  Returns 0, 1 (error) or 2 (NaN/Inf).
-// ------------------------------------------------------------------------------------------------
-// `n` chunks of `tiles` frames each (tiles == 1: the frame-per-chunk case); `rctx`: residual engine for the stacked
-// chunk image when tiles > 1.
-int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
-                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, unsigned slices, PhaseNote *note)
-{
-    struct Release { SliceGate *g; ~Release() { if (g) g->release(); } } release_on_exit{next};   // (error paths too)
-    struct NoteOnce { PhaseNote *n; void tell() { if (n) { n->slice_done(); n = nullptr; } } ~NoteOnce() { tell(); } } gpu_phase_over{note};   // (every path reports once)
-    const EncodeEnv env;
-    const double q_target = 1 - env.base_error_quantile;
-    const int mode = (int) cfg->residual_compression_type;
-    const bool searching = mode == MAX_ERROR || mode == RELATIVE_ERROR;
-    const size_t n_pix = ctx->n_pix * tiles;                           // pixels of a chunk
-    const size_t nt = n * tiles;
-    Batch b(ctx, d_frames, n, tiles, rctx);
-    J2kBuffers &jb = b.jb;
-    hipStream_t s = b.s;
-    ebcc_hip_ctx *rc = b.rc;                                           // residual engine and its stream (== ctx, s for one-frame chunks)
-    hipStream_t rs = b.rs;
-    std::vector<Job> jobs(n);
-    PhaseTimer pt;
-
-    // ---- statistics, scaling, transform, tier-1: once per frame
-    launch_input_stats(d_frames, (int) nt, ctx->n_pix, ctx->rb.fs, s);
+    ebcc_hip_ctx *ctx = b.ctx, *rc = b.rc;
+    const size_t tiles = b.tiles, nt = b.nt;
+    launch_input_stats(b.d_frames, (int) nt, ctx->n_pix, ctx->rb.fs, b.s);
     if (tiles > 1) {
         // the reference scales the whole chunk with one (min, max) (:686-689): combine the tiles' statistics before
         // the transform reads them; a tile that happens to be constant inside a varying chunk is coded normally
@@ -438,11 +452,11 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         }
         push_frame_states(ctx, nt);
     }
-    launch_j2k_analysis(d_frames, jb, (int) nt, s);
-    if (next) { next->release(); release_on_exit.g = nullptr; }       // the next slice may start: this one's first stage is queued
+    launch_j2k_analysis(b.d_frames, b.jb, (int) nt, b.s);
+    next.release();                                                    // the next slice may start: this one's first stage is queued
     fetch_frame_states(ctx, nt);
     b.fetch_jf();
-    if (j2k_tier1_retry(jb, (int) nt, b.tjf, s)) b.fetch_jf();        // (a group's decisions outgrew the segmented encoder's buffer)
+    if (j2k_tier1_retry(b.jb, (int) nt, b.tjf, b.s)) b.fetch_jf();    // (a group's decisions outgrew the segmented encoder's buffer)
     for (size_t f = 0; f < n; f++) {
         const FrameState &t0 = ctx->h_fs[f * tiles];                   // (all tiles of a chunk carry the chunk's statistics)
         if (t0.has_nonfinite) { log_fatal("NaN or Inf found in data of frame %zu", f); return 2; }
@@ -470,6 +484,13 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
         push_frame_states(rc, n);
     }
     pt.mark("analysis (dwt, tier-1, ckpt)");
+    return 0;
+}
+
+// ---- :693-716: the first encode at base_cr and, unless NONE, its decode (:707-709) and the residual range of that decode
+void BatchEncode::first_probe()
+{
+    ebcc_hip_ctx *rc = b.rc;
     const bool need_decode = mode != NONE;
     if (need_decode)
         for (size_t f = 0; f < n; f++) {
@@ -478,7 +499,6 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
             jobs[f].target = target;
             b.jf[f].target = target;
         }
-    // ---- first encode at base_cr (:693) and, unless NONE, its decode (:707-709)
     b.probe(need_decode);
     if (mode == NONE) {
         b.collect_tails(jobs);
@@ -488,11 +508,11 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
             jobs[f].mean_err = b.jf[f].err_sum / (double) n_pix;                              // :709
             jobs[f].q = jobs[f].q_first = 1. - ((double) b.jf[f].nbad / (double) n_pix);
             jobs[f].cr = cfg->base_cr;
-            jobs[f].probes.push_back(ProbeRec{b.jf[f].cr, b.jf[f].nbad, b.jf[f].stream_bytes, b.jf[f].err_sum});
+            jobs[f].probes.push_back(DevProbe{b.jf[f].cr, b.jf[f].stream_bytes, b.jf[f].nbad, b.jf[f].err_sum, 1, 0});
             b.state_cr[f] = b.jf[f].cr;
         }
         // residual range of the first decode: only the header fields survive when no search runs (:716)
-        launch_residual_minmax(d_frames, jb.DEC, (int) n, n_pix, rc->rb.fs, rs);
+        launch_residual_minmax(b.d_frames, b.jb.DEC, (int) n, n_pix, rc->rb.fs, b.rs);
         fetch_frame_states(rc, n);
         for (size_t f = 0; f < n; f++) { jobs[f].rmin = rc->h_fs[f].rmin; jobs[f].rmax = rc->h_fs[f].rmax; }
         if (!searching) {                       // stale enum values fall through to a base-only stream (quirk Q2)
@@ -500,420 +520,274 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
             b.collect_tails(jobs);
         }
     }
-
     pt.mark("first probe");
-    if (searching) {
-        // ---- rate search #1 (:728)
-        const bool pure_done = q_target == 1.0;                                               // :738
-        const bool want_pure = !pure_done && !env.no_fallback;
-        for (size_t f = 0; f < n; f++)
-            if (!jobs[f].const_field) jobs[f].rs[0].start(cfg->base_cr, jobs[f].q, q_target);
-        rate_search(b, 0, jobs, n_pix, slices);
-        for (size_t f = 0; f < n; f++) {
-            b.active[f] = jobs[f].const_field ? 0 : 1;
-            if (!jobs[f].const_field) { jobs[f].cr = jobs[f].rs[0].result; jobs[f].len1 = (size_t) jobs[f].last[0].stream_bytes; }
+}
+
+// ---- :728: rate search #1 (error-bounded) and the codestreams of its result
+void BatchEncode::search_1()
+{
+    for (size_t f = 0; f < n; f++)
+        if (!jobs[f].const_field) jobs[f].rs[0] = rate_search_start(cfg->base_cr, jobs[f].q, q_target);
+    rate_search(0);
+    for (size_t f = 0; f < n; f++) {
+        b.active[f] = jobs[f].const_field ? 0 : 1;
+        if (!jobs[f].const_field) { jobs[f].cr = jobs[f].rs[0].result; jobs[f].len1 = (size_t) jobs[f].rs[0].last.stream_bytes; }
+    }
+    pt.mark("rate search 1");
+    // base layer of search #1.  (Sending the codestreams off without waiting for them - written and packed on the second
+    // search's stream, fetched at the assembly - was measured: the slice's next stages are queued 2 ms earlier and the step
+    // gets 1 - 5 ms LONGER, three alternating runs on two boxes; the wait stays.)
+    b.collect_tails(jobs);
+}
+
+// :829-833: search #2 restarts from base_cr with the quantile of the first probe (== a re-encode at base_cr), or - that
+// consistency step disabled - from search #1's state
+void BatchEncode::start_search_2()
+{
+    for (Job &j : jobs)
+        if (!j.const_field) j.rs[1] = env.no_consistency ? rate_search_start(j.cr, j.q, 1.0) : rate_search_start(cfg->base_cr, j.q_first, 1.0);
+}
+
+// ---- the pure base-layer search (:819-836) depends on nothing the residual layer produces: for one-frame chunks its rounds
+//      are queued on the engine's second stream now (own state, counters and mask: rate_search lane 1) and run beside the
+//      residual layer and the truncation search; it is taken up again where the reference runs it (entropy_and_fallback).
+//      Round 2 measured this slower - the search was hidden behind the level-22 zstd of every prefix then; with the entropy
+//      stage cut down to the prefixes whose size can matter, the search was what the slice waited for, and its sizes are
+//      what decides which prefixes those are.
+void BatchEncode::queue_search_2()
+{
+    if (!overlap2) return;
+    start_search_2();
+    rate_search(1, 1, kSearchStart);
+    search2_queued = true;
+}
+
+// ---- :730-762: the residual range of search #1's decode, then for the chunks it does not leave within the target SPIHT
+//      with a budget of the base layer's size, the probe of the whole stream, and "could not reach the target"
+bool BatchEncode::residual_layer()
+{
+    ebcc_hip_ctx *rc = b.rc;
+    hipStream_t rs = b.rs;
+    launch_residual_minmax(b.d_frames, b.jb.DEC, (int) n, n_pix, rc->rb.fs, rs);          // :730-733
+    fetch_frame_states(rc, n);
+    for (size_t f = 0; f < n; f++) {
+        Job &j = jobs[f];
+        b.active[f] = 0;
+        if (j.const_field) continue;
+        j.rmin = rc->h_fs[f].rmin; j.rmax = rc->h_fs[f].rmax;
+        float cur = fmaxf(fabsf(j.rmin), fabsf(j.rmax));                                  // :735
+        j.skip = cur <= j.target;                                                         // :737
+        if (!j.skip) { b.active[f] = 1; any_resid = true; }
+    }
+    pt.mark("tails + residual range");
+    if (!zstd().ok) { log_fatal("libzstd not available"); return false; }
+    if (!any_resid) return true;
+    // :744-754 (budgets, the encoder, the cut "everything" and its probe are queued without a look at the frame states in
+    // between: the budget follows from the base layer's size, the whole stream's length stays on the device)
+    b.push_ractive();
+    launch_pad_and_dc(b.d_frames, b.jb.DEC, rc->rb, (int) n, rc->d_active, rs);
+    launch_analysis(rc->rb, (int) n, rc->d_active, rs);
+    for (size_t f = 0; f < n; f++) rc->h_u64a[f] = (unsigned long long) jobs[f].len1 * 8 + 128;   // bits0 = trunc_bits + 128
+    EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64a, rc->h_u64a, n * sizeof(unsigned long long), hipMemcpyHostToDevice, rs));
+    launch_residual_budget(rc->rb, (int) n, rc->d_u64a, rc->d_active, rs);
+    launch_spiht_encode(rc->rb, (int) n, rc->d_u64a, rc->d_active, rs);
+    launch_whole_stream_cut(rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);
+    launch_prefix_synthesis_stats(b.d_frames, b.jb.DEC, rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);   // full decode, :749
+    fetch_frame_states(rc, n);
+    pt.mark("residual: analysis, SPIHT, whole-stream probe");
+    for (size_t f = 0; f < n; f++) {
+        Job &j = jobs[f];
+        if (!b.active[f]) continue;
+        j.coeffs_orig = j.coeffs_size = rc->h_fs[f].stream_bytes;
+        float cur = u2f(rc->h_fs[f].maxerr_bits);                                        // :754
+        if (cur > j.target) {                                                             // :755-759
+            log_info("frame %zu: could not reach error target %f (%f instead); retry with pure base compression", f, j.target, cur);
+            j.skip = true; j.need_pure = true;
+        } else {
+            j.best_err = cur;
+            j.mean_err = rc->h_fs[f].err_sum / (double) n_pix;                           // :762
+            j.t_hi = (double) j.coeffs_size * 8; j.t_lo = 112.0; j.t_best = j.t_hi;       // :766-776
+            j.trunc_active = true;
         }
-        pt.mark("rate search 1");
-        // base layer of search #1.  (Sending the codestreams off without waiting for them - written and packed on the second
-        // search's stream, fetched at the assembly - was measured: the slice's next stages are queued 2 ms earlier and the step
-        // gets 1 - 5 ms LONGER, three alternating runs on two boxes; the wait stays.)
-        b.collect_tails(jobs);
-        auto start_search2 = [&]() {
-            for (size_t f = 0; f < n; f++) {
-                if (jobs[f].const_field) continue;
-                if (env.no_consistency) jobs[f].rs[1].start(jobs[f].cr, jobs[f].q, 1.0);      // from search #1's state
-                else jobs[f].rs[1].start(cfg->base_cr, jobs[f].q_first, 1.0);                 // :829-833 == the first probe
+    }
+    return true;
+}
+
+// ---- :765-796: truncation bisection of the SPIHT streams as the device state machine (search.hpp): advance, reconstruct the
+//      decoder state at the cut, synthesis + statistics - enqueued back to back, one look at the states after a batch of
+//      rounds, more rounds only while a chunk is still searching
+void BatchEncode::truncation_search()
+{
+    ebcc_hip_ctx *rc = b.rc;
+    hipStream_t rs = b.rs;
+    if (any_resid) {
+        DevChunk *h = static_cast<DevChunk *>(rc->h_search), *d = static_cast<DevChunk *>(rc->d_search);
+        for (size_t f = 0; f < n; f++) {
+            const Job &j = jobs[f];
+            DevChunk &c = h[f];
+            c.t_hi = j.t_hi; c.t_lo = j.t_lo; c.t_best = j.t_best; c.mean_err = j.mean_err; c.best_err = j.best_err;
+            c.target = j.target; c.trunc_active = j.trunc_active ? 1 : 0; c.trunc_pending = 0;
+        }
+        EBCC_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevChunk) * n, hipMemcpyHostToDevice, rs));
+        EBCC_HIP_CHECK(hipMemsetAsync(rc->d_counter, 0, sizeof(int) * 4, rs));
+        // rounds a chunk can still need: a cut halves the interval (rounded up to a byte: + 8 bits at most) until it is
+        // 32 bits wide (:777), then one more advance sees that nothing is left
+        auto rounds_left = [](const DevChunk &c) {
+            if (!c.trunc_active) return 0;
+            double w = c.t_hi - c.t_lo;
+            int r = 1;
+            while (w > 32 && r < 64) { w = w / 2 + 8; r++; }
+            return r;
+        };
+        int cuts_left = 1;                                               // cuts the longest search still visits, + the advance that ends it
+        for (size_t f = 0; f < n; f++) cuts_left = std::max(cuts_left, rounds_left(h[f]));
+        const bool forced_rounds = getenv("EBCC_HIP_SEARCH_ROUNDS") != nullptr;
+        // `rounds` rounds back to back, a look at the states, then `more` rounds at a time until no chunk is searching
+        auto drive = [&](int rounds, int more, auto round) {
+            for (;; rounds = more) {
+                for (int r = 0; r < rounds; r++) round();
+                EBCC_HIP_CHECK(hipMemcpyAsync(h, d, sizeof(DevChunk) * n, hipMemcpyDeviceToHost, rs));
+                wait_stream(rs);
+                if (std::none_of(h, h + n, [](const DevChunk &c) { return c.trunc_active != 0; })) return;
             }
         };
-        // ---- the pure base-layer search (:819-836) depends on nothing the residual layer produces: its rounds are queued on the
-        //      engine's second stream now (own state, counters and mask: device_rate_search lane 1) and run beside the residual
-        //      layer and the truncation search; it is taken up again where the reference runs it (below).  Round 2 measured
-        //      this slower - the search was hidden behind the level-22 zstd of every prefix then; with the entropy stage cut
-        //      down to the prefixes whose size can matter, the search was what the slice waited for, and its sizes are what
-        //      decides which prefixes those are.  (With EBCC_HIP_HOST_SEARCH=1 it runs in the reference's place.)
-        const bool overlap2 = want_pure && tiles == 1 && rc == ctx && !getenv("EBCC_HIP_HOST_SEARCH");
-        struct DrainSecond {               // an error return between here and the take-up must not leave rounds in flight
-            ebcc_hip_ctx *c; bool armed;
-            ~DrainSecond() { if (armed && c->stream2) hipStreamSynchronize(c->stream2); }
-        } drain2{ctx, false};
-        if (overlap2) {
-            start_search2();
-            device_rate_search(b, 1, jobs, n_pix, slices, 1, kSearchStart);
-            drain2.armed = true;
+        // Look-ahead (search.hpp: launch_trunc_advance_multi): a round probes the cut :779 chooses now and the cuts either
+        // outcome leads to - `levels` levels of the bisection tree, 2^levels - 1 cut slots per frame - so the search takes
+        // 1 / levels of the rounds.  The rounds are latency (a chain of six small launches beside the other slices' work),
+        // the probes off the path mostly stop early (a cut shorter than an infeasible one is infeasible too: its first wave
+        // over the target ends it).  EBCC_HIP_TRUNC_LEVELS=1, or no room for the cut slots: one cut per round.
+        int levels = getenv("EBCC_HIP_TRUNC_LEVELS") ? std::min(3, std::max(1, atoi(getenv("EBCC_HIP_TRUNC_LEVELS")))) : 2;
+        while (levels > 1 && !ensure_cut_slots(rc, (int) n * ((1 << levels) - 1))) levels--;
+        if (levels > 1) {
+            const CutSlots &cs = rc->cut;
+            const int n_slots = (int) n * ((1 << levels) - 1);
+            auto advance = [&] { launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, rc->d_counter, rs); };
+            advance();
+            drive(forced_rounds ? search_rounds() : (cuts_left + levels - 1) / levels + 1, 3, [&] {
+                launch_prefix_synthesis_slots(b.d_frames, b.jb.DEC, rc->rb, cs, n_slots, rs);
+                advance();
+            });
+        } else {
+            auto advance = [&] { launch_trunc_advance(d, rc->rb.fs, rc->d_u64b, rc->d_active, (int) n, (double) n_pix, rc->d_counter, rs); };
+            advance();
+            drive(forced_rounds ? search_rounds() : cuts_left + 1, 6, [&] {
+                launch_prefix_synthesis_stats(b.d_frames, b.jb.DEC, rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);
+                advance();
+            });
         }
-        launch_residual_minmax(d_frames, jb.DEC, (int) n, n_pix, rc->rb.fs, rs);             // :730-733
-        fetch_frame_states(rc, n);
-        bool any_resid = false;
+        for (size_t f = 0; f < n; f++) {
+            Job &j = jobs[f];
+            const DevChunk &c = h[f];
+            if (j.trunc_active) { j.t_hi = c.t_hi; j.t_lo = c.t_lo; j.t_best = c.t_best; j.mean_err = c.mean_err; j.best_err = c.best_err; }
+            j.trunc_active = false;
+        }
+    }
+    for (Job &j : jobs) {
+        if (j.const_field || j.skip) j.coeffs_size = j.need_pure ? j.coeffs_orig : 0;
+        else j.coeffs_size = (size_t) (j.t_best / 8.);                                    // :796
+    }
+    pt.mark("truncation search");
+}
+
+// ---- :811-854: entropy stage of the kept SPIHT prefix on host cores (:811-817) and the pure base-layer fallback (:819-854).
+//      Level-22 zstd is by far the longest host step (~160 ns per byte on one core: 1.3 core-seconds per 256 frames
+//      of the bench workload on a box whose container has 16 CPUs), and the reference throws most of it away: the
+//      compressed size z is compared with what the pure base-layer search gives (:838: len2 < z + len1), and for
+//      ~95 % of ERA5-like frames the base layer alone wins.  So z is only worked out where it can matter: a frame
+//      whose z is PROVABLY above len2 - len1 (zstd_size_lower_bound: the literals no match can cover cost at least
+//      their entropy) takes the pure base layer without being compressed - the same decision, bytes unchanged.
+bool BatchEncode::entropy_and_fallback()
+{
+    ebcc_hip_ctx *rc = b.rc;
+    Entropy es(jobs, slices, env.zstd_level, pt.on);
+    // the kept SPIHT prefixes of the batch in one packed download; the workers read them where they land (the staging
+    // buffer of the residual engine is not touched again before they are done)
+    std::vector<size_t> coeff_len(n, 0), coeff_off(n, 0);
+    for (size_t f = 0; f < n; f++) {
+        if (jobs[f].coeffs_size <= 16) jobs[f].coeffs_size = 0;
+        coeff_len[f] = jobs[f].coeffs_size;
+    }
+    stage_download(rc, (const uint8_t *) rc->rb.stream, rc->rb.stream_words * sizeof(uint32_t), coeff_len.data(), coeff_off.data(), n, b.rs);
+    std::vector<size_t> with_prefix;
+    for (size_t f = 0; f < n; f++)
+        if (coeff_len[f]) { es.coeff_ptr[f] = rc->h_stage + coeff_off[f]; with_prefix.push_back(f); }
+    std::vector<size_t> cand;                                       // frames whose floor may decide them (search #2's sizes)
+    if (!want_pure) {
+        es.submit_zstd(es.longest_first(with_prefix));                  // no fallback: every prefix is part of its stream
+    } else {
+        // frames whose residual layer could not reach the target are coded by the base layer whatever z is (:838 need_pure)
+        const bool use_floor = zstd_floor_usable() && !getenv("EBCC_HIP_NO_SHORTCUTS");
+        std::vector<size_t> now;
+        for (size_t f : with_prefix) {
+            if (jobs[f].need_pure) { es.zstate[f] = Entropy::kSkipped; continue; }
+            (use_floor && jobs[f].coeffs_size <= kZstdFloorMaxBytes ? cand : now).push_back(f);
+        }
+        if (!now.empty()) es.submit_zstd(es.longest_first(now));
+        if (!cand.empty()) es.submit_floors(cand);
+    }
+    pt.mark("zstd: queued");
+    if (want_pure) {
+        // search #2 re-uses every probe search #1 made; it runs while host cores work on the prefixes: first the floors (a
+        // few microseconds per KB), then - the search still running on the GPU, len2 not known yet - zstd of the candidates
+        // in the order in which they are likely to need it; the moment the search's sizes are in, the candidates they
+        // decide are struck from the queue
+        if (overlap2) {
+            // the search has been running beside the residual layer: its sizes are (nearly) there, the floors take a
+            // millisecond - the prefixes that are still open after that are compressed, longest first
+            rate_search(1, 1, kSearchFinish);                                                 // :836
+            search2_queued = false;
+            pt.mark("rate search 2");
+            gpu_phase_over.tell();                                                            // (what follows is host work and one small launch)
+            if (!es.join_floors()) return false;
+        } else {
+            start_search_2();
+            rate_search(1, 0, kSearchStart);
+            if (!cand.empty()) {
+                if (!es.join_floors()) return false;
+                es.submit_zstd(es.lowest_floor_first(cand));
+            }
+            rate_search(1, 0, kSearchFinish);                                                 // :836
+            pt.mark("rate search 2");
+            gpu_phase_over.tell();
+        }
+        long long skipped_bytes = 0, skipped = 0;
+        for (size_t f : cand)
+            if (es.floor_decides(f) && es.strike(f)) { skipped++; skipped_bytes += (long long) jobs[f].coeffs_size; }
+        if (overlap2) {
+            const std::vector<size_t> open = es.not_started(cand);
+            if (!open.empty()) es.submit_zstd(es.longest_first(open));
+        }
+        if (!es.join_all()) return false;
+        pt.mark("zstd: wait for the workers");
+        for (size_t f : with_prefix) if (jobs[f].need_pure) { skipped++; skipped_bytes += (long long) jobs[f].coeffs_size; }
+        es.report(with_prefix, skipped, skipped_bytes);
+        // :838-854: the pure base layer where it beats base + residual, or where the residual layer could not reach the target
+        bool any_pure = false;
         for (size_t f = 0; f < n; f++) {
             Job &j = jobs[f];
             b.active[f] = 0;
             if (j.const_field) continue;
-            j.rmin = rc->h_fs[f].rmin; j.rmax = rc->h_fs[f].rmax;
-            float cur = fmaxf(fabsf(j.rmin), fabsf(j.rmax));                                  // :735
-            j.skip = cur <= j.target;                                                         // :737
-            if (!j.skip) { b.active[f] = 1; any_resid = true; }
-        }
-        pt.mark("tails + residual range");
-
-        if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-        // ---- the entropy stage's state (the stage itself follows the truncation search).
-        //      jobs on the process-wide pool (HostPool): every slice of a batch feeds the same workers, so the host is never
-        //      oversubscribed however many slices run
-        std::vector<const uint8_t *> coeff_ptr(n, nullptr);             // the kept prefix of a frame in pinned host memory
-        std::atomic<long long> zstd_us{0}, zstd_max_us{0}, zstd_bytes{0}, bound_us{0};    // core time, longest job, bytes
-        enum : uint8_t { kZNone = 0, kZQueued = 1, kZRunning = 2, kZSkipped = 3 };
-        std::unique_ptr<std::atomic<uint8_t>[]> zstate(new std::atomic<uint8_t>[n]);
-        for (size_t f = 0; f < n; f++) zstate[f] = kZNone;
-        std::vector<size_t> zfloor(n, 0);                               // lower bound of z (0: none)
-        std::vector<char> floor_done(n, 0);
-        using PoolBatches = std::vector<std::shared_ptr<HostPool::Batch>>;
-        PoolBatches zbatches, fbatches;                                 // level-22 jobs; lower bounds
-        struct WaitOnExit { PoolBatches &v; ~WaitOnExit() { for (auto &b : v) if (b) b->wait(); } } wait_on_exit{zbatches}, wait_on_exit_f{fbatches};   // (error paths too: the jobs point into this frame)
-        // level-22 zstd of the frames in `list`, in the order given; a frame that was decided in the meantime (kZSkipped)
-        // is passed over
-        const bool trace_jobs = pt.on && getenv("EBCC_HIP_ZSTD_TRACE");
-        auto submit_zstd = [&](std::vector<size_t> list) {
-            if (trace_jobs) {
-                static const auto epoch0 = std::chrono::steady_clock::now(); (void) epoch0;
-                fprintf(stderr, "zstd-submit batch %p jobs %zu\n", (const void *) &jobs, list.size());
-            }
-            for (size_t f : list) zstate[f] = kZQueued;
-            auto order = std::make_shared<std::vector<size_t>>(std::move(list));
-            zbatches.push_back(HostPool::instance().submit(order->size(), entropy_threads(slices), [&, order](size_t i) {
-                const size_t f = (*order)[i];
-                uint8_t expect = kZQueued;
-                if (!zstate[f].compare_exchange_strong(expect, kZRunning)) return;
-                Job &j = jobs[f];
-                const auto z0 = std::chrono::steady_clock::now();
-                j.zbytes.resize(zstd().bound(j.coeffs_size));
-                const size_t z = zstd().compress(j.zbytes.data(), j.zbytes.size(), coeff_ptr[f], j.coeffs_size, env.zstd_level);
-                if ((zstd().is_error && zstd().is_error(z)) || z > j.zbytes.size()) throw std::runtime_error("ZSTD_compress failed on a residual prefix");
-                j.zbytes.resize(z);
-                const long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - z0).count();
-                if (trace_jobs) {                                           // (EBCC_HIP_ZSTD_TRACE: when each job ran, on which CPU)
-                    static const auto epoch = std::chrono::steady_clock::now();
-                    const long long a = std::chrono::duration_cast<std::chrono::microseconds>(z0 - epoch).count();
-                    fprintf(stderr, "zstd-job batch %p bytes %zu start %lld us end %lld us cpu %d\n", (const void *) &jobs, j.coeffs_size, a, a + us, sched_getcpu());
-                }
-                zstd_us += us; zstd_bytes += (long long) j.coeffs_size;
-                long long m = zstd_max_us.load(); while (us > m && !zstd_max_us.compare_exchange_weak(m, us)) {}
-            }));
-        };
-        // the lower bounds of z for the frames in `list` (zstd_size_lower_bound)
-        auto submit_floors = [&](const std::vector<size_t> &frames_) {
-            auto list = std::make_shared<std::vector<size_t>>(frames_);
-            fbatches.push_back(HostPool::instance().submit(list->size(), entropy_threads(slices), [&, list](size_t i) {
-                const size_t f = (*list)[i];
-                const auto z0 = std::chrono::steady_clock::now();
-                zfloor[f] = zstd_size_lower_bound(coeff_ptr[f], jobs[f].coeffs_size);
-                floor_done[f] = 1;
-                bound_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - z0).count();
-            }));
-        };
-        // longest first: level 22 takes ~0.2 ms per KB on one core and a batch has frames whose prefix is ten times the
-        // average - started last, such a frame alone decides when the slice can go on
-        auto longest_first = [&](std::vector<size_t> &list) {
-            std::stable_sort(list.begin(), list.end(), [&](size_t a, size_t c) { return jobs[a].coeffs_size > jobs[c].coeffs_size; });
-        };
-        long long wait_us = 0;
-        auto join = [&](PoolBatches &v) -> bool {
-            const auto w0 = std::chrono::steady_clock::now();
-            bool ok = true;
-            std::string why;
-            for (auto &b : v) if (b && !b->wait()) { ok = false; if (why.empty()) why = b->error; }
-            v.clear();
-            wait_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - w0).count();
-            if (!ok) { log_fatal("entropy stage failed: %s", why.c_str()); set_error("%s", why.c_str()); }
-            return ok;
-        };
-        auto zjoin = [&]() -> bool { const bool a = join(fbatches), c = join(zbatches); return a && c; };
-        const bool use_floor = want_pure && zstd_floor_usable() && !getenv("EBCC_HIP_NO_SHORTCUTS");
-        if (any_resid) {
-            // ---- residual layer: SPIHT with a budget of the base layer's size (:744-754)
-            b.push_ractive();
-            launch_pad_and_dc(d_frames, jb.DEC, rc->rb, (int) n, rc->d_active, rs);
-            launch_analysis(rc->rb, (int) n, rc->d_active, rs);
-            // (budgets, the encoder, the cut "everything" and its probe are queued without a look at the frame states in
-            //  between: the budget follows from the base layer's size, the whole stream's length stays on the device)
-            for (size_t f = 0; f < n; f++) rc->h_u64a[f] = (unsigned long long) jobs[f].len1 * 8 + 128;   // bits0 = trunc_bits + 128
-            EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64a, rc->h_u64a, n * sizeof(unsigned long long), hipMemcpyHostToDevice, rs));
-            launch_residual_budget(rc->rb, (int) n, rc->d_u64a, rc->d_active, rs);
-            launch_spiht_encode(rc->rb, (int) n, rc->d_u64a, rc->d_active, rs);
-            launch_whole_stream_cut(rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);
-            launch_prefix_synthesis_stats(d_frames, jb.DEC, rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);   // full decode, :749
-            fetch_frame_states(rc, n);
-            for (size_t f = 0; f < n; f++) {
-                if (!b.active[f]) continue;
-                jobs[f].coeffs_orig = rc->h_fs[f].stream_bytes;
-                jobs[f].coeffs_size = jobs[f].coeffs_orig;
-                rc->h_u64b[f] = (unsigned long long) jobs[f].coeffs_orig * 8;
-            }
-            auto probe_residual = [&]() {
-                EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64b, rc->h_u64b, n * sizeof(unsigned long long), hipMemcpyHostToDevice, rs));
-                b.push_ractive();
-                launch_prefix_synthesis_stats(d_frames, jb.DEC, rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);
-                fetch_frame_states(rc, n);
-            };
-            pt.mark("residual: analysis, SPIHT, whole-stream probe");
-            for (size_t f = 0; f < n; f++) {
-                Job &j = jobs[f];
-                if (!b.active[f]) continue;
-                float cur = u2f(rc->h_fs[f].maxerr_bits);                                    // :754
-                if (cur > j.target) {                                                         // :755-759
-                    log_info("frame %zu: could not reach error target %f (%f instead); retry with pure base compression", f, j.target, cur);
-                    j.skip = true; j.need_pure = true;
-                } else {
-                    j.best_err = cur;
-                    j.mean_err = rc->h_fs[f].err_sum / (double) n_pix;                       // :762
-                    j.t_hi = (double) j.coeffs_size * 8; j.t_lo = 112.0; j.t_best = j.t_hi;   // :766-776
-                    j.trunc_active = true;
-                }
-            }
-            // ---- truncation bisection (:777-795): all frames advance one cut per round
-            const bool host_loop = getenv("EBCC_HIP_HOST_SEARCH") != nullptr;
-            if (!host_loop) {
-                // state machine on the device (search.hpp): advance, reconstruct the decoder state at the cut, synthesis +
-                // statistics - enqueued back to back, one look at the states after `rounds` of them
-                DevChunk *h = static_cast<DevChunk *>(rc->h_search), *d = static_cast<DevChunk *>(rc->d_search);
-                for (size_t f = 0; f < n; f++) {
-                    const Job &j = jobs[f];
-                    DevChunk &c = h[f];
-                    c.t_hi = j.t_hi; c.t_lo = j.t_lo; c.t_best = j.t_best; c.mean_err = j.mean_err; c.best_err = j.best_err;
-                    c.target = j.target; c.trunc_active = j.trunc_active ? 1 : 0; c.trunc_pending = 0;
-                }
-                EBCC_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevChunk) * n, hipMemcpyHostToDevice, rs));
-                EBCC_HIP_CHECK(hipMemsetAsync(rc->d_counter, 0, sizeof(int) * 4, rs));
-                // rounds a chunk can still need: a cut halves the interval (rounded up to a byte: + 8 bits at most) until it is
-                // 32 bits wide (:777), then one more advance sees that nothing is left
-                auto rounds_left = [](const DevChunk &c) {
-                    if (!c.trunc_active) return 0;
-                    double w = c.t_hi - c.t_lo;
-                    int r = 1;
-                    while (w > 32 && r < 64) { w = w / 2 + 8; r++; }
-                    return r;
-                };
-                const bool forced_rounds = getenv("EBCC_HIP_SEARCH_ROUNDS") != nullptr;
-                int cuts_left = 1;                                       // cuts the longest search still visits, + the advance that ends it
-                for (size_t f = 0; f < n; f++) cuts_left = std::max(cuts_left, rounds_left(h[f]));
-                auto take_result = [&](const DevChunk &c, Job &j) {
-                    j.t_hi = c.t_hi; j.t_lo = c.t_lo; j.t_best = c.t_best; j.mean_err = c.mean_err; j.best_err = c.best_err;
-                    j.trunc_active = false;
-                };
-                // ---- Look-ahead (search.hpp: launch_trunc_advance_multi): a round probes the cut :779 chooses now and the cuts
-                //      either outcome leads to - `levels` levels of the bisection tree, 2^levels - 1 cut slots per frame - so the
-                //      search takes 1 / levels of the rounds.  The rounds are latency (a chain of six small launches beside the
-                //      other slices' work), the probes off the path mostly stop early (a cut shorter than an infeasible one is
-                //      infeasible too: its first wave over the target ends it).  EBCC_HIP_TRUNC_LEVELS=1: one cut per round.
-                int levels = getenv("EBCC_HIP_TRUNC_LEVELS") ? std::min(3, std::max(1, atoi(getenv("EBCC_HIP_TRUNC_LEVELS")))) : 2;
-                while (levels > 1 && !ensure_cut_slots(rc, (int) n * ((1 << levels) - 1))) levels--;
-                if (levels > 1) {
-                    const CutSlots &cs = rc->cut;
-                    const int n_slots = (int) n * ((1 << levels) - 1);
-                    launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, rc->d_counter, rs);
-                    int rounds = forced_rounds ? search_rounds() : (cuts_left + levels - 1) / levels + 1;
-                    for (;;) {
-                        for (int r = 0; r < rounds; r++) {
-                            launch_prefix_synthesis_slots(d_frames, jb.DEC, rc->rb, cs, n_slots, rs);
-                            launch_trunc_advance_multi(d, rc->rb.fs, cs, (int) n, (double) n_pix, levels, rc->d_counter, rs);
-                        }
-                        EBCC_HIP_CHECK(hipMemcpyAsync(h, d, sizeof(DevChunk) * n, hipMemcpyDeviceToHost, rs));
-                        wait_stream(rs);
-                        bool done = true;
-                        for (size_t f = 0; f < n; f++) done &= !h[f].trunc_active;
-                        if (done) break;
-                        rounds = 3;
-                    }
-                    for (size_t f = 0; f < n; f++) if (jobs[f].trunc_active) take_result(h[f], jobs[f]);
-                } else {
-                    launch_trunc_advance(d, rc->rb.fs, rc->d_u64b, rc->d_active, (int) n, (double) n_pix, rc->d_counter, rs);
-                    int rounds = forced_rounds ? search_rounds() : cuts_left + 1;
-                    for (;;) {
-                        for (int r = 0; r < rounds; r++) {
-                            launch_prefix_synthesis_stats(d_frames, jb.DEC, rc->rb, (int) n, rc->d_u64b, rc->d_active, rs);
-                            launch_trunc_advance(d, rc->rb.fs, rc->d_u64b, rc->d_active, (int) n, (double) n_pix, rc->d_counter, rs);
-                        }
-                        EBCC_HIP_CHECK(hipMemcpyAsync(h, d, sizeof(DevChunk) * n, hipMemcpyDeviceToHost, rs));
-                        wait_stream(rs);
-                        bool done = true;
-                        for (size_t f = 0; f < n; f++) done &= !h[f].trunc_active;
-                        if (done) break;
-                        rounds = 6;
-                    }
-                    for (size_t f = 0; f < n; f++) if (jobs[f].trunc_active) take_result(h[f], jobs[f]);
-                }
-            } else
-            for (;;) {
-                const double eps = 1e-8;
-                bool any = false;
-                for (size_t f = 0; f < n; f++) {
-                    Job &j = jobs[f];
-                    b.active[f] = 0;
-                    if (!j.trunc_active) continue;
-                    if (((j.target - j.best_err) / j.target > eps) && (j.t_hi - j.t_lo > 8 * 4)) {
-                        size_t tb = ((size_t) ceill((long double) ((j.t_hi + j.t_lo) / 2 / 8))) * 8;
-                        rc->h_u64b[f] = tb;
-                        b.active[f] = 1;
-                        any = true;
-                    } else {
-                        j.trunc_active = false;
-                    }
-                }
-                if (!any) break;
-                probe_residual();
-                for (size_t f = 0; f < n; f++) {
-                    Job &j = jobs[f];
-                    if (!b.active[f]) continue;
-                    const double tb = (double) rc->h_u64b[f];
-                    float cur = u2f(rc->h_fs[f].maxerr_bits);
-                    if (cur > j.target) j.t_lo = tb;
-                    else {
-                        j.t_hi = tb;
-                        if (cur >= j.best_err) { j.best_err = cur; j.t_best = tb; j.mean_err = rc->h_fs[f].err_sum / (double) n_pix; }
-                    }
-                    log_trace("frame %zu: trunc_lo %.1f trunc_hi %.1f max error %f", f, j.t_lo, j.t_hi, cur);
-                }
-            }
-            for (size_t f = 0; f < n; f++) {
-                Job &j = jobs[f];
-                if (j.const_field || j.skip) { if (j.need_pure) j.coeffs_size = j.coeffs_orig; else j.coeffs_size = 0; }
-                else j.coeffs_size = (size_t) (j.t_best / 8.);                                // :796
+            const size_t len2 = (size_t) j.rs[1].last.stream_bytes;
+            const bool decided = es.floor_decides(f);                                         // (z may not be known - only that it loses)
+            if (decided || len2 < j.zbytes.size() + j.len1 || j.need_pure) {                  // :838
+                if (decided) log_info("frame %zu: pure base compression (%zu) beats base (%zu) + residual (at least %zu)", f, len2, j.len1, es.zfloor[f]);
+                else if (len2 < j.zbytes.size() + j.len1)
+                    log_info("frame %zu: pure base compression (%zu) beats base (%zu) + residual (%zu)", f, len2, j.len1, j.zbytes.size());
+                j.mean_err = j.rs[1].last.err_sum / (double) n_pix;                           // :843
+                j.zbytes.clear(); j.coeffs_size = 0;
+                b.active[f] = 1; b.jf[f].cr = j.rs[1].result; any_pure = true;
             }
         }
-        pt.mark("truncation search");
-        // ---- entropy stage of the kept SPIHT prefix on host cores (:811-817) and the pure base-layer fallback (:819-854).
-        //      Level-22 zstd is by far the longest host step (~160 ns per byte on one core: 1.3 core-seconds per 256 frames
-        //      of the bench workload on a box whose container has 16 CPUs), and the reference throws most of it away: the
-        //      compressed size z is compared with what the pure base-layer search gives (:838: len2 < z + len1), and for
-        //      ~95 % of ERA5-like frames the base layer alone wins.  So z is only worked out where it can matter: a frame
-        //      whose z is PROVABLY above len2 - len1 (zstd_size_lower_bound: the literals no match can cover cost at least
-        //      their entropy) takes the pure base layer without being compressed - the same decision, bytes unchanged.
-        // the kept SPIHT prefixes of the batch in one packed download; the workers read them where they land (the staging
-        // buffer of the residual engine is not touched again before they are done)
-        std::vector<size_t> coeff_len(n, 0), coeff_off(n, 0);
-        for (size_t f = 0; f < n; f++) {
-            Job &j = jobs[f];
-            if (j.coeffs_size <= 16) j.coeffs_size = 0;
-            if (!coeff_ptr[f]) coeff_len[f] = j.coeffs_size;
-        }
-        stage_download(rc, (const uint8_t *) rc->rb.stream, rc->rb.stream_words * sizeof(uint32_t), coeff_len.data(), coeff_off.data(), n, rs);
-        for (size_t f = 0; f < n; f++) if (coeff_len[f]) coeff_ptr[f] = rc->h_stage + coeff_off[f];
-        std::vector<size_t> with_prefix;
-        for (size_t f = 0; f < n; f++) if (jobs[f].coeffs_size > 0) with_prefix.push_back(f);
-        std::vector<size_t> cand;
-        auto not_started = [&](std::vector<size_t> v) {                 // (frames already queued or decided)
-            v.erase(std::remove_if(v.begin(), v.end(), [&](size_t f) { return zstate[f] != kZNone; }), v.end());
-            return v;
-        };
-        if (!want_pure) {
-            std::vector<size_t> rest = not_started(with_prefix);
-            longest_first(rest);
-            submit_zstd(rest);                                          // no fallback: every prefix is part of its stream
-        } else {
-            // frames whose residual layer could not reach the target are coded by the base layer whatever z is (:838 need_pure)
-            std::vector<size_t> now;
-            for (size_t f : with_prefix) {
-                if (jobs[f].need_pure) { zstate[f] = kZSkipped; continue; }
-                if (use_floor && jobs[f].coeffs_size <= kZstdFloorMaxBytes) cand.push_back(f); else now.push_back(f);
-            }
-            now = not_started(now);
-            longest_first(now);
-            if (!now.empty()) submit_zstd(now);
-            std::vector<size_t> want_floor;
-            for (size_t f : cand) if (!floor_done[f]) want_floor.push_back(f);
-            if (!want_floor.empty()) submit_floors(want_floor);
-        }
-        pt.mark("zstd: queued");
-        if (want_pure) {
-            // The pure-base-layer search restarts from base_cr with the quantile of a re-encode at base_cr
-            // (:829-833), i.e. of the first probe above (unless that consistency step is disabled), and re-uses
-            // every probe search #1 made; it runs here, while host cores work on the prefixes: first the floors (a few
-            // microseconds per KB), then - the search still running on the GPU, len2 not known yet - zstd of the
-            // candidates in the order in which they are likely to need it (lowest floor per byte first); the moment the
-            // search's sizes are in, the candidates they decide are struck from the queue.
-            const bool host_loop = getenv("EBCC_HIP_HOST_SEARCH") != nullptr;
-            if (overlap2) {
-                // the search has been running beside the residual layer: its sizes are (nearly) there, the floors take a
-                // millisecond - the prefixes that are still open after that are compressed, longest first
-                device_rate_search(b, 1, jobs, n_pix, slices, 1, kSearchFinish);              // :836
-                drain2.armed = false;
-                pt.mark("rate search 2");
-                gpu_phase_over.tell();                                                        // (what follows is host work and one small launch)
-                if (!join(fbatches)) return 1;                                                // (the floors)
-            } else {
-                start_search2();
-                if (!host_loop) device_rate_search(b, 1, jobs, n_pix, slices, 0, kSearchStart);
-                if (!cand.empty()) {
-                    if (!join(fbatches)) return 1;                                            // (the floors)
-                    std::vector<size_t> spec = not_started(cand);
-                    std::stable_sort(spec.begin(), spec.end(), [&](size_t a, size_t c) {
-                        return (double) zfloor[a] * (double) jobs[c].coeffs_size < (double) zfloor[c] * (double) jobs[a].coeffs_size; });
-                    submit_zstd(spec);
-                }
-                if (host_loop) run_search(b, 1, jobs, n_pix); else device_rate_search(b, 1, jobs, n_pix, slices, 0, kSearchFinish);   // :836
-                pt.mark("rate search 2");
-                gpu_phase_over.tell();
-            }
-            long long skipped_bytes = 0, skipped = 0;
-            for (size_t f : cand) {
-                const Job &j = jobs[f];
-                const size_t len2 = (size_t) j.last[1].stream_bytes;
-                // z >= zfloor: len2 < zfloor + len1 implies len2 < z + len1 - the base layer alone wins (:838)
-                if (!(zfloor[f] > 0 && len2 < zfloor[f] + j.len1)) continue;
-                // (decided before a worker took it up: not queued yet, or queued on the speculative list)
-                uint8_t expect = kZNone;
-                bool struck = zstate[f].compare_exchange_strong(expect, kZSkipped);
-                if (!struck) { expect = kZQueued; struck = zstate[f].compare_exchange_strong(expect, kZSkipped); }
-                if (struck) { skipped++; skipped_bytes += (long long) j.coeffs_size; }
-            }
-            if (overlap2) {
-                std::vector<size_t> open;
-                for (size_t f : cand) if (zstate[f] == kZNone) open.push_back(f);
-                longest_first(open);
-                if (!open.empty()) submit_zstd(open);
-            }
-            if (!zjoin()) return 1;
-            pt.mark("zstd: wait for the workers");
-            for (size_t f : with_prefix) if (jobs[f].need_pure) { skipped++; skipped_bytes += (long long) jobs[f].coeffs_size; }
-            if (pt.on) fprintf(stderr, "ebcc-mi355x zstd: %.1f ms of core time for %lld bytes, longest job %.1f ms; floors %.1f ms; %lld of %zu prefixes (%lld bytes) not compressed\n",
-                               zstd_us.load() / 1e3, zstd_bytes.load(), zstd_max_us.load() / 1e3, bound_us.load() / 1e3, skipped, with_prefix.size(), skipped_bytes);
-            host_stats().skipped_bytes += skipped_bytes;
-            if (pt.on && getenv("EBCC_HIP_ZSTD_TRACE"))
-                for (size_t f : with_prefix) {
-                    const Job &j = jobs[f];
-                    const long long x = (long long) j.last[1].stream_bytes - (long long) j.len1;
-                    fprintf(stderr, "zstd-trace c %zu floor %zu X %lld z %zu state %d need_pure %d nbad1 %llu len1 %zu orig %zu\n", j.coeffs_size, zfloor[f], x, j.zbytes.size(), (int) zstate[f].load(), (int) j.need_pure,
-                            (unsigned long long) j.last[0].nbad, j.len1, j.coeffs_orig);
-                }
-            bool any_pure = false;
-            for (size_t f = 0; f < n; f++) {
-                Job &j = jobs[f];
-                b.active[f] = 0;
-                if (j.const_field) continue;
-                const size_t len2 = (size_t) j.last[1].stream_bytes;
-                const bool decided = zfloor[f] > 0 && len2 < zfloor[f] + j.len1;              // (z may not be known - only that it loses)
-                if (decided || len2 < j.zbytes.size() + j.len1 || j.need_pure) {              // :838
-                    if (decided) log_info("frame %zu: pure base compression (%zu) beats base (%zu) + residual (at least %zu)", f, len2, j.len1, zfloor[f]);
-                    else if (len2 < j.zbytes.size() + j.len1)
-                        log_info("frame %zu: pure base compression (%zu) beats base (%zu) + residual (%zu)", f, len2, j.len1, j.zbytes.size());
-                    j.mean_err = j.last[1].err_sum / (double) n_pix;                          // :843
-                    j.zbytes.clear(); j.coeffs_size = 0;
-                    b.active[f] = 1; b.jf[f].cr = j.rs[1].result; any_pure = true;
-                }
-            }
-            if (any_pure) {
-                // the layer assignment of that rate again (allocation only, no decode), then its codestream
-                b.push_jf();
-                b.push_active();
-                launch_j2k_rate(jb, (int) nt, b.d_active, s);
-                b.collect_tails(jobs);
-            }
-        }
-        if (!zjoin()) return 1;
-        host_stats().add(zstd_us.load() + bound_us.load(), wait_us, zstd_bytes.load());
+        if (any_pure) { b.allocate(); b.collect_tails(jobs); }           // (that rate's layer assignment again, no decode)
     }
+    if (!es.join_all()) return false;
+    host_stats().add(es.zstd_us.load() + es.bound_us.load(), es.wait_us, es.zstd_bytes.load());
+    return true;
+}
 
-    pt.mark("fallback search + tails");
-    // ---- assemble (:863-907)
+// ---- :863-907: the frame streams - header, zstd payload, codestream (or the sample count of a constant field)
+int BatchEncode::assemble(uint8_t **outs, size_t *sizes)
+{
     for (size_t f = 0; f < n; f++) {
         Job &j = jobs[f];
         float minv = j.minv, maxv = j.maxv;
@@ -947,6 +821,31 @@ int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec
     pt.mark("assemble");
     return 0;
 }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// ebcc_encode for a batch of device-resident single-frame chunks.  Returns 0, 1 (error) or 2 (NaN/Inf).
+// ------------------------------------------------------------------------------------------------
+// `n` chunks of `tiles` frames each (tiles == 1: the frame-per-chunk case); `rctx`: residual engine for the stacked
+// chunk image when tiles > 1.
+int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, unsigned slices, PhaseNote *note)
+{
+    BatchEncode e(ctx, d_frames, n, cfg, next, tiles, rctx, slices, note);
+    if (const int r = e.analyse()) return r;                          // :671-692 (releases `next`)
+    e.first_probe();                                                  // :693-716
+    if (e.searching) {
+        e.search_1();                                                 // :728
+        e.queue_search_2();                                           // (:836, beside what follows)
+        if (!e.residual_layer()) return 1;                            // :730-762
+        e.truncation_search();                                        // :765-796
+        if (!e.entropy_and_fallback()) return 1;                      // :811-854 (tells `note`)
+    }
+    e.pt.mark("fallback search + tails");
+    return e.assemble(outs, sizes);                                   // :863-907
+}
+
 
 // One frame stream, either format: the 48-byte "EBCC" header (:190-202, :1234-1260) or the legacy header-less
 // prefix `f32 min, f32 max, u64 coeffs_size, f32 rmin, f32 rmax, u64 compressed_size` (ebcc_decode_legacy,

@@ -267,7 +267,7 @@ def test_tuning_knobs_do_not_change_results(monkeypatch):
     L.oracle().orc_set_j2k_backend(0)
     assert base[0] == L.orc_encode(frames[0], cfg) and base[16] == L.orc_encode(frames[16], cfg)
     for env in ({"EBCC_HOST_THREADS": "3"}, {"EBCC_T1_LPW": "8"}, {"EBCC_T1_LPW": "16,32,1,2"}, {"EBCC_HIP_SLICES": "2", "EBCC_HIP_DECODE_SLICES": "3"},
-                {"EBCC_HIP_SLICES": "4"}, {"EBCC_HIP_HOST_SEARCH": "1"}, {"EBCC_HIP_NO_SHORTCUTS": "1"}, {"EBCC_HIP_SLICES": "2", "EBCC_HIP_SPECULATION": "1"},
+                {"EBCC_HIP_SLICES": "4"}, {"EBCC_HIP_NO_SHORTCUTS": "1"}, {"EBCC_HIP_SLICES": "2", "EBCC_HIP_SPECULATION": "1"},
                 {"EBCC_HIP_SLICES": "1", "EBCC_HIP_SPECULATION": "0"}, {"EBCC_HOST_CPU_QUOTA": "2"}, {"EBCC_HIP_MQ_NATURAL_ORDER": "1"},
                 {"EBCC_HIP_TRUNC_LEVELS": "1"}, {"EBCC_HIP_TRUNC_LEVELS": "3"}):
         for k, v in env.items():
@@ -502,14 +502,15 @@ def test_chunking_in_several_batches_gives_the_same_container():
         assert r.returncode == 0 and r.stdout == one.stdout, (cap, r.stdout, r.stderr[-400:])
 
 
-def test_host_and_device_search_loops_agree(monkeypatch):
-    """The device-side state machines of the rate search and the truncation bisection (search.hpp) against the host
-    loops they replace, and batches of rounds too short for a search (more rounds are enqueued then)."""
+def test_search_loop_variants_agree(monkeypatch):
+    """The device-side state machines of the rate search and the truncation bisection (search.hpp) under their variants -
+    batches of rounds too short for a search (more rounds are enqueued then), with and without speculative rate
+    allocation, exact probes, one or three cut levels per round - give the default's streams, and those are the oracle's."""
     frames = np.stack([L.era5_like(96, 160, 700 + s, 1.0 + 0.15 * (s % 3), 0.5 + 0.2 * (s % 4)) for s in range(9)])
     for mode, err in ((L.MAX_ERROR, 0.03), (L.RELATIVE_ERROR, 2e-3)):
         cfg = L.make_config((1, 96, 160), base_cr=40.0, error=err, residual_type=mode)
         got = {}
-        for name, env in (("device", {}), ("host", {"EBCC_HIP_HOST_SEARCH": "1"}), ("short", {"EBCC_HIP_SEARCH_ROUNDS": "3"}),
+        for name, env in (("device", {}), ("short", {"EBCC_HIP_SEARCH_ROUNDS": "3"}),
                           ("plain", {"EBCC_HIP_SPECULATION": "0"}), ("spec", {"EBCC_HIP_SPECULATION": "1"}), ("exact", {"EBCC_HIP_NO_SHORTCUTS": "1"}),
                           # the truncation bisection one cut per round, three levels of look-ahead per round (default: two), and the
                           # look-ahead in batches of rounds too short for the search

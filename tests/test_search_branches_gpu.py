@@ -20,8 +20,8 @@ pytestmark = pytest.mark.gpu
 
 CASES = D.catalogue()
 FIXTURE = json.load(open(os.path.join(L.GOLDEN, "search_branches.json")))["cases"]
-VARIANTS = [{"EBCC_HIP_HOST_SEARCH": "1"}, {"EBCC_HIP_SEARCH_ROUNDS": "2"}, {"EBCC_HIP_TRUNC_LEVELS": "1"},
-            {"EBCC_HIP_TRUNC_LEVELS": "3"}, {"EBCC_HIP_SPECULATION": "0"}]
+VARIANTS = [{"EBCC_HIP_SEARCH_ROUNDS": "2"}, {"EBCC_HIP_TRUNC_LEVELS": "1"}, {"EBCC_HIP_TRUNC_LEVELS": "3"},
+            {"EBCC_HIP_SPECULATION": "0"}]
 
 
 def sha(b):
@@ -96,7 +96,7 @@ def _groups():
 def test_batches_and_search_variants(group, monkeypatch):
     """(b) Context.encode_frames: every case of one shape and quantile with the fields of all the others in one batch
     under its config (their searches end in different rounds), and (c) the same batches under the search variants
-    (host loops, short batches of rounds, one / three cut levels per round, no speculative rate allocation).  The case's
+    (short batches of rounds, one / three cut levels per round, no speculative rate allocation).  The case's
     own frame is the reference's stream, every other frame the product's single-frame stream of the same input, and
     Context.decode_frames gives the oracle's decode."""
     (shape, quantile), cases = group
