@@ -68,6 +68,32 @@ std::mutex &device_mutex(int dev)
     static std::mutex m[64];
     return m[dev & 63];
 }
+
+// The prologue of every entry point that works on a device: the device's lock, the device current (DeviceScope), and an
+// exception turned into a logged failure that returns `fail`.  on_codec also needs libzstd, as every encode and the decode
+// of a residual layer do.
+template <class R, class Fn>
+R on_device(int device, R fail, Fn &&fn)
+{
+    try {
+        std::lock_guard<std::mutex> lock(device_mutex(device));
+        DeviceScope scope(device);
+        return fn();
+    } catch (const std::exception &e) {
+        log_fatal("MI355X engine failure: %s", e.what());
+        set_error("%s", e.what());
+        return fail;
+    }
+}
+template <class R, class Fn>
+R on_codec(int device, R fail, Fn &&fn)
+{
+    return on_device(device, fail, [&]() -> R {
+        if (!zstd().ok) { log_fatal("libzstd not available"); return fail; }
+        return fn();
+    });
+}
+
 std::mutex g_map_mutex;
 std::map<std::tuple<int, int, int, int>, ebcc_hip_ctx *> g_ctx;
 
@@ -149,6 +175,36 @@ static void copy_pageable(ebcc_hip_ctx *ctx, void *host, void *dev, size_t bytes
     }
 }
 
+// A fresh allocation of hundreds of MB is unmapped pages: a download into it would fault them in one by one on the copying
+// threads.  Huge pages where the system grants them (512 x fewer faults), and a few host threads that touch the pages
+// meanwhile (while the GPU decodes).
+constexpr size_t kFreshPagesBytes = (size_t) 64 << 20;
+void huge_pages(void *p, size_t bytes)
+{
+    if (bytes < kFreshPagesBytes) return;
+    const uintptr_t a = ((uintptr_t) p + ((size_t) 2 << 20) - 1) & ~(((uintptr_t) 2 << 20) - 1), e = ((uintptr_t) p + bytes) & ~(((uintptr_t) 2 << 20) - 1);
+    if (e > a) madvise((void *) a, e - a, MADV_HUGEPAGE);
+}
+struct Prefault {
+    std::vector<std::thread> pool;
+    Prefault(void *p, size_t bytes)
+    {
+        const size_t nthreads = bytes >= kFreshPagesBytes ? std::min<size_t>(16, std::max(1u, (unsigned) entropy_threads(1))) : 0;
+        huge_pages(p, bytes);
+        try {
+            for (size_t t = 0; t < nthreads; t++)
+                pool.emplace_back([=]() {
+                    volatile char *c = (volatile char *) p;
+                    const size_t lo = bytes / nthreads * t, hi = t + 1 == nthreads ? bytes : bytes / nthreads * (t + 1);
+                    for (size_t i = lo; i < hi; i += 4096) c[i] = 0;
+                });
+        } catch (const std::exception &) {}                         // (no thread to be had: the download faults the pages in itself)
+    }
+    std::mutex m;                                                   // (one device thread per device may come here)
+    void join() { std::lock_guard<std::mutex> g(m); for (auto &t : pool) if (t.joinable()) t.join(); }
+    ~Prefault() { join(); }
+};
+
 // Frames per device batch of the host-pointer entry points: EBCC_HIP_MAX_BATCH (default 256), reduced for large
 // frames so that an engine's workspace (about 160 bytes per pixel and frame with the worst-case slots) stays
 // under ~48 GB.
@@ -161,22 +217,23 @@ size_t batch_capacity(size_t n_pix)
     return std::max<size_t>(1, std::min(v, fit));
 }
 
-// the engine of the tiles and, for chunks of several frames, the engine of the stacked chunk image
+// the engine of the tiles and, for chunks of several frames, the engine of the stacked chunk image (false: logged)
 bool chunk_engines(int device, int H, int W, size_t chunks, size_t tiles, ebcc_hip_ctx **ctx, ebcc_hip_ctx **rc)
 {
+    auto none = [] { log_fatal("no MI355X engine available: %s", ebcc_hip_last_error()); return false; };
     *rc = nullptr;
     if (tiles > 1) {
         *rc = get_context(device, (int) (tiles * (size_t) H), W, chunks);
-        if (!*rc) return false;
+        if (!*rc) return none();
     }
     const int period = tiles > 1 && !tile_geometry_uniform((size_t) H) ? (int) tiles : 1;
     *ctx = get_context(device, H, W, chunks * tiles, period);
-    if (!*ctx) return false;
+    if (!*ctx) return none();
     if (tiles > 1) {                                             // (creating the second engine may have evicted the first)
         *rc = get_context(device, (int) (tiles * (size_t) H), W, chunks);
-        if (!*rc) return false;
+        if (!*rc) return none();
         std::lock_guard<std::mutex> lock(g_map_mutex);
-        if (g_ctx.find(std::make_tuple(device, H, W, period)) == g_ctx.end()) return false;
+        if (g_ctx.find(std::make_tuple(device, H, W, period)) == g_ctx.end()) return none();
     }
     return true;
 }
@@ -217,178 +274,9 @@ struct ChunkBox {
     }
 };
 
-int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
-                      GpuPhase *phase = nullptr);
-int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out);
-
-// n_frames one-frame chunks in batches of the context's capacity, alternately on the context's engines and on a second set
-// (ebcc_hip_ctx::twin, made on first use; without memory for it the batches run one after the other on the first):
-// one batch at a time is in its GPU phase, the next enters it when every slice of the current one has reached its
-// entropy stage (GpuPhase / PhaseNote).  stage(set, first frame, count) -> where the batch's frames are on the device
-// (a host array is uploaded there: that copy runs beside the other batch's kernels too).
-template <class Stage>
-int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes, Stage stage)
-{
-    const size_t cap = ctx->max_frames, batches = (n_frames + cap - 1) / cap;
-    if (batches == 1) return run_encode_slices(ctx, stage(ctx, (size_t) 0, n_frames), n_frames, cfg, outs, sizes);
-    // (a second set that could not be made is not tried again at every call - tens of GB allocated and freed each time -
-    //  until ebcc_hip_release_engines / a new context gives the memory a chance to have changed)
-    if (!ctx->twin && !ctx->twin_failed) {
-        ctx->twin = ebcc_hip_create(ctx->device, cap, (size_t) ctx->height, (size_t) ctx->width);
-        if (!ctx->twin) ctx->twin_failed = true;
-    }
-    ebcc_hip_ctx *const set[2] = {ctx, ctx->twin};
-    GpuPhase phase;
-    std::atomic<int> worst{0};
-    std::atomic<size_t> next{0};
-    std::mutex redo_m;
-    std::vector<size_t> redo;                                        // batches the second set could not stage
-    std::string err[2];
-    auto work = [&](int t) {
-        try {
-            EBCC_HIP_CHECK(hipSetDevice(ctx->device));
-            for (;;) {
-                size_t b = next++;
-                if (b >= batches) {
-                    if (t != 0) break;
-                    std::lock_guard<std::mutex> l(redo_m);
-                    if (redo.empty()) break;
-                    b = redo.back(); redo.pop_back();
-                }
-                if (worst.load()) break;
-                const size_t lo = b * cap, cnt = std::min(cap, n_frames - lo);
-                const float *where = nullptr;
-                try { where = stage(set[t], lo, cnt); }
-                catch (const std::exception &e) {
-                    // the second set has no room for its image of the frames: the first set does its batches after its own
-                    if (t == 0) throw;
-                    log_warn("second engine set: %s - its batches run on the first", e.what());
-                    clear_error();
-                    std::lock_guard<std::mutex> l(redo_m);
-                    redo.push_back(b);
-                    for (size_t r = next++; r < batches; r = next++) redo.push_back(r);
-                    return;
-                }
-                const int r = run_encode_slices(set[t], where, cnt, cfg, outs + lo, sizes + lo, &phase);
-                if (r) { err[t] = ebcc_hip_last_error(); int e = 0; worst.compare_exchange_strong(e, r); }
-            }
-        } catch (const std::exception &e) { err[t] = e.what(); int z = 0; worst.compare_exchange_strong(z, 1); }
-    };
-    if (set[1]) {
-        std::thread second(work, 1);
-        work(0);
-        second.join();
-        work(0);                                                      // (what the second set handed back after the first had finished)
-    } else {
-        work(0);
-    }
-    if (worst.load()) set_error("%s", (err[0].empty() ? err[1] : err[0]).c_str());
-    return worst.load();
-}
-
-// The decode counterpart: batches of `cap` frames alternately on the two engine sets, both free-running - one batch's
-// download (or, for long residual streams, its one-wave-per-frame SPIHT chains, which leave most of the chip idle) beside
-// the other's kernels.  each(set, first frame, count) decodes one batch and puts its output where it belongs.
-template <class Each>
-int decode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, size_t cap, Each each)
-{
-    const size_t batches = (n_frames + cap - 1) / cap;
-    if (batches == 1) return each(ctx, (size_t) 0, n_frames);
-    if (!ctx->twin && !ctx->twin_failed) {
-        ctx->twin = ebcc_hip_create(ctx->device, ctx->max_frames, (size_t) ctx->height, (size_t) ctx->width);
-        if (!ctx->twin) ctx->twin_failed = true;
-    }
-    ebcc_hip_ctx *const set[2] = {ctx, ctx->twin};
-    std::atomic<int> worst{0};
-    std::string err[2];
-    auto work = [&](int t) {
-        try {
-            EBCC_HIP_CHECK(hipSetDevice(ctx->device));
-            for (size_t b = (size_t) t; b < batches && !worst.load(); b += set[1] ? 2 : 1) {
-                const size_t lo = b * cap;
-                const int r = each(set[t], lo, std::min(cap, n_frames - lo));
-                if (r) { err[t] = ebcc_hip_last_error(); int e = 0; worst.compare_exchange_strong(e, r); }
-            }
-        } catch (const std::exception &e) { err[t] = e.what(); int z = 0; worst.compare_exchange_strong(z, 1); }
-    };
-    if (set[1]) {
-        std::thread second(work, 1);
-        work(0);
-        second.join();
-    } else {
-        work(0);
-    }
-    if (worst.load()) set_error("%s", (err[0].empty() ? err[1] : err[0]).c_str());
-    return worst.load();
-}
-
-// host-pointer convenience used by the reference-compatible entry points
-// n chunks of `tiles` frames of H x W each, contiguous in host memory, on device `device`.  Returns 0 ok, 1 error (logged),
-// 2 NaN / Inf in the data (the caller exits as the reference does, /root/reference/src/ebcc_codec.c:598-605).
-int encode_host_frames(int device, const float *data, size_t n, int H, int W, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
-                       size_t tiles = 1)
-{
-    try {
-        std::lock_guard<std::mutex> lock(device_mutex(device));
-        DeviceScope scope(device);
-        const size_t n_pix = (size_t) H * W * tiles;
-        const size_t cap = std::min(n, batch_capacity(n_pix));
-        ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
-        PhaseTimer pt;
-        if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) { log_fatal("no MI355X engine available: %s", ebcc_hip_last_error()); return 1; }
-        pt.mark("host frames: engine");
-        // (a batch is uploaded in one go: uploads issued from inside the slices slow every slice down - measured in round 1 with
-        //  pageable copies, 5.6 against 3.7 GB/s, and again in round 2 through the bounce buffers, 7.1 against 6.5)
-        if (tiles == 1 && ctx->max_frames == cap)                   // one-frame chunks: concurrent slices, batches on alternating engine sets
-            return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
-                float *d = io_buffer(set, cap * n_pix * sizeof(float));
-                copy_pageable(set, const_cast<float *>(data + lo * n_pix), d, cnt * n_pix * sizeof(float), false);
-                pt.mark("host frames: upload");
-                return (const float *) d;
-            });
-        float *d = io_buffer(ctx, cap * n_pix * sizeof(float));
-        size_t done = 0;
-        while (done < n) {
-            size_t k = std::min(cap, n - done);
-            copy_pageable(ctx, const_cast<float *>(data + done * n_pix), d, k * n_pix * sizeof(float), false);
-            const int rcode = tiles == 1 ? run_encode_slices(ctx, d, k, cfg, outs + done, sizes + done)
-                                         : encode_batch(ctx, d, k, cfg, outs + done, sizes + done, nullptr, tiles, rc);
-            if (rcode) return rcode;
-            done += k;
-        }
-        return 0;
-    } catch (const std::exception &e) {
-        log_fatal("MI355X engine failure: %s", e.what());
-        set_error("%s", e.what());
-        return 1;
-    }
-}
-
-// A list of independent chunks spread over the devices of device_list(): contiguous blocks, one host thread per device
-// (/root/reference/src/ebcc_codec.c:1007-1046 is a serial loop over the chunks; the order of the results is that of the
-// chunks).  fn(device, first, count) -> status; returns the worst status.
-template <class Fn>
-int run_on_devices(size_t n_chunks, Fn fn)
-{
-    std::vector<int> devs = device_list();
-    if (devs.size() > n_chunks) devs.resize(std::max<size_t>(1, n_chunks));
-    if (devs.size() == 1) return fn(devs[0], (size_t) 0, n_chunks);
-    const size_t per = (n_chunks + devs.size() - 1) / devs.size();
-    std::vector<int> rc(devs.size(), 0);
-    std::vector<std::thread> th;
-    for (size_t i = 0; i < devs.size(); i++) {
-        const size_t lo = i * per, hi = std::min(n_chunks, lo + per);
-        if (lo >= hi) break;
-        th.emplace_back([&, i, lo, hi]() { rc[i] = fn(devs[i], lo, hi - lo); });
-    }
-    for (auto &t : th) t.join();
-    int worst = 0;
-    for (int r : rc) worst = std::max(worst, r);
-    return worst;
-}
-
-}  // namespace
-
+// ================================================================================================
+// slices of a batch
+// ================================================================================================
 // Slices of a batch: EBCC_HIP_SLICES (encode, 1 = off) / EBCC_HIP_DECODE_SLICES engines of max_frames / slices
 // frames each, created on first use.  Small batches stay on the context's own engine.  More than two slices only
 // pay when the HIP runtime has a hardware queue for each stream (GPU_MAX_HW_QUEUES, default 4, shared with the
@@ -399,7 +287,7 @@ int run_on_devices(size_t n_chunks, Fn fn)
 // (A/B on one box, tools/gpu/ab_dec.sh: 33 GB/s with one slice, 27 with two).
 constexpr size_t kDefaultDecodeSlices = 1;
 constexpr size_t kSliceFromFrames = 96;                             // smaller batches run as one slice unless the environment says otherwise
-static size_t default_encode_slices()
+size_t default_encode_slices()
 {
     // Four with eight hardware queues in round 1; two at the end of round 2 (the search loops had moved to the device and every
     // further slice repeated the latency-bound launches for fewer frames: 8.4-8.5 GB/s with two, 6.8-7.5 with four); three
@@ -408,14 +296,20 @@ static size_t default_encode_slices()
     // per step with two, 146-153 with three, 160-165 with four).
     return 3;
 }
-static size_t slice_engines(ebcc_hip_ctx *ctx, size_t n_frames, const char *env_name, size_t k)
+// slices of a batch of n_frames: `k` unless the environment (env_name) says otherwise
+size_t slice_count(size_t n_frames, const char *env_name, size_t k)
 {
     // (a batch below about a hundred frames is a chain whatever it is cut into - 43 frames of 721 x 1440: 53.9 ms per step as
     //  one slice, 56.8 as two, 60.3 as three; 85 frames: 75.8 / 77.4 / 76.4; 128 frames: 85.9 / 84.6 / 83.0, tools/gpu/slices_frames.sh)
     if (const char *e = getenv(env_name)) k = (size_t) std::max(1L, strtol(e, nullptr, 10));
     else if (n_frames < kSliceFromFrames) k = 1;
     k = std::min<size_t>(k, 8);
-    if (k < 2 || n_frames < 4 * k) return 1;
+    return k < 2 || n_frames < 4 * k ? 1 : k;
+}
+size_t slice_engines(ebcc_hip_ctx *ctx, size_t n_frames, const char *env_name, size_t k)
+{
+    k = slice_count(n_frames, env_name, k);
+    if (k == 1) return 1;
     const size_t per = (ctx->max_frames + k - 1) / k;
     for (size_t i = 0; i + 1 < k; i++) {                    // slice 0 runs on the context's own engine
         if (i < ctx->lanes.size() && ctx->lanes[i]->max_frames >= per) continue;
@@ -432,7 +326,7 @@ static size_t slice_engines(ebcc_hip_ctx *ctx, size_t n_frames, const char *env_
 }
 
 template <class Fn>
-static int run_slices(ebcc_hip_ctx *ctx, size_t n_frames, Fn fn, const char *env_name, size_t default_slices)
+int run_slices(ebcc_hip_ctx *ctx, size_t n_frames, Fn fn, const char *env_name, size_t default_slices)
 {
     const size_t k = slice_engines(ctx, n_frames, env_name, default_slices);
     if (k == 1) return fn(ctx, (size_t) 0, n_frames, (SliceGate *) nullptr, 1u);
@@ -467,11 +361,9 @@ static int run_slices(ebcc_hip_ctx *ctx, size_t n_frames, Fn fn, const char *env
     return worst;
 }
 
-namespace {
-
 // n_frames one-frame chunks as concurrent slices
 int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
-                      GpuPhase *phase)
+                      GpuPhase *phase = nullptr)
 {
     const size_t n_pix = ctx->n_pix;
     PhaseNote note;
@@ -495,37 +387,266 @@ int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const si
     }, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);
 }
 
+// ================================================================================================
+// batches on two alternating engine sets
+// ================================================================================================
+// The context's engines and a second set of the same size (ebcc_hip_ctx::twin, made on first use), one host thread each.
+// Without memory for the second set the first runs every batch; a second set that could not be made is not tried again at
+// every call - tens of GB allocated and freed each time - until ebcc_hip_release_second_set / a new context gives the
+// memory a chance to have changed.  The schedulers below decide which batch runs where; this owns the second set, the
+// threads and the first failure.
+struct TwoSets {
+    ebcc_hip_ctx *set[2];
+    std::atomic<int> worst{0};
+    std::string err[2];
+    explicit TwoSets(ebcc_hip_ctx *ctx)
+    {
+        if (!ctx->twin && !ctx->twin_failed) {
+            ctx->twin = ebcc_hip_create(ctx->device, ctx->max_frames, (size_t) ctx->height, (size_t) ctx->width);
+            if (!ctx->twin) ctx->twin_failed = true;
+        }
+        set[0] = ctx;
+        set[1] = ctx->twin;
+    }
+    bool failed() const { return worst.load() != 0; }
+    void fail(int t, int r, const char *what) { err[t] = what; int e = 0; worst.compare_exchange_strong(e, r); }
+    void note(int t, int r) { if (r) fail(t, r, ebcc_hip_last_error()); }          // a batch's status on set t's thread
+    // work(t) on set t's thread, with the device current there
+    template <class Work> void run(int t, Work &work)
+    {
+        try {
+            EBCC_HIP_CHECK(hipSetDevice(set[0]->device));
+            work(t);
+        } catch (const std::exception &e) { fail(t, 1, e.what()); }
+    }
+    // work(1) on a second thread beside work(0) on this one (work(0) alone without a second set)
+    template <class Work> void both(Work &work)
+    {
+        if (!set[1]) { run(0, work); return; }
+        std::thread second([&] { run(1, work); });
+        run(0, work);
+        second.join();
+    }
+    // the worst status; the first failure's text is this thread's last error
+    int status() { if (failed()) set_error("%s", (err[0].empty() ? err[1] : err[0]).c_str()); return worst.load(); }
+};
+
+// n_frames one-frame chunks in batches of the context's capacity, alternately on the two sets: one batch at a time is in its
+// GPU phase, the next enters it when every slice of the current one has reached its entropy stage (GpuPhase / PhaseNote).
+// stage(set, first frame, count) -> where the batch's frames are on the device (a host array is uploaded there: that copy
+// runs beside the other batch's kernels too).
+template <class Stage>
+int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes, Stage stage)
+{
+    const size_t cap = ctx->max_frames, batches = (n_frames + cap - 1) / cap;
+    if (batches == 1) return run_encode_slices(ctx, stage(ctx, (size_t) 0, n_frames), n_frames, cfg, outs, sizes);
+    TwoSets two(ctx);
+    GpuPhase phase;
+    std::atomic<size_t> next{0};
+    std::mutex redo_m;
+    std::vector<size_t> redo;                                        // batches the second set could not stage
+    auto work = [&](int t) {
+        for (;;) {
+            size_t b = next++;
+            if (b >= batches) {
+                if (t != 0) break;
+                std::lock_guard<std::mutex> l(redo_m);
+                if (redo.empty()) break;
+                b = redo.back(); redo.pop_back();
+            }
+            if (two.failed()) break;
+            const size_t lo = b * cap, cnt = std::min(cap, n_frames - lo);
+            const float *where = nullptr;
+            try { where = stage(two.set[t], lo, cnt); }
+            catch (const std::exception &e) {
+                // the second set has no room for its image of the frames: the first set does its batches after its own
+                if (t == 0) throw;
+                log_warn("second engine set: %s - its batches run on the first", e.what());
+                clear_error();
+                std::lock_guard<std::mutex> l(redo_m);
+                redo.push_back(b);
+                for (size_t r = next++; r < batches; r = next++) redo.push_back(r);
+                return;
+            }
+            two.note(t, run_encode_slices(two.set[t], where, cnt, cfg, outs + lo, sizes + lo, &phase));
+        }
+    };
+    two.both(work);
+    if (two.set[1]) two.run(0, work);                               // (what the second set handed back after the first had finished)
+    return two.status();
+}
+
+// The decode counterpart: both sets free-running on the odd and the even batches - one batch's download (or, for long
+// residual streams, its one-wave-per-frame SPIHT chains, which leave most of the chip idle) beside the other's kernels.
+// each(set, first frame, count) decodes one batch and puts its output where it belongs.
+template <class Each>
+int decode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, Each each)
+{
+    const size_t cap = ctx->max_frames, batches = (n_frames + cap - 1) / cap;
+    if (batches == 1) return each(ctx, (size_t) 0, n_frames);
+    TwoSets two(ctx);
+    auto work = [&](int t) {
+        for (size_t b = (size_t) t; b < batches && !two.failed(); b += two.set[1] ? 2 : 1) {
+            const size_t lo = b * cap;
+            two.note(t, each(two.set[t], lo, std::min(cap, n_frames - lo)));
+        }
+    };
+    two.both(work);
+    return two.status();
+}
+
+// ================================================================================================
+// frames in pageable host memory <-> streams
+// ================================================================================================
+// n chunks of `tiles` frames each (tiles > 1: rc is the engine of the stacked chunk image), contiguous in host memory, in
+// batches of `cap` chunks on ctx.  A batch is uploaded in one go: uploads issued from inside the slices slow every slice
+// down (measured in round 1 with pageable copies, 5.6 against 3.7 GB/s, and again in round 2 through the bounce buffers,
+// 7.1 against 6.5).  One-frame chunks in batches that fill the engine run on the alternating sets, anything else batch
+// after batch.  0 ok, 1 error, 2 NaN / Inf in the data.
+int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const float *data, size_t n, const codec_config_t *cfg,
+                     uint8_t **outs, size_t *sizes)
+{
+    const size_t n_pix = ctx->n_pix * tiles;
+    PhaseTimer pt[2];                                               // (one per engine set: each has its own thread)
+    auto stage = [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
+        float *d = io_buffer(set, cap * n_pix * sizeof(float));
+        copy_pageable(set, const_cast<float *>(data + lo * n_pix), d, cnt * n_pix * sizeof(float), false);
+        pt[set != ctx].mark("host frames: upload");
+        return (const float *) d;
+    };
+    if (tiles == 1 && ctx->max_frames == cap) return encode_batches_alternating(ctx, n, cfg, outs, sizes, stage);
+    for (size_t lo = 0; lo < n; lo += cap) {
+        const size_t k = std::min(cap, n - lo);
+        const float *d = stage(ctx, lo, k);
+        const int r = tiles == 1 ? run_encode_slices(ctx, d, k, cfg, outs + lo, sizes + lo)
+                                 : encode_batch(ctx, d, k, cfg, outs + lo, sizes + lo, nullptr, tiles, rc);
+        if (r) return r;
+    }
+    return 0;
+}
+
+// The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
+// the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
+int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
+                   float *out, Prefault *prefault)
+{
+    const size_t n_pix = ctx->n_pix * tiles;
+    auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+        PhaseTimer pt;
+        float *d = io_buffer(set, cap * n_pix * sizeof(float));
+        pt.mark("host decode: device image");
+        const int r = tiles > 1 ? decode_tiled(set, rc, streams + lo, sizes + lo, k, tiles, d) : run_decode_slices(set, streams + lo, sizes + lo, k, d);
+        if (r) return r;
+        pt.mark("host decode: decode");
+        if (prefault) prefault->join();
+        pt.mark("host decode: output pages");
+        copy_pageable(set, out + lo * n_pix, d, k * n_pix * sizeof(float), true);
+        pt.mark("host decode: download");
+        return 0;
+    };
+    if (tiles == 1 && ctx->max_frames == cap) return decode_batches_alternating(ctx, n, one_batch);
+    for (size_t lo = 0; lo < n; lo += cap) {
+        const int r = one_batch(ctx, lo, std::min(cap, n - lo));
+        if (r) return r;
+    }
+    return 0;
+}
+
+// The reference-compatible entry points' host arrays on the engines cached for `device`: n chunks of `tiles` frames of
+// H x W each.  Returns 0 ok, 1 error (logged), 2 NaN / Inf in the data (the caller exits as the reference does,
+// /root/reference/src/ebcc_codec.c:598-605).
+int encode_on_device(int device, const float *data, size_t n, int H, int W, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+                     size_t tiles = 1)
+{
+    return on_codec(device, 1, [&] {
+        const size_t cap = std::min(n, batch_capacity((size_t) H * W * tiles));
+        ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
+        PhaseTimer pt;
+        if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) return 1;
+        pt.mark("host frames: engine");
+        return encode_from_host(ctx, rc, tiles, cap, data, n, cfg, outs, sizes);
+    });
+}
+
+// A list of independent chunks spread over the devices of device_list(): contiguous blocks, one host thread per device
+// (/root/reference/src/ebcc_codec.c:1007-1046 is a serial loop over the chunks; the order of the results is that of the
+// chunks).  fn(device, first, count) -> status; returns the worst status.
+template <class Fn>
+int run_on_devices(size_t n_chunks, Fn fn)
+{
+    std::vector<int> devs = device_list();
+    if (devs.size() > n_chunks) devs.resize(std::max<size_t>(1, n_chunks));
+    if (devs.size() == 1) return fn(devs[0], (size_t) 0, n_chunks);
+    const size_t per = (n_chunks + devs.size() - 1) / devs.size();
+    std::vector<int> rc(devs.size(), 0);
+    std::vector<std::thread> th;
+    for (size_t i = 0; i < devs.size(); i++) {
+        const size_t lo = i * per, hi = std::min(n_chunks, lo + per);
+        if (lo >= hi) break;
+        th.emplace_back([&, i, lo, hi]() { rc[i] = fn(devs[i], lo, hi - lo); });
+    }
+    for (auto &t : th) t.join();
+    int worst = 0;
+    for (int r : rc) worst = std::max(worst, r);
+    return worst;
+}
+
+// ================================================================================================
+// what the batch entry points of a caller's context share
+// ================================================================================================
+// Encode: the argument checks, out_streams emptied first and, when the call fails, every stream made so far freed again;
+// code() runs in the device prologue and returns the status.
+template <class Code>
+int encode_call(const char *who, ebcc_hip_ctx *ctx, const void *frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+                Code &&code)
+{
+    if (!ctx || !frames || !cfg || !outs || !sizes || n < 1) { set_error("%s: bad arguments", who); return 1; }
+    if (cfg->dims[0] != 1 || (int) cfg->dims[1] != ctx->height || (int) cfg->dims[2] != ctx->width) {
+        set_error("%s: config dims must be (1, %d, %d)", who, ctx->height, ctx->width);
+        return 1;
+    }
+    log_set_level_from_env();
+    for (size_t f = 0; f < n; f++) { outs[f] = nullptr; sizes[f] = 0; }
+    const int rc = on_codec(ctx->device, 1, code);
+    if (rc)
+        for (size_t f = 0; f < n; f++) { free(outs[f]); outs[f] = nullptr; sizes[f] = 0; }
+    return rc;
+}
+
+// device-resident frames: batches of the context's capacity on the alternating sets (one batch: one run_encode_slices)
+int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes)
+{
+    return encode_call(who, ctx, d_frames, n, cfg, outs, sizes, [&] {
+        return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * ctx->n_pix; });
+    });
+}
+int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out)
+{
+    if (!ctx || !streams || !sizes || !d_out || n < 1) { set_error("%s: bad arguments", who); return 1; }
+    return on_codec(ctx->device, 1, [&] {
+        return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + lo * ctx->n_pix);
+        });
+    });
+}
+
 }  // namespace
 
 namespace ebcc {
 
 int cached_encode_host_frames(const float *h_frames, size_t n, int H, int W, const codec_config_t *cfg, uint8_t **outs, size_t *sizes)
 {
-    return encode_host_frames(resolve_device(), h_frames, n, H, W, cfg, outs, sizes);
+    return encode_on_device(resolve_device(), h_frames, n, H, W, cfg, outs, sizes);
 }
 
 int cached_decode_host_frames(const uint8_t *const *streams, const size_t *sizes, size_t n, int H, int W, float *h_out)
 {
-    try {
-        const int device = resolve_device();
-        std::lock_guard<std::mutex> lock(device_mutex(device));
-        DeviceScope scope(device);
-        if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-        const size_t n_pix = (size_t) H * W, cap = std::min(n, batch_capacity(n_pix));
-        ebcc_hip_ctx *ctx = get_context(device, H, W, cap);
-        if (!ctx) { log_fatal("no MI355X engine available: %s", ebcc_hip_last_error()); return 1; }
-        return decode_batches_alternating(ctx, n, ctx->max_frames, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-            float *d = io_buffer(set, ctx->max_frames * n_pix * sizeof(float));
-            const int r = run_decode_slices(set, streams + lo, sizes + lo, k, d);
-            if (r) return r;
-            copy_pageable(set, h_out + lo * n_pix, d, k * n_pix * sizeof(float), true);
-            return 0;
-        });
-    } catch (const std::exception &e) {
-        log_fatal("MI355X engine failure: %s", e.what());
-        set_error("%s", e.what());
-        return 1;
-    }
+    const int device = resolve_device();
+    return on_codec(device, 1, [&] {
+        ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
+        if (!chunk_engines(device, H, W, std::min(n, batch_capacity((size_t) H * W)), 1, &ctx, &rc)) return 1;
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n, h_out, nullptr);
+    });
 }
 
 }  // namespace ebcc
@@ -559,14 +680,7 @@ void print_config(codec_config_t *c)
 
 int ebcc_hip_host_threads(int slices) { return (int) entropy_threads((unsigned) std::max(1, slices)); }
 int ebcc_hip_default_encode_slices(void) { return (int) default_encode_slices(); }
-int ebcc_hip_encode_slices_for(size_t n_frames)
-{
-    size_t k = default_encode_slices();
-    if (const char *e = getenv("EBCC_HIP_SLICES")) k = (size_t) std::max(1L, strtol(e, nullptr, 10));
-    else if (n_frames < kSliceFromFrames) k = 1;
-    k = std::min<size_t>(k, 8);
-    return k < 2 || n_frames < 4 * k ? 1 : (int) k;
-}
+int ebcc_hip_encode_slices_for(size_t n_frames) { return (int) slice_count(n_frames, "EBCC_HIP_SLICES", default_encode_slices()); }
 
 // out[0..6] = usable CPUs (affinity mask cut to the cgroup quota), CPU quota (0: none), zstd core-seconds, seconds the
 // slices waited for the zstd workers, bytes compressed, entropy batches, prefix bytes whose compression was proved
@@ -590,58 +704,26 @@ void ebcc_hip_host_stats(double *out, int reset)
     if (reset) h.reset();
 }
 
-// A fresh allocation of hundreds of MB is unmapped pages: a download into it would fault them in one by one on the copying
-// threads.  A few host threads ask for huge pages and touch them meanwhile (while the GPU decodes).
-struct Prefault {
-    std::vector<std::thread> pool;
-    Prefault(void *p, size_t bytes)
-    {
-        const size_t nthreads = bytes >= ((size_t) 64 << 20) ? std::min<size_t>(16, std::max(1u, (unsigned) entropy_threads(1))) : 0;
-        if (nthreads) {                                             // huge pages where the system grants them: 512 x fewer faults
-            const uintptr_t a = ((uintptr_t) p + ((size_t) 2 << 20) - 1) & ~(((uintptr_t) 2 << 20) - 1), e = ((uintptr_t) p + bytes) & ~(((uintptr_t) 2 << 20) - 1);
-            if (e > a) madvise((void *) a, e - a, MADV_HUGEPAGE);
-        }
-        try {
-            for (size_t t = 0; t < nthreads; t++)
-                pool.emplace_back([=]() {
-                    volatile char *c = (volatile char *) p;
-                    const size_t lo = bytes / nthreads * t, hi = t + 1 == nthreads ? bytes : bytes / nthreads * (t + 1);
-                    for (size_t i = lo; i < hi; i += 4096) c[i] = 0;
-                });
-        } catch (const std::exception &) {}                         // (no thread to be had: the download faults the pages in itself)
-    }
-    std::mutex m;                                                   // (one device thread per device may come here)
-    void join() { std::lock_guard<std::mutex> g(m); for (auto &t : pool) if (t.joinable()) t.join(); }
-    ~Prefault() { join(); }
-};
-
 // A pageable host array <-> device memory at PCIe speed: through the engine's two pinned bounce buffers with several host
 // threads copying (copy_pageable) instead of hipMemcpy's single staging thread (~10 GB/s, and a fresh destination's page
 // faults on top) - what ebcc_decode_chunking does for its own output, for callers of the frames API that keep their
 // frames in host memory (ebcc_amd/h5_batch.py).  Return 0 = ok.
 int ebcc_hip_upload(ebcc_hip_ctx *ctx, void *d_dst, const void *h_src, size_t bytes)
 {
-    EBCC_API_TRY
     if (!ctx || !d_dst || !h_src) { set_error("ebcc_hip_upload: null argument"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    copy_pageable(ctx, const_cast<void *>(h_src), d_dst, bytes, false);
-    return 0;
-    EBCC_API_CATCH(1)
+    return on_device(ctx->device, 1, [&] {
+        copy_pageable(ctx, const_cast<void *>(h_src), d_dst, bytes, false);
+        return 0;
+    });
 }
 int ebcc_hip_download(ebcc_hip_ctx *ctx, void *h_dst, const void *d_src, size_t bytes)
 {
-    EBCC_API_TRY
     if (!ctx || !h_dst || !d_src) { set_error("ebcc_hip_download: null argument"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    if (bytes >= ((size_t) 64 << 20)) {                                   // huge pages where the system grants them: 512 x fewer faults on a fresh array
-        const uintptr_t a = ((uintptr_t) h_dst + ((size_t) 2 << 20) - 1) & ~(((uintptr_t) 2 << 20) - 1), e = ((uintptr_t) h_dst + bytes) & ~(((uintptr_t) 2 << 20) - 1);
-        if (e > a) madvise((void *) a, e - a, MADV_HUGEPAGE);
-    }
-    copy_pageable(ctx, h_dst, const_cast<void *>(d_src), bytes, true);
-    return 0;
-    EBCC_API_CATCH(1)
+    return on_device(ctx->device, 1, [&] {
+        huge_pages(h_dst, bytes);                                       // (a fresh array: fewer faults)
+        copy_pageable(ctx, h_dst, const_cast<void *>(d_src), bytes, true);
+        return 0;
+    });
 }
 
 // The pages of a host array that is about to receive a download, mapped by several threads (huge pages where granted);
@@ -664,48 +746,19 @@ int ebcc_hip_prefault(void *h_dst, size_t bytes)
 int ebcc_hip_encode_host_frames(ebcc_hip_ctx *ctx, const float *h_frames, size_t n_frames, const codec_config_t *config,
                                 uint8_t **out_streams, size_t *out_sizes)
 {
-    EBCC_API_TRY
-    if (!ctx || !h_frames || !config || !out_streams || !out_sizes || n_frames < 1) { set_error("ebcc_hip_encode_host_frames: bad arguments"); return 1; }
-    if (config->dims[0] != 1 || (int) config->dims[1] != ctx->height || (int) config->dims[2] != ctx->width) {
-        set_error("ebcc_hip_encode_host_frames: config dims must be (1, %d, %d)", ctx->height, ctx->width);
-        return 1;
-    }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    log_set_level_from_env();
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    for (size_t f = 0; f < n_frames; f++) { out_streams[f] = nullptr; out_sizes[f] = 0; }
-    const size_t n_pix = ctx->n_pix, cap = ctx->max_frames;
-    const int rc = encode_batches_alternating(ctx, n_frames, config, out_streams, out_sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
-        float *d = io_buffer(set, cap * n_pix * sizeof(float));
-        copy_pageable(set, const_cast<float *>(h_frames + lo * n_pix), d, cnt * n_pix * sizeof(float), false);
-        return (const float *) d;
+    const int rc = encode_call("ebcc_hip_encode_host_frames", ctx, h_frames, n_frames, config, out_streams, out_sizes, [&] {
+        return encode_from_host(ctx, nullptr, 1, ctx->max_frames, h_frames, n_frames, config, out_streams, out_sizes);
     });
-    if (rc) {
-        if (rc == 2) set_error("ebcc_hip_encode_host_frames: NaN or Inf in the data");
-        for (size_t f = 0; f < n_frames; f++) { free(out_streams[f]); out_streams[f] = nullptr; out_sizes[f] = 0; }
-    }
+    if (rc == 2) set_error("ebcc_hip_encode_host_frames: NaN or Inf in the data");
     return rc;
-    EBCC_API_CATCH(1)
 }
 int ebcc_hip_decode_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_frames_out)
 {
-    EBCC_API_TRY
     if (!ctx || !streams || !sizes || !h_frames_out || n_frames < 1) { set_error("ebcc_hip_decode_host_frames: bad arguments"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    const size_t n_pix = ctx->n_pix, cap = ctx->max_frames;
-    Prefault prefault(h_frames_out, n_frames * n_pix * sizeof(float));
-    return decode_batches_alternating(ctx, n_frames, cap, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-        float *d = io_buffer(set, cap * n_pix * sizeof(float));
-        const int r = run_decode_slices(set, streams + lo, sizes + lo, k, d);
-        if (r) return r;
-        prefault.join();
-        copy_pageable(set, h_frames_out + lo * n_pix, d, k * n_pix * sizeof(float), true);
-        return 0;
+    return on_codec(ctx->device, 1, [&] {
+        Prefault prefault(h_frames_out, n_frames * ctx->n_pix * sizeof(float));
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_frames_out, &prefault);
     });
-    EBCC_API_CATCH(1)
 }
 
 // The engines the reference-compatible entry points keep between calls (one per device and frame geometry, with their slice
@@ -720,11 +773,8 @@ void ebcc_hip_release_engines(void)
         for (auto &kv : g_ctx) victims.emplace_back(std::get<0>(kv.first), kv.second);
         g_ctx.clear();
     }
-    for (auto &v : victims) {
-        std::lock_guard<std::mutex> lock(device_mutex(v.first));       // (a call that is using the engine finishes first)
-        DeviceScope scope(v.first);
-        ebcc_hip_destroy(v.second);
-    }
+    for (auto &v : victims)                                               // (a call that is using the engine finishes first)
+        on_device(v.first, 0, [&] { ebcc_hip_destroy(v.second); return 0; });
     EBCC_API_CATCH_VOID
 }
 
@@ -732,45 +782,38 @@ void ebcc_hip_release_engines(void)
 // device memory as the context itself) is destroyed; the next such call makes it again.
 void ebcc_hip_release_second_set(ebcc_hip_ctx *ctx)
 {
-    EBCC_API_TRY
     if (!ctx) return;
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    if (ctx->twin) { ebcc_hip_destroy(ctx->twin); ctx->twin = nullptr; }
-    ctx->twin_failed = false;
-    EBCC_API_CATCH_VOID
+    on_device(ctx->device, 0, [&] {
+        if (ctx->twin) { ebcc_hip_destroy(ctx->twin); ctx->twin = nullptr; }
+        ctx->twin_failed = false;
+        return 0;
+    });
 }
 
 int ebcc_hip_prepare(ebcc_hip_ctx *ctx, size_t n_frames)
 {
-    EBCC_API_TRY
     if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_prepare: bad batch"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    slice_engines(ctx, n_frames, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);                     // (the coarser slicing first:
-    slice_engines(ctx, n_frames, "EBCC_HIP_SLICES", default_encode_slices());                        //  its lanes serve both)
-    second_stream(ctx);
-    for (ebcc_hip_ctx *c : ctx->lanes) second_stream(c);
-    return 0;
-    EBCC_API_CATCH(1)
+    return on_device(ctx->device, 1, [&] {
+        slice_engines(ctx, n_frames, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);                     // (the coarser slicing first:
+        slice_engines(ctx, n_frames, "EBCC_HIP_SLICES", default_encode_slices());                        //  its lanes serve both)
+        second_stream(ctx);
+        for (ebcc_hip_ctx *c : ctx->lanes) second_stream(c);
+        return 0;
+    });
 }
 
+// One batch: the shard entry points below with at most the context's capacity of frames.
 int ebcc_hip_encode_frames(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *config,
                            uint8_t **out_streams, size_t *out_sizes)
 {
-    EBCC_API_TRY
     if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_encode_frames: bad batch"); return 1; }
-    if (config->dims[0] != 1 || (int) config->dims[1] != ctx->height || (int) config->dims[2] != ctx->width) {
-        set_error("ebcc_hip_encode_frames: config dims must be (1, %d, %d)", ctx->height, ctx->width);
-        return 1;
-    }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    log_set_level_from_env();
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    for (size_t f = 0; f < n_frames; f++) { out_streams[f] = nullptr; out_sizes[f] = 0; }   // on error: free the non-null ones
-    return run_encode_slices(ctx, d_frames, n_frames, config, out_streams, out_sizes);
-    EBCC_API_CATCH(1)
+    return encode_resident("ebcc_hip_encode_frames", ctx, d_frames, n_frames, config, out_streams, out_sizes);
+}
+int ebcc_hip_decode_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                           float *d_frames_out)
+{
+    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames: bad batch"); return 1; }
+    return decode_resident("ebcc_hip_decode_frames", ctx, streams, sizes, n_frames, d_frames_out);
 }
 
 // Any number of frames resident on the device, coded in batches of the context's capacity on two alternating engine sets
@@ -779,36 +822,7 @@ int ebcc_hip_encode_frames(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_fr
 int ebcc_hip_encode_shard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *config,
                           uint8_t **out_streams, size_t *out_sizes)
 {
-    EBCC_API_TRY
-    if (!ctx || !d_frames || !config || !out_streams || !out_sizes || n_frames < 1) { set_error("ebcc_hip_encode_shard: bad arguments"); return 1; }
-    if (config->dims[0] != 1 || (int) config->dims[1] != ctx->height || (int) config->dims[2] != ctx->width) {
-        set_error("ebcc_hip_encode_shard: config dims must be (1, %d, %d)", ctx->height, ctx->width);
-        return 1;
-    }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    log_set_level_from_env();
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    for (size_t f = 0; f < n_frames; f++) { out_streams[f] = nullptr; out_sizes[f] = 0; }
-    const size_t n_pix = ctx->n_pix;
-    const int rc = encode_batches_alternating(ctx, n_frames, config, out_streams, out_sizes,
-                                              [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * n_pix; });
-    if (rc)
-        for (size_t f = 0; f < n_frames; f++) { free(out_streams[f]); out_streams[f] = nullptr; out_sizes[f] = 0; }
-    return rc;
-    EBCC_API_CATCH(1)
-}
-
-int ebcc_hip_decode_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
-                           float *d_frames_out)
-{
-    EBCC_API_TRY
-    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames: bad batch"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    return run_decode_slices(ctx, streams, sizes, n_frames, d_frames_out);
-    EBCC_API_CATCH(1)
+    return encode_resident("ebcc_hip_encode_shard", ctx, d_frames, n_frames, config, out_streams, out_sizes);
 }
 
 // Any number of streams decoded to consecutive frames on the device, in batches of the context's capacity on the two
@@ -816,16 +830,7 @@ int ebcc_hip_decode_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, con
 int ebcc_hip_decode_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                           float *d_frames_out)
 {
-    EBCC_API_TRY
-    if (!ctx || !streams || !sizes || !d_frames_out || n_frames < 1) { set_error("ebcc_hip_decode_shard: bad arguments"); return 1; }
-    std::lock_guard<std::mutex> lock(device_mutex(ctx->device));
-    DeviceScope scope(ctx->device);
-    if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-    const size_t n_pix = ctx->n_pix;
-    return decode_batches_alternating(ctx, n_frames, ctx->max_frames, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-        return run_decode_slices(set, streams + lo, sizes + lo, k, d_frames_out + lo * n_pix);
-    });
-    EBCC_API_CATCH(1)
+    return decode_resident("ebcc_hip_decode_shard", ctx, streams, sizes, n_frames, d_frames_out);
 }
 
 size_t ebcc_encode(float *data, codec_config_t *config, uint8_t **out_buffer)
@@ -846,7 +851,7 @@ size_t ebcc_encode(float *data, codec_config_t *config, uint8_t **out_buffer)
     }
     size_t size = 0;
     uint8_t *o = nullptr;
-    const int rcode = encode_host_frames(resolve_device(), data, 1, (int) config->dims[1], (int) config->dims[2], config, &o, &size, config->dims[0]);
+    const int rcode = encode_on_device(resolve_device(), data, 1, (int) config->dims[1], (int) config->dims[2], config, &o, &size, config->dims[0]);
     if (rcode == 2) exit(1);                                                                   // check_nan_inf, :598-605
     if (rcode) { free(o); return 0; }
     *out_buffer = o;
@@ -878,11 +883,10 @@ size_t ebcc_decode(uint8_t *data, size_t data_size, float **out_buffer)
         return 0;
     }
     const int device = resolve_device();
-    try {
-        std::lock_guard<std::mutex> lock(device_mutex(device));
-        DeviceScope scope(device);
+    // (no libzstd needed here for a stream without a residual layer: decode_batch asks for it when there is one)
+    return on_device(device, (size_t) 0, [&]() -> size_t {
         ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
-        if (!chunk_engines(device, th, W, 1, tiles, &ctx, &rc)) { log_fatal("no MI355X engine available: %s", ebcc_hip_last_error()); return 0; }
+        if (!chunk_engines(device, th, W, 1, tiles, &ctx, &rc)) return 0;
         const size_t n_pix = (size_t) H * W;
         PhaseTimer pt;
         float *d = io_buffer(ctx, n_pix * sizeof(float));
@@ -897,11 +901,7 @@ size_t ebcc_decode(uint8_t *data, size_t data_size, float **out_buffer)
         pt.mark("ebcc_decode: download");
         *out_buffer = o;
         return n_pix;
-    } catch (const std::exception &e) {
-        log_fatal("MI355X engine failure: %s", e.what());
-        set_error("%s", e.what());
-        return 0;
-    }
+    });
 }
 
 // ---- EBCK chunk container (:920-1052) -------------------------------------------------------------
@@ -952,7 +952,7 @@ size_t ebcc_encode_chunking(float *data, codec_config_t *config, uint8_t **out_b
     std::vector<uint8_t *> outs(nchunks, nullptr);
     std::vector<size_t> sizes(nchunks, 0);
     const int rcode = run_on_devices(nchunks, [&](int device, size_t first, size_t count) {
-        return encode_host_frames(device, chunk_data + first * csize, count, (int) cd[1], (int) cd[2], &cc, outs.data() + first, sizes.data() + first, cd[0]);
+        return encode_on_device(device, chunk_data + first * csize, count, (int) cd[1], (int) cd[2], &cc, outs.data() + first, sizes.data() + first, cd[0]);
     });
     if (rcode == 2) exit(1);                                                                   // check_nan_inf, :598-605
     if (rcode) {
@@ -1049,46 +1049,16 @@ size_t ebcc_decode_chunking(uint8_t *data, size_t data_size, float **out_buffer)
     std::vector<float> chunks;
     if (!in_place) chunks.resize(nchunks * csize);
     float *h_chunks = in_place ? o : chunks.data();
-    // a fresh allocation of this size is unmapped pages: the download would fault them in one by one on the copying thread.
-    // A few host threads touch them while the GPU decodes (the reference-compatible output must be a malloc'd buffer).
+    // (the reference-compatible output must be a malloc'd buffer: its pages are mapped while the GPU decodes)
     Prefault prefault(in_place ? (void *) o : nullptr, in_place ? total * sizeof(float) : 0);
     const size_t tiles = cd[0];
     const int rcode = run_on_devices(nchunks, [&](int device, size_t first, size_t count) {
-        try {
-            std::lock_guard<std::mutex> lock(device_mutex(device));
-            DeviceScope scope(device);
+        return on_codec(device, 1, [&] {
             const size_t cap = std::min(count, batch_capacity(csize));
             ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
-            if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) { log_fatal("no MI355X engine available: %s", ebcc_hip_last_error()); return 1; }
-            if (!zstd().ok) { log_fatal("libzstd not available"); return 1; }
-            // (one download per batch: copies issued from inside the slices slowed them down)
-            auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-                PhaseTimer pt;
-                float *d = io_buffer(set, cap * csize * sizeof(float));
-                pt.mark("decode_chunking: engine, device image");
-                const size_t done = first + lo;
-                const int r = tiles > 1 ? decode_tiled(set, rc, ptrs.data() + done, lens.data() + done, k, tiles, d)
-                                        : run_decode_slices(set, ptrs.data() + done, lens.data() + done, k, d);
-                if (r) return r;
-                pt.mark("decode_chunking: decode");
-                prefault.join();
-                pt.mark("decode_chunking: output pages");
-                copy_pageable(set, h_chunks + done * csize, d, k * csize * sizeof(float), true);
-                pt.mark("decode_chunking: download");
-                return 0;
-            };
-            // one-frame chunks in several batches: on two alternating engine sets, a batch's download beside the next one's kernels
-            if (tiles == 1 && ctx->max_frames == cap) return decode_batches_alternating(ctx, count, cap, one_batch);
-            for (size_t lo = 0; lo < count; lo += cap) {
-                const int r = one_batch(ctx, lo, std::min(cap, count - lo));
-                if (r) return r;
-            }
-            return 0;
-        } catch (const std::exception &e) {
-            log_fatal("MI355X engine failure: %s", e.what());
-            set_error("%s", e.what());
-            return 1;
-        }
+            if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) return 1;
+            return decode_to_host(ctx, rc, tiles, cap, ptrs.data() + first, lens.data() + first, count, h_chunks + first * csize, &prefault);
+        });
     });
     if (rcode) { prefault.join(); free(o); return 0; }         // (the page-touching threads write into `o` until they are joined)
     if (!in_place)

@@ -90,8 +90,8 @@ int ebcc_hip_j2k_parse_check(const uint8_t *cs, size_t n, size_t height, size_t 
  * Batch forms of ebcc_encode / ebcc_decode (src/ebcc_codec.h:41-42) for frames resident in HBM.
  * config->dims must be {1, height, width} of the context (one frame per stream, as HDF5 chunks of
  * one frame / ebcc_encode_chunking with chunk_dims {1,H,W} produce).  Streams are malloc'd (free_buffer).
- * Return 0 = ok, 1 = error, 2 = NaN/Inf in the input; on failure entries of out_streams that are not NULL
- * still have to be freed.  A batch is coded as EBCC_HIP_SLICES concurrent slices (default: ebcc_hip_default_encode_slices() = 3 from 96 frames on, one slice below),
+ * Return 0 = ok, 1 = error, 2 = NaN/Inf in the input; on failure every stream made so far has been freed
+ * (out_streams all NULL).  A batch is coded as EBCC_HIP_SLICES concurrent slices (default: ebcc_hip_default_encode_slices() = 3 from 96 frames on, one slice below),
  * each on its own engine, stream and host thread; results do not depend on the slicing.  The slice engines are created on first use; ebcc_hip_prepare creates them ahead of time for batches of
  * n_frames (part of setting a context up, like ebcc_hip_create).  Returns 0. */
 int ebcc_hip_prepare(ebcc_hip_ctx *ctx, size_t n_frames);

@@ -696,13 +696,31 @@ for attempt in range(3):
     except AssertionError:                                   # (the frames' own device buffer was the allocation that failed)
         got = None
     print("RETURNED", "-" if got is None else hashlib.sha256(b"".join(got)).hexdigest(), flush=True)
+lib.ebcc_hip_encode_host_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(L.CodecConfig), L.c_void_pp, L.c_size_p]
+lib.ebcc_hip_decode_host_frames.argtypes = [ctypes.c_void_p, L.c_void_pp, L.c_size_p, ctypes.c_size_t, ctypes.c_void_p]
+for attempt in range(3):                                     # the same frames from host memory, and back to host memory
+    outs = (ctypes.c_void_p * m)()
+    sizes = (ctypes.c_size_t * m)()
+    got = "-"
+    if lib.ebcc_hip_encode_host_frames(ctx.ptr, frames.ctypes.data, m, ctypes.byref(cfg), outs, sizes) == 0:
+        streams = [ctypes.string_at(outs[f], sizes[f]) for f in range(m)]
+        back = np.empty_like(frames)
+        if lib.ebcc_hip_decode_host_frames(ctx.ptr, outs, sizes, m, back.ctypes.data) == 0:
+            got = hashlib.sha256(b"".join(streams)).hexdigest() + " " + hashlib.sha256(back.tobytes()).hexdigest()
+        for f in range(m):
+            lib.free_buffer(outs[f])
+    else:
+        assert not any(outs[f] for f in range(m))              # (freed by the library)
+    print("HOST", got, flush=True)
 ctx.close()
 """
 
 
 def test_shard_entry_point_survives_failed_allocations():
     """EBCC_HIP_FAIL_ALLOC in a child: when the second engine set (or a slice engine of either set) cannot be made the shard
-    runs on what there is, or the call fails cleanly; the process always recovers and gives the same streams."""
+    runs on what there is, or the call fails cleanly; the process always recovers and gives the same streams.  The same
+    holds for the same frames from host memory (ebcc_hip_encode_host_frames, then ebcc_hip_decode_host_frames): the
+    allocations of their device images fail there too, among them the second set's, whose batches go back to the first."""
     import os
     import subprocess
     import sys
@@ -710,13 +728,19 @@ def test_shard_entry_point_survives_failed_allocations():
     ok = subprocess.run([sys.executable, "-c", _SHARD.format(root=L.ROOT)], capture_output=True, text=True, env=base, timeout=600)
     want = [l for l in ok.stdout.splitlines() if l.startswith("RETURNED")]
     assert ok.returncode == 0 and len(want) == 3 and len(set(want)) == 1 and want[0] != "RETURNED -", (ok.stdout, ok.stderr[-400:])
-    for nth in (2, 40, 70, 100, 130, 160, 190):
+    host = [l for l in ok.stdout.splitlines() if l.startswith("HOST")]
+    assert len(host) == 3 and len(set(host)) == 1 and host[0].split()[1] == want[0].split()[1], (ok.stdout, ok.stderr[-400:])
+    # (143 and 144: the device images of the first host-array encode on the two sets, the child's last allocations)
+    for nth in (2, 40, 70, 100, 130, 143, 144, 160, 190):
         r = subprocess.run([sys.executable, "-c", _SHARD.format(root=L.ROOT)], capture_output=True, text=True, env=dict(base, EBCC_HIP_FAIL_ALLOC=str(nth)),
                            timeout=600)
         got = [l for l in r.stdout.splitlines() if l.startswith("RETURNED")]
         assert r.returncode == 0 and len(got) == 3, (nth, r.returncode, r.stdout, r.stderr[-600:])
         assert got[2] == want[0], (nth, got)
         assert all(g == want[0] or g == "RETURNED -" for g in got), (nth, got)
+        got = [l for l in r.stdout.splitlines() if l.startswith("HOST")]
+        assert len(got) == 3 and got[2] == host[0], (nth, got)
+        assert all(g == host[0] or g == "HOST -" for g in got), (nth, got)
 
 
 _BIG = r"""
