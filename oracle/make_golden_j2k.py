@@ -3,11 +3,18 @@
 oracle's optional backend (oracle/opj_backend.c: the reference's own call sequence, /root/reference/src/ebcc_codec.c:105-180
 encode and :1092-1136 decode, on a u16 image).  TEST INFRASTRUCTURE; run in the dev container only:
 
-    python3 oracle/make_golden_j2k.py        ->  tests/golden/j2k_openjpeg.json, tests/golden/j2k_inputs.npz
+    python3 oracle/make_golden_j2k.py          ->  tests/golden/j2k_openjpeg.json, tests/golden/j2k_inputs.npz
+    python3 oracle/make_golden_j2k.py fields   ->  tests/golden/j2k_fields.json
 
 tests/test_oracle_golden.py::test_j2k_restatement_against_openjpeg_fixtures pins oracle/j2k_oracle.c on them on any box
 (the live comparison with the library only runs where the library is).  Inputs are integer formulas (reproducible
-anywhere) or stored arrays; small codestreams are stored whole, large ones as sha256."""
+anywhere) or stored arrays; small codestreams are stored whole, large ones as sha256.
+
+`fields` covers the frame sizes real callers hit (1024 x 1024 chunks, the largest legal 2047 x 2047, the thinnest) with
+the high-entropy content of tests/_fields.py at the whole rate ladder of tests/test_j2k_gpu.py, as hashes only: the
+input frame, the codestream, the decoded samples and the samples mapped back to float32 (ebcc_codec.c:1130).  The GPU
+tests compare the product with these directly; the CPU test pins the oracle on the cases marked "pin" (every rate at
+the small shapes, a trimmed ladder at the two biggest)."""
 import ctypes
 import hashlib
 import json
@@ -71,5 +78,41 @@ def main():
     print(len(cases), "cases,", sum(len(c.get("stream_hex", "")) // 2 for c in cases), "stream bytes stored")
 
 
+FIELD_SHAPES = [(257, 383), (1024, 1024), (2047, 2047), (2047, 33), (32, 2047)]
+FIELD_RATES = [1.0, 3.0, 7.5, 30.0, 120.0, 1000.0]                 # tests/test_j2k_gpu.py RATES
+PIN_RATES = {(1024, 1024): (1.0, 30.0), (2047, 2047): (1.0, 1000.0)}
+
+
+def _field_case(job):
+    kind, h, w, cr = job
+    from tests import _fields as F
+    lib = L.oracle()
+    x = F.field(kind, h, w)
+    u16, mn, mx = L.scale_u16(x)
+    out = ctypes.c_void_p()
+    n = lib.orc_opj_encode(u16.ctypes.data, h, w, ctypes.c_float(cr), ctypes.byref(out))
+    s = ctypes.string_at(out.value, n)
+    lib.orc_free(out)
+    b = ctypes.create_string_buffer(s, len(s))
+    out, dh, dw = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_size_t()
+    m = lib.orc_opj_decode(b, len(s), ctypes.byref(out), ctypes.byref(dh), ctypes.byref(dw))
+    samples = np.frombuffer(ctypes.string_at(out.value, 4 * m), np.int32).reshape(h, w).copy()
+    lib.orc_free(out)
+    return {"kind": kind, "h": h, "w": w, "cr": cr, "pin": cr in PIN_RATES.get((h, w), FIELD_RATES),
+            "field_sha256": F.sha(x.tobytes()), "n": len(s), "stream_sha256": F.sha(s),
+            "decoded_sha256": F.sha(samples.tobytes()), "mapped_sha256": F.sha(L.map_decoded(samples, mn, mx).tobytes())}
+
+
+def fields():
+    import multiprocessing as mp
+    from tests import _fields as F
+    assert hasattr(L.oracle(), "orc_opj_encode") and L.opj_version().startswith("2.4.0"), "needs the OpenJPEG 2.4.0 backend"
+    jobs = [(k, h, w, cr) for h, w in FIELD_SHAPES for k in F.KINDS for cr in FIELD_RATES]
+    with mp.get_context("spawn").Pool(min(8, os.cpu_count() or 1)) as pool:
+        cases = pool.map(_field_case, jobs, chunksize=1)
+    json.dump({"openjpeg": L.opj_version(), "cases": cases}, open(os.path.join(OUT, "j2k_fields.json"), "w"), indent=0)
+    print(len(cases), "cases,", sum(c["pin"] for c in cases), "pinned on the oracle")
+
+
 if __name__ == "__main__":
-    main()
+    fields() if sys.argv[1:] == ["fields"] else main()

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _fields as F
 from tests import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -316,7 +317,8 @@ def test_legacy_headerless_streams_decode(name):
 
 def test_extreme_frame_sizes():
     """Smallest and most ragged legal frames bit-exact against the oracle; the largest legal frame (2047 x 2047,
-    EBCC_MAX_INTERNAL_IMAGE_DIM) through the size-independent property: decode(encode(x)) within the bound."""
+    EBCC_MAX_INTERNAL_IMAGE_DIM) bit-exact against the reference build's stream and decoded field
+    (tests/golden/large_frames.json), and decode(encode(x)) within the bound."""
     L.oracle().orc_set_j2k_backend(0)
     for h, w, seed in ((32, 32, 1), (33, 2047, 2), (2047, 32, 3), (65, 127, 4)):
         data = L.era5_like(h, w, seed, 1.2, 1.0)
@@ -324,11 +326,16 @@ def test_extreme_frame_sizes():
         s = api_encode(data, cfg)
         assert s == L.orc_encode(data, cfg), (h, w)
         assert np.abs(api_decode(s).reshape(h, w) - data).max() <= 0.05 * 1.01 + 1e-4
-    big = L.era5_like(2047, 2047, 11, 1.5, 2.5)
-    for mode, err in ((L.MAX_ERROR, 0.25), (L.RELATIVE_ERROR, 2e-3)):
+    big = F.extreme_frame()
+    large = json.load(open(os.path.join(L.GOLDEN, "large_frames.json")))["cases"]
+    for mode, err in F.EXTREME_MODES:
+        want = large[F.large_key("extreme", None, mode)]
+        assert sha(big.tobytes()) == want["field_sha256"], "input differs"
         cfg = L.make_config((1, 2047, 2047), base_cr=40.0, error=err, residual_type=mode)
         s = api_encode(big, cfg)
+        assert len(s) == want["n"] and sha(s) == want["stream_sha256"], mode       # the reference build's stream
         dec = api_decode(s).reshape(2047, 2047)
+        assert sha(dec.tobytes()) == want["decoded_sha256"], mode
         tgt = err if mode == L.MAX_ERROR else err * float(big.max() - big.min())
         assert np.abs(dec - big).max() <= tgt * 1.01 + 1e-4
         assert len(s) < big.nbytes / 8

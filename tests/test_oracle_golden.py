@@ -181,9 +181,16 @@ def test_j2k_restatement_matches_openjpeg_live():
 
 _j2k = json.load(open(os.path.join(L.GOLDEN, "j2k_openjpeg.json")))
 _j2k_inputs = np.load(os.path.join(L.GOLDEN, "j2k_inputs.npz"))
+# the high-entropy fields at the large and thin shapes (oracle/make_golden_j2k.py fields): the cases marked "pin"
+_j2k_cases = _j2k["cases"] + [c for c in load("j2k_fields.json")["cases"] if c["pin"]]
 
 
 def _j2k_input(c):
+    if "kind" in c:
+        from tests import _fields as F
+        x = F.field(c["kind"], c["h"], c["w"])
+        assert sha(x.tobytes()) == c["field_sha256"], "input differs"
+        return L.scale_u16(x)[0]
     if c["input"] == "stored":
         return np.ascontiguousarray(_j2k_inputs[c["spec"]])
     h, w, k = c["spec"]
@@ -192,18 +199,25 @@ def _j2k_input(c):
     return np.ascontiguousarray((v % 65536).astype(np.uint16))
 
 
-@pytest.mark.parametrize("i", range(len(_j2k["cases"])), ids=lambda i: "{h}x{w}-cr{cr}".format(**_j2k["cases"][i]))
+@pytest.mark.parametrize("i", range(len(_j2k_cases)),
+                         ids=lambda i: ("{h}x{w}-{kind}-cr{cr}" if "kind" in _j2k_cases[i] else "{h}x{w}-cr{cr}").format(**_j2k_cases[i]))
 def test_j2k_restatement_against_openjpeg_fixtures(i):
     """oracle/j2k_oracle.c (the restated JPEG 2000 base layer) against codestreams and decoded samples produced by the real
     OpenJPEG 2.4.0 through the reference's call sequence (oracle/make_golden_j2k.py; /root/reference/src/ebcc_codec.c:105-180,
-    :1092-1136): byte-identical codestream, identical decoded samples - on any box, with or without the library."""
-    c = _j2k["cases"][i]
+    :1092-1136): byte-identical codestream, identical decoded samples - on any box, with or without the library.  The
+    field cases also pin the samples mapped back to float32, which the GPU tests compare with."""
+    c = _j2k_cases[i]
     img = _j2k_input(c)
     s = L.orc_j2k_encode(img, c["cr"])
     assert len(s) == c["n"] and sha(s) == c["stream_sha256"]
     if "stream_hex" in c:
         assert s == bytes.fromhex(c["stream_hex"])
-    assert sha(L.orc_j2k_decode(s).tobytes()) == c["decoded_sha256"]
+    samples = L.orc_j2k_decode(s)
+    assert sha(samples.tobytes()) == c["decoded_sha256"]
+    if "mapped_sha256" in c:
+        from tests import _fields as F
+        _, mn, mx = L.scale_u16(F.field(c["kind"], c["h"], c["w"]))
+        assert sha(L.map_decoded(samples, mn, mx).tobytes()) == c["mapped_sha256"]
 
 
 def test_j2k_nmsedec_tables_match_openjpeg_binary_dump():
@@ -301,3 +315,67 @@ def test_search_branch_streams():
     finally:
         if old is not None:
             os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"] = old
+
+
+_large = load("large_frames.json")
+# the oracle's restated search takes tens of seconds per full-size frame of noise: it is pinned on the frames it codes in
+# a few seconds (the reference build on the same ones, where it is present); the GPU module compares every case
+_LARGE_SAMPLE = [("batch_1024", ("spike", 0)), ("batch_1024", ("checker", 0)), ("batch_1024", ("lowbit", 0)),
+                 ("batch_2047", ("spike", 2))]
+
+
+def test_large_frame_inputs():
+    """Every input of tests/golden/large_frames.json is the frame the generators make here."""
+    from tests import _fields as F
+    for batch, ((h, w), specs) in F.LARGE_BATCHES.items():
+        for spec in specs:
+            x = F.large_frame(spec[0], h, w, spec[1])
+            for mode, _ in F.LARGE_MODES:
+                assert sha(x.tobytes()) == _large["cases"][F.large_key(batch, spec, mode)]["field_sha256"], (batch, spec)
+    for mode, _ in F.EXTREME_MODES:
+        assert sha(F.extreme_frame().tobytes()) == _large["cases"][F.large_key("extreme", None, mode)]["field_sha256"]
+    for mode, _ in F.LARGE_MODES:
+        assert sha(F.compat_array().tobytes()) == _large["cases"][F.large_key("compat", None, mode)]["field_sha256"]
+
+
+@pytest.mark.parametrize("mode,err", [(L.MAX_ERROR, 0.05), (L.RELATIVE_ERROR, 1e-3)], ids=["abs", "rel"])
+@pytest.mark.parametrize("batch,spec", _LARGE_SAMPLE, ids=lambda v: v if isinstance(v, str) else "{}{}".format(*v))
+def test_large_frame_streams(batch, spec, mode, err, monkeypatch):
+    """oracle == the reference build's stream and decoded field at 1024 x 1024 and 2047 x 2047 (as stored, and the
+    build itself where it is present)."""
+    from tests import _fields as F
+    monkeypatch.delenv("EBCC_INIT_BASE_ERROR_QUANTILE", raising=False)
+    assert (mode, err) in F.LARGE_MODES
+    (h, w), _ = F.LARGE_BATCHES[batch]
+    c = _large["cases"][F.large_key(batch, spec, mode)]
+    x = F.large_frame(spec[0], h, w, spec[1])
+    cfg = L.make_config((1, h, w), base_cr=_large["base_cr"], error=err, residual_type=mode)
+    L.oracle().orc_set_j2k_backend(0)
+    s = L.orc_encode(x, cfg)
+    assert len(s) == c["n"] and sha(s) == c["stream_sha256"]
+    assert sha(L.orc_decode(s).tobytes()) == c["decoded_sha256"]
+    if L.reference() is not None:
+        assert L.ref_encode(x, cfg) == s
+
+
+@pytest.mark.parametrize("i", range(len(_large["spiht"])),
+                         ids=lambda i: "{h}x{w}-{kind}-tb{trunc_bits}".format(**_large["spiht"][i]))
+def test_spiht_large_fields(i):
+    """The residual coder at 1024 x 1024, 2047 x 2047 and 2047 x 33 on noise, spike and checkerboard images, untruncated
+    and truncated: oracle == the reference build (as stored, and the build itself where it is present)."""
+    from tests import _fields as F
+    c = _large["spiht"][i]
+    h, w = c["h"], c["w"]
+    x = F.field(c["kind"], h, w, c["seed"])
+    assert sha(x.tobytes()) == c["field_sha256"], "input differs"
+    s = L.orc_spiht_encode(x, c["trunc_bits"])
+    assert len(s) == c["n"] and sha(s) == c["stream_sha256"]
+    assert c["trunc_bits"] or len(s) <= h * w * 4                    # the reference's buffer when untruncated
+    assert sha(L.orc_spiht_decode(s, h, w).tobytes()) == c["decoded_sha256"]
+    if os.path.exists(L.REF_SPIHT_SO):
+        sp = ctypes.CDLL(L.REF_SPIHT_SO)
+        sp.spiht_encode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, L.c_void_pp, L.c_size_p,
+                                    ctypes.c_size_t, ctypes.c_size_t]
+        buf, n = ctypes.c_void_p(), ctypes.c_size_t()
+        sp.spiht_encode(x.ctypes.data, h, w, ctypes.byref(buf), ctypes.byref(n), c["trunc_bits"], 3)
+        assert ctypes.string_at(buf.value, n.value) == s

@@ -1,18 +1,26 @@
-"""GPU parity of the residual layer (pad + DC + CDF 9/7 + SPIHT) against the CPU oracle: bit-exact."""
+"""GPU parity of the residual layer (pad + DC + CDF 9/7 + SPIHT) against the CPU oracle: bit-exact.
+
+Up to the largest legal frame, with full-range noise, a single spike and a checkerboard beside the smooth images.  At
+trunc_bits 0 the stream is bounded by the reference's buffer of h*w*4 bytes (src/spiht/spiht_re.c:433); the noise
+frame at 2047 x 2047 comes closest to it.  The oracle is pinned to the reference build at these shapes by
+tests/test_oracle_golden.py::test_spiht_large_fields."""
 import numpy as np
 import pytest
 
+from tests import _fields as F
 from tests import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(32, 32), (33, 47), (64, 64), (100, 130), (181, 360), (37, 2047), (721, 1440)]
+SHAPES = [(32, 32), (33, 47), (64, 64), (100, 130), (181, 360), (37, 2047), (721, 1440), (1024, 1024), (2047, 2047),
+          (2047, 33)]
 
 
 def _images(h, w):
     r = np.random.default_rng(h * 10007 + w)
     return np.stack([L.kat_image(h, w), r.random((h, w), dtype=np.float32), L.smooth_image(h, w, 3),
-                     np.full((h, w), 0.25, np.float32)])
+                     np.full((h, w), 0.25, np.float32), F.field("noise", h, w, 7), F.field("spike", h, w),
+                     F.field("checker", h, w)])
 
 
 @pytest.mark.parametrize("shape", SHAPES)
