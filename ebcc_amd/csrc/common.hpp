@@ -43,6 +43,10 @@ void set_error(const char *fmt, ...);
 void clear_error();                 // this thread's last-error text
 // hipMalloc through one door: EBCC_HIP_FAIL_ALLOC=<n> (tests) makes the n-th allocation of the process fail
 hipError_t device_malloc(void **p, size_t bytes);
+// EBCC_HIP_POISON_ALLOC=<byte> (tests): the float / double workspace (ctx_alloc) and the byte buffers that end up in
+// streams are filled with that byte before they are handed out, so a kernel that reads what it did not write in the call
+// gives wrong numbers instead of the zeros of a fresh allocation.  Unset: nothing happens.
+void poison_alloc(void *p, size_t bytes);
 
 // Host wait for a stream.  By default through an event created with hipEventBlockingSync: the waiting thread sleeps
 // instead of spinning (hipStreamSynchronize spins on a core for as long as the GPU works - two slice threads waiting are

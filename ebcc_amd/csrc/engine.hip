@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <cstring>
 #include <vector>
 
@@ -62,6 +63,15 @@ hipError_t device_malloc(void **p, size_t bytes)
     return e;
 }
 
+void poison_alloc(void *p, size_t bytes)
+{
+    static const int byte = getenv("EBCC_HIP_POISON_ALLOC") ? (int) (strtol(getenv("EBCC_HIP_POISON_ALLOC"), nullptr, 0) & 0xFF) : -1;
+    if (byte < 0 || !p) return;
+    // (the null stream, then a wait for it: the fill is complete before any engine stream can touch the buffer)
+    EBCC_HIP_CHECK(hipMemsetAsync(p, byte, bytes, nullptr));
+    EBCC_HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+
 template <typename T>
 T *ctx_alloc(ebcc_hip_ctx *ctx, size_t count)
 {
@@ -73,6 +83,9 @@ T *ctx_alloc(ebcc_hip_ctx *ctx, size_t count)
         set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
         return nullptr;
     }
+    // integer and struct buffers (offsets, lengths, tables, checkpoints) are never poisoned: a wrong read of an index
+    // there would become a wild address rather than a wrong number
+    if (std::is_same<T, float>::value || std::is_same<T, double>::value) poison_alloc(p, bytes);
     ctx->allocs.push_back(p);
     ctx->bytes += bytes;
     return static_cast<T *>(p);
@@ -123,6 +136,7 @@ size_t stage_layout(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t n)
         const hipError_t e = device_malloc((void **) &d_new, cap);
         if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
         ctx->h_stage = h_new; ctx->d_stage = d_new; ctx->stage_cap = cap;
+        poison_alloc(d_new, cap);
     }
     return total;
 }

@@ -126,6 +126,7 @@ float *io_buffer(ebcc_hip_ctx *ctx, size_t bytes)
     hipError_t e = device_malloc(&p, bytes);
     if (e != hipSuccess) { char b[128]; snprintf(b, sizeof b, "device buffer of %zu bytes: %s", bytes, hipGetErrorString(e)); throw HipFailure(b); }
     ctx->d_io = (float *) p; ctx->io_cap = bytes;
+    poison_alloc(p, bytes);
     return ctx->d_io;
 }
 

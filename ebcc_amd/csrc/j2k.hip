@@ -97,6 +97,8 @@ bool j2k_create(ebcc_hip_ctx *ctx)
     ok &= (jb->partial = ctx_alloc<double>(ctx, F * kPartials)) != nullptr;
     ok &= (jb->partial_u = ctx_alloc<unsigned long long>(ctx, F * kPartials)) != nullptr;
     if (!ok) return false;
+    poison_alloc(jb->cblk_bytes, groups * 64 * kJ2kCblkBytes);
+    poison_alloc(jb->stream, F * jb->stream_cap);
     if (stride >= 65535) { set_error("too many code-blocks"); return false; }
     std::vector<uint16_t> map((size_t) period * n_pix, 0);
     std::vector<J2kBlock> blocks((size_t) period * (size_t) stride, J2kBlock{});

@@ -142,11 +142,16 @@ def test_multi_frame_chunks_with_short_frames_are_refused():
     assert lib.ebcc_encode(x.ctypes.data, ctypes.byref(cfg), ctypes.byref(out)) == 0
 
 
+def full_size_formula_frame():
+    """the 721 x 1440 input of tests/golden/codec_big.json"""
+    y, x = np.mgrid[0:721, 0:1440]
+    return (250.0 + ((x * 3 + y * 5) % 1024).astype(np.float32) / np.float32(64.0)
+            + (((x // 16) * 7 + (y // 16) * 13) % 97).astype(np.float32)).astype(np.float32)
+
+
 def test_full_size_formula_frames_bit_exact():
     big = json.load(open(os.path.join(L.GOLDEN, "codec_big.json")))
-    y, x = np.mgrid[0:721, 0:1440]
-    f1 = (250.0 + ((x * 3 + y * 5) % 1024).astype(np.float32) / np.float32(64.0)
-          + (((x // 16) * 7 + (y // 16) * 13) % 97).astype(np.float32)).astype(np.float32)
+    f1 = full_size_formula_frame()
     for key, c in big.items():
         cfg = L.make_config((1, 721, 1440), base_cr=c["base_cr"], error=c["error"], residual_type=c["mode"])
         s = api_encode(f1, cfg)
