@@ -1,7 +1,8 @@
 // batch_codec.hip - one device batch of the frame codec (host.hpp): /root/reference/src/ebcc_codec.c:607-918 as
-// encode_batch, :1215-1320 as decode_batch / decode_tiled, with the rate search (:545-596, twice per frame) and the
-// truncation bisection (:765-796) as device-side state machines (search.hpp).  The host only steers: per-frame scalars
-// come back from the device after every search, every per-sample operation runs in the kernels.
+// encode_batch, :1215-1320 as decode_batch - chunks of one frame or of several (Batch) either way - with the rate search
+// (:545-596, twice per frame) and the truncation bisection (:765-796) as device-side state machines (search.hpp).  The
+// host only steers: per-frame scalars come back from the device after every search, every per-sample operation runs in
+// the kernels.
 #include "host.hpp"
 
 namespace ebcc {
@@ -891,35 +892,42 @@ bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf)
 }
 
 // ------------------------------------------------------------------------------------------------
-// ebcc_decode for a batch of single-frame EBCC streams -> device buffer d_out [n][H*W]
+// ebcc_decode for a batch of chunk streams -> device buffer d_out [n][chunk pixels]
 // ------------------------------------------------------------------------------------------------
+// The chunks of encode_batch: chunk c is the frames c * tiles .. c * tiles + tiles - 1 of `ctx` - for tiles > 1 the
+// tile-parts of one tiled codestream (reference :121-125) - and its residual layer one frame of `rctx` (== ctx for
+// one-frame chunks).
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                 SliceGate *next)
+                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx)
 {
     struct Release { SliceGate *g; ~Release() { if (g) g->release(); } } release_on_exit{next};
+    ebcc_hip_ctx *const rc = rctx ? rctx : ctx;
     J2kBuffers &jb = *static_cast<J2kBuffers *>(ctx->j2k);
     hipStream_t s = ctx->stream;
-    const size_t n_pix = ctx->n_pix;
+    const size_t nt = n * tiles, n_pix = ctx->n_pix * tiles;         // frames of ctx; pixels of a chunk
     const J2kGeom &g = jb.geom;
     int *const table = ctx->h_table;                                  // (pinned)
-    const size_t table_ints = n * (size_t) g.stride * 4;
+    const size_t table_ints = nt * (size_t) g.stride * 4;
     memset(table, 0, table_ints * sizeof(int));
-    // pieces to upload: codestream k = f, SPIHT bytes k = n + f - staged in pinned memory and sent as one copy
-    std::vector<size_t> piece(2 * n, 0), piece_off(2 * n, 0);
+    // pieces to upload: codestream (tiles == 1) or tile-part k of chunk c at c * tiles + k, found at src_off in the
+    // chunk's tail; SPIHT bytes of chunk c at nt + c - staged in pinned memory and sent as one copy
+    std::vector<size_t> piece(nt + n, 0), piece_off(nt + n, 0), src_off(nt, 0);
     std::vector<ParsedFrame> heads(n);
     PhaseTimer pt;
-    fetch_frame_states(ctx, n);
-    // the host side of a batch - frame headers, packet headers, zstd of the residual streams - is per frame and runs on a
-    // few host threads (decode is one slice: nothing else hides it); a frame's failure fails the batch
+    // frame states: the device's for one-frame chunks, zeroed ones for tiles and chunks; the header's fields are set below
+    if (tiles == 1) fetch_frame_states(ctx, n);
+    else { std::fill_n(ctx->h_fs, nt, FrameState{}); std::fill_n(rc->h_fs, n, FrameState{}); }
+    // the host side of a batch - frame headers, packet headers, zstd of the residual streams - is per chunk and runs on a
+    // few host threads (decode is one slice: nothing else hides it); a chunk's failure fails the batch
     std::atomic<bool> failed{false}, resid{false};
-    // (the reason a frame was rejected is written on the worker's thread - set_error's text is per thread; the first one is
+    // (the reason a chunk was rejected is written on the worker's thread - set_error's text is per thread; the first one is
     //  carried over to the calling thread, where ebcc_hip_last_error is read)
-    auto for_frames = [&](auto body) {
+    auto for_chunks = [&](auto body) {
         const unsigned width = (unsigned) std::min<size_t>({(size_t) 16, (size_t) entropy_threads(1), (n + 7) / 8});
-        auto batch = HostPool::instance().submit(n, width, [&](size_t f) {
+        auto batch = HostPool::instance().submit(n, width, [&](size_t c) {
             if (failed.load(std::memory_order_relaxed)) return;
             clear_error();
-            if (!body(f)) {
+            if (!body(c)) {
                 failed = true;
                 const char *why = ebcc_hip_last_error();
                 throw std::runtime_error(why && *why ? why : "invalid encoded data");
@@ -927,58 +935,74 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
         });
         if (!batch->wait()) { failed = true; set_error("%s", batch->error.c_str()); }
     };
-    for_frames([&](size_t f) -> bool {
-        const uint8_t *d = streams[f];
-        const size_t len = sizes[f];
-        ctx->h_active[f] = 0;
-        ParsedFrame &hd = heads[f];
-        if (!parse_frame(d, len, hd)) return false;
-        FrameState &fs = ctx->h_fs[f];
+    for_chunks([&](size_t c) -> bool {
+        rc->h_active[c] = 0;
+        ParsedFrame &hd = heads[c];
+        if (!parse_frame(streams[c], sizes[c], hd)) return false;
+        // the chunk's range on every tile (ctx), and with the residual range on the chunk (rc: the same state for tiles == 1)
+        for (size_t t = c * tiles; t < (c + 1) * tiles; t++) {
+            FrameState &fs = ctx->h_fs[t];
+            fs.minv = hd.minv; fs.maxv = hd.maxv; fs.const_field = hd.const_field ? 1 : 0;
+        }
+        FrameState &fs = rc->h_fs[c];
         fs.minv = hd.minv; fs.maxv = hd.maxv;
         fs.rmin = hd.rmin; fs.rmax = hd.rmax;
         fs.const_field = hd.const_field ? 1 : 0;
         if (fs.const_field) {
             uint64_t cnt = 0;
             memcpy(&cnt, hd.tail, 8);
-            if (cnt != n_pix) { log_fatal("const-field length %llu does not match the frame", (unsigned long long) cnt); return false; }
-        } else {
+            if (cnt != n_pix) { log_fatal("const-field length %llu does not match the %s", (unsigned long long) cnt, tiles > 1 ? "chunk" : "frame"); return false; }
+            return true;
+        }
+        int *const rows = table + c * tiles * g.stride * 4;
+        if (tiles == 1) {
             if (hd.tail_size > jb.stream_cap) { log_fatal("codestream larger than the device slot"); return false; }
-            if (!j2k_parse_codestream(hd.tail, hd.tail_size, g, table + f * g.stride * 4)) return false;
-            piece[f] = hd.tail_size;
-            if (hd.compressed_size > 0 && hd.coeffs_size > 0) {                                                    // :1294-1304
-                if (!zstd().ok) { log_fatal("libzstd not available"); return false; }
-                if (hd.coeffs_size > ctx->rb.stream_words * 4 - 64) { log_fatal("residual stream larger than the device slot"); return false; }
-                piece[n + f] = hd.coeffs_size;
-                ctx->h_active[f] = 1;
-                resid = true;
+            if (!j2k_parse_codestream(hd.tail, hd.tail_size, g, rows)) return false;
+            piece[c] = hd.tail_size;
+        } else {
+            if (!j2k_parse_tiled(hd.tail, hd.tail_size, jb, (int) tiles, rows, &src_off[c * tiles], &piece[c * tiles])) {
+                log_fatal("Invalid encoded data: %s", ebcc_hip_last_error());
+                return false;
             }
+            for (size_t t = c * tiles; t < (c + 1) * tiles; t++)
+                if (piece[t] > jb.stream_cap) { log_fatal("tile-part larger than the device slot"); return false; }
+        }
+        if (hd.compressed_size > 0 && hd.coeffs_size > 0) {                                                    // :1294-1304
+            if (!zstd().ok) { log_fatal("libzstd not available"); return false; }
+            if (hd.coeffs_size > rc->rb.stream_words * 4 - 64) { log_fatal("residual stream larger than the device slot"); return false; }
+            piece[nt + c] = hd.coeffs_size;
+            rc->h_active[c] = 1;
+            resid = true;
         }
         return true;
     });
     if (failed) return 1;
     const bool any_resid = resid;
-    stage_reserve(ctx, piece.data(), piece_off.data(), 2 * n);
-    for_frames([&](size_t f) -> bool {
-        const ParsedFrame &hd = heads[f];
-        if (piece[f]) memcpy(ctx->h_stage + piece_off[f], hd.tail, hd.tail_size);
-        if (piece[n + f]) {
+    stage_reserve(ctx, piece.data(), piece_off.data(), nt + n);
+    for_chunks([&](size_t c) -> bool {
+        const ParsedFrame &hd = heads[c];
+        for (size_t t = c * tiles; t < (c + 1) * tiles; t++)
+            if (piece[t]) memcpy(ctx->h_stage + piece_off[t], hd.tail + src_off[t], piece[t]);
+        if (piece[nt + c]) {
             // the residual stream: exactly coeffs_size bytes (the staging buffer holds whatever an earlier call left),
-            // a SPIHT header for this grid and a bit budget the decoder can work with (:1294-1304)
-            const size_t got = zstd().decompress(ctx->h_stage + piece_off[n + f], hd.coeffs_size, hd.z, hd.compressed_size);
+            // a SPIHT header for the chunk's grid and a bit budget the decoder can work with (:1294-1304)
+            uint8_t *const z = ctx->h_stage + piece_off[nt + c];
+            const size_t got = zstd().decompress(z, hd.coeffs_size, hd.z, hd.compressed_size);
             if ((zstd().is_error && zstd().is_error(got)) || got != hd.coeffs_size) { log_fatal("Invalid encoded data: residual payload does not decompress to %zu bytes", hd.coeffs_size); return false; }
-            if (check_ims_header(ctx, ctx->h_stage + piece_off[n + f], hd.coeffs_size, hd.coeffs_size * 8)) { log_fatal("Invalid encoded data: %s", ebcc_hip_last_error()); return false; }
+            if (check_ims_header(rc, z, hd.coeffs_size, hd.coeffs_size * 8)) { log_fatal("Invalid encoded data: %s", ebcc_hip_last_error()); return false; }
         }
         return true;
     });
     if (failed) return 1;
-    stage_send(ctx, 2 * n, s);
-    stage_scatter(ctx, jb.stream, jb.stream_cap, 0, n, s);
+    stage_send(ctx, nt + n, s);
+    stage_scatter(ctx, jb.stream, jb.stream_cap, 0, nt, s);
     pt.mark("decode: parse, zstd, uploads");
-    push_frame_states(ctx, n);
-    // The residual layer (SPIHT decode + synthesis: one wave per frame, latency-bound) does not depend on the
+    push_frame_states(ctx, nt);
+    // The residual layer (SPIHT decode + synthesis: one wave per chunk, latency-bound) does not depend on the
     // base layer until the final addition, so it runs on the engine's second stream beside the tier-1 decode.
     hipStream_t s2 = s;
     if (any_resid) {
+        if (rc != ctx) push_frame_states(rc, n, s);                   // (on s: ordered before the event like the rest)
         s2 = second_stream(ctx);
         if (!ctx->ev_a) {
             EBCC_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_a, hipEventDisableTiming));
@@ -987,125 +1011,37 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
         EBCC_HIP_CHECK(hipEventRecord(ctx->ev_a, s));                       // frame states and the staged pieces are on the device
         EBCC_HIP_CHECK(hipStreamWaitEvent(s2, ctx->ev_a, 0));
     }
-    // the residual stream is fed first: its one-wave-per-frame kernel has to find a wave slot on every CU, and once the
+    // the residual stream is fed first: its one-wave-per-chunk kernel has to find a wave slot on every CU, and once the
     // tier-1 decoder's ~10^4 workgroups (longest code-blocks first) hold the slots none frees up for milliseconds
     if (any_resid) {
-        const size_t slot = ctx->rb.stream_words * 4;
-        for (size_t f = 0; f < n; f++) {
-            ctx->h_u64a[f] = piece[n + f];
-            ctx->h_u64b[f] = piece[n + f] * 8;
+        const size_t slot = rc->rb.stream_words * 4;
+        for (size_t c = 0; c < n; c++) {
+            rc->h_u64a[c] = piece[nt + c];
+            rc->h_u64b[c] = piece[nt + c] * 8;
         }
-        stage_scatter(ctx, (uint8_t *) ctx->rb.stream, slot, n, n, s2);
-        EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_u64a, ctx->h_u64a, n * sizeof(unsigned long long), hipMemcpyHostToDevice, s2));
-        EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_u64b, ctx->h_u64b, n * sizeof(unsigned long long), hipMemcpyHostToDevice, s2));
-        EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_active, ctx->h_active, n * sizeof(int), hipMemcpyHostToDevice, s2));
-        launch_spiht_decode((const uint8_t *) ctx->rb.stream, slot, ctx->d_u64a, ctx->d_u64b, ctx->rb, (int) n, ctx->d_active, s2);
-        launch_synthesis_head(ctx->rb, (int) n, ctx->d_active, s2);
+        stage_scatter(ctx, (uint8_t *) rc->rb.stream, slot, nt, n, s2);
+        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64a, rc->h_u64a, n * sizeof(unsigned long long), hipMemcpyHostToDevice, s2));
+        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64b, rc->h_u64b, n * sizeof(unsigned long long), hipMemcpyHostToDevice, s2));
+        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_active, rc->h_active, n * sizeof(int), hipMemcpyHostToDevice, s2));
+        launch_spiht_decode((const uint8_t *) rc->rb.stream, slot, rc->d_u64a, rc->d_u64b, rc->rb, (int) n, rc->d_active, s2);
+        launch_synthesis_head(rc->rb, (int) n, rc->d_active, s2);
         if (s2 != s) EBCC_HIP_CHECK(hipEventRecord(ctx->ev_b, s2));
     }
     EBCC_HIP_CHECK(hipMemcpyAsync(jb.dec_table, table, table_ints * sizeof(int), hipMemcpyHostToDevice, s));
-    // the decoded field is written where the caller wants it (the engine's own field buffer and a 1 GB device-to-device copy
-    // per 256 frames only for an output that is not aligned the way the engine's buffers are)
+    // the decoded field is written where the caller wants it ([n][tiles][tile pixels] == [n][chunk pixels]; the engine's own
+    // field buffer and a 1 GB device-to-device copy per 256 frames only for an output that is not aligned the way the
+    // engine's buffers are)
     const bool direct = ((uintptr_t) d_out & 255u) == 0;
     J2kBuffers view = jb;
     if (direct) view.DEC = d_out;
-    launch_j2k_decode(view, (int) n, s, table);
+    launch_j2k_decode(view, (int) nt, s, table);
     if (next) { next->release(); release_on_exit.g = nullptr; }     // host parsing done, kernels queued
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
-        launch_synthesis_tail_add(view.DEC, ctx->rb, (int) n, ctx->d_active, s);     // last row pass: field += residual
+        launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s);     // last row pass: field += residual
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // constant fields: fill on the host side of the copy (rare path)
-    for (size_t f = 0; f < n; f++)
-        if (ctx->h_fs[f].const_field) {
-            std::vector<float> v(n_pix, ctx->h_fs[f].minv);
-            EBCC_HIP_CHECK(hipMemcpyAsync(d_out + f * n_pix, v.data(), n_pix * sizeof(float), hipMemcpyHostToDevice, s));
-            wait_stream(s);
-        }
-    wait_stream(s);
-    pt.mark("decode: kernels");
-    return 0;
-}
-
-// Chunks of several frames: the tail is one codestream with a tile per frame (reference :121-125); the tiles are
-// decoded as frames of `ctx`, the residual of the whole chunk image in `rc`.
-// Frame heights a chunk of several frames can have: OpenJPEG cannot set up 6 resolutions on smaller tiles (the
-// reference crashes on them), and the chunk image itself is bounded by the reference's 2047-row limit.
-bool tile_height_supported(size_t h) { return h >= 32 && h <= 1023; }
-// Heights for which every tile has the geometry of a tile at the origin (sub-band extents, parity and code-block
-// partition repeat): the context then needs a single geometry for all tile positions.
-bool tile_geometry_uniform(size_t h) { return h >= 32 && h <= 1024 && (h & (h - 1)) == 0; }
-
-int decode_tiled(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, const uint8_t *const *streams, const size_t *sizes, size_t n, size_t tiles,
-                 float *d_out)
-{
-    J2kBuffers &jb = *static_cast<J2kBuffers *>(ctx->j2k);
-    hipStream_t s = ctx->stream, rs = rc->stream;
-    const J2kGeom &g = jb.geom;
-    const size_t tile_pix = ctx->n_pix, n_pix = tile_pix * tiles, nt = n * tiles;
-    std::vector<int> table(nt * (size_t) g.stride * 4, 0);
-    std::vector<std::vector<uint8_t>> coeffs(n);
-    std::vector<size_t> off(tiles), len(tiles);
-    bool any_resid = false;
-    for (size_t c = 0; c < n; c++) {
-        ParsedFrame hd;
-        if (!parse_frame(streams[c], sizes[c], hd)) return 1;
-        rc->h_active[c] = 0;
-        FrameState &r = rc->h_fs[c];
-        r = FrameState{};
-        r.minv = hd.minv; r.maxv = hd.maxv; r.rmin = hd.rmin; r.rmax = hd.rmax; r.const_field = hd.const_field ? 1 : 0;
-        for (size_t k = 0; k < tiles; k++) {
-            FrameState &t = ctx->h_fs[c * tiles + k];
-            t = FrameState{};
-            t.minv = hd.minv; t.maxv = hd.maxv; t.const_field = r.const_field;
-        }
-        if (hd.const_field) {
-            uint64_t cnt = 0;
-            memcpy(&cnt, hd.tail, 8);
-            if (cnt != n_pix) { log_fatal("const-field length %llu does not match the chunk", (unsigned long long) cnt); return 1; }
-            continue;
-        }
-        if (!j2k_parse_tiled(hd.tail, hd.tail_size, jb, (int) tiles, table.data() + c * tiles * g.stride * 4, off.data(), len.data())) {
-            log_fatal("Invalid encoded data: %s", ebcc_hip_last_error());
-            return 1;
-        }
-        for (size_t k = 0; k < tiles; k++) {
-            if (len[k] > jb.stream_cap) { log_fatal("tile-part larger than the device slot"); return 1; }
-            EBCC_HIP_CHECK(hipMemcpyAsync(jb.stream + (c * tiles + k) * jb.stream_cap, hd.tail + off[k], len[k], hipMemcpyHostToDevice, s));
-        }
-        if (hd.compressed_size > 0 && hd.coeffs_size > 0) {
-            if (hd.coeffs_size > rc->rb.stream_words * 4 - 64) { log_fatal("residual stream larger than the device slot"); return 1; }
-            coeffs[c].assign(hd.coeffs_size, 0);
-            const size_t got = zstd().decompress(coeffs[c].data(), hd.coeffs_size, hd.z, hd.compressed_size);
-            if ((zstd().is_error && zstd().is_error(got)) || got != hd.coeffs_size) { log_fatal("Invalid encoded data: residual payload does not decompress to %zu bytes", hd.coeffs_size); return 1; }
-            if (check_ims_header(rc, coeffs[c].data(), hd.coeffs_size, hd.coeffs_size * 8)) { log_fatal("Invalid encoded data: %s", ebcc_hip_last_error()); return 1; }
-            rc->h_active[c] = 1;
-            any_resid = true;
-        }
-    }
-    push_frame_states(ctx, nt);
-    EBCC_HIP_CHECK(hipMemcpyAsync(jb.dec_table, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    launch_j2k_decode(jb, (int) nt, s, table.data());
-    wait_stream(s);
-    if (any_resid) {
-        push_frame_states(rc, n);
-        const size_t slot = rc->rb.stream_words * 4;
-        for (size_t c = 0; c < n; c++) {
-            rc->h_u64a[c] = coeffs[c].size();
-            rc->h_u64b[c] = coeffs[c].size() * 8;
-            if (rc->h_active[c])
-                EBCC_HIP_CHECK(hipMemcpyAsync((uint8_t *) rc->rb.stream + c * slot, coeffs[c].data(), coeffs[c].size(), hipMemcpyHostToDevice, rs));
-        }
-        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64a, rc->h_u64a, n * sizeof(unsigned long long), hipMemcpyHostToDevice, rs));
-        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_u64b, rc->h_u64b, n * sizeof(unsigned long long), hipMemcpyHostToDevice, rs));
-        EBCC_HIP_CHECK(hipMemcpyAsync(rc->d_active, rc->h_active, n * sizeof(int), hipMemcpyHostToDevice, rs));
-        launch_spiht_decode((const uint8_t *) rc->rb.stream, slot, rc->d_u64a, rc->d_u64b, rc->rb, (int) n, rc->d_active, rs);
-        launch_synthesis_head(rc->rb, (int) n, rc->d_active, rs);
-        launch_synthesis_tail_add(jb.DEC, rc->rb, (int) n, rc->d_active, rs);
-        wait_stream(rs);
-    }
-    EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // constant chunks: fill on the host side of the copy (rare path)
     for (size_t c = 0; c < n; c++)
         if (rc->h_fs[c].const_field) {
             std::vector<float> v(n_pix, rc->h_fs[c].minv);
@@ -1113,7 +1049,15 @@ int decode_tiled(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, const uint8_t *const *stre
             wait_stream(s);
         }
     wait_stream(s);
+    pt.mark("decode: kernels");
     return 0;
 }
+
+// Frame heights a chunk of several frames can have: OpenJPEG cannot set up 6 resolutions on smaller tiles (the
+// reference crashes on them), and the chunk image itself is bounded by the reference's 2047-row limit.
+bool tile_height_supported(size_t h) { return h >= 32 && h <= 1023; }
+// Heights for which every tile has the geometry of a tile at the origin (sub-band extents, parity and code-block
+// partition repeat): the context then needs a single geometry for all tile positions.
+bool tile_geometry_uniform(size_t h) { return h >= 32 && h <= 1024 && (h & (h - 1)) == 0; }
 
 }  // namespace ebcc

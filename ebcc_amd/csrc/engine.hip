@@ -209,9 +209,9 @@ void fetch_frame_states(ebcc_hip_ctx *ctx, size_t n)
     EBCC_HIP_CHECK(hipMemcpyAsync(ctx->h_fs, ctx->rb.fs, n * sizeof(FrameState), hipMemcpyDeviceToHost, ctx->stream));
     wait_stream(ctx->stream);
 }
-void push_frame_states(ebcc_hip_ctx *ctx, size_t n)
+void push_frame_states(ebcc_hip_ctx *ctx, size_t n, hipStream_t s)
 {
-    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->rb.fs, ctx->h_fs, n * sizeof(FrameState), hipMemcpyHostToDevice, ctx->stream));
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->rb.fs, ctx->h_fs, n * sizeof(FrameState), hipMemcpyHostToDevice, s ? s : ctx->stream));
 }
 
 // ---- optional kernel timing -------------------------------------------------------------------------

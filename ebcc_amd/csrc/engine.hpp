@@ -75,8 +75,8 @@ bool ensure_cut_slots(ebcc_hip_ctx *ctx, int capacity);
 // header of a SPIHT stream against the context's grid and a usable bit budget (non-zero: reject, message set)
 int check_ims_header(ebcc_hip_ctx *ctx, const uint8_t *b, size_t n, size_t num_bits);
 
-// synchronous copy of the frame states to ctx->h_fs
+// synchronous copy of the frame states to ctx->h_fs; and back, on ctx->stream unless `s` is given
 void fetch_frame_states(ebcc_hip_ctx *ctx, size_t n_frames);
-void push_frame_states(ebcc_hip_ctx *ctx, size_t n_frames);
+void push_frame_states(ebcc_hip_ctx *ctx, size_t n_frames, hipStream_t s = nullptr);
 
 }  // namespace ebcc

@@ -2,7 +2,7 @@
 //   host_pool.hip    logging, the dlopen'd libzstd and the provable lower bound of its output, the CPU budget, the
 //                    process-wide worker pool of the entropy stage (HostPool) and its accounting
 //   batch_codec.hip  one device batch: the frame codec of /root/reference/src/ebcc_codec.c:607-918 (encode_batch) and
-//                    :1215-1320 (decode_batch, decode_tiled) on an engine, with its three search loops
+//                    :1215-1320 (decode_batch) on an engine, with its three search loops
 //   host_codec.hip   engines per device and geometry, slices and alternating engine sets, host <-> device copies, the EBCK
 //                    container, and the C API of include/ebcc_codec.h / include/ebcc_hip.h
 //   h5z_filter.hip   the HDF5 filter plugin (id 308) of /root/reference/src/h5z_ebcc.c
@@ -279,13 +279,14 @@ struct ParsedFrame {
     const uint8_t *z = nullptr, *tail = nullptr;
 };
 bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf);
-// ebcc_decode for a batch of single-frame EBCC streams -> device buffer d_out [n][H*W]
-int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out, SliceGate *next = nullptr);
-// chunks of several frames (one tiled codestream per chunk): frame heights such a chunk can have, heights for which every
-// tile has the geometry of a tile at the origin, and the decode
+// ebcc_decode for a batch of `n` chunk streams of `tiles` frames each, as encode_batch codes them -> device buffer
+// d_out [n][tiles * H * W].  Returns 0 or 1 (error).
+int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out, SliceGate *next = nullptr,
+                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr);
+// chunks of several frames (one tiled codestream per chunk): frame heights such a chunk can have, and heights for which
+// every tile has the geometry of a tile at the origin
 bool tile_height_supported(size_t h);
 bool tile_geometry_uniform(size_t h);
-int decode_tiled(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, const uint8_t *const *streams, const size_t *sizes, size_t n, size_t tiles, float *d_out);
 
 // ---- frames in host memory <-> frame streams on the engines the reference-compatible entry points keep (host_codec.hip):
 //      any number of one-frame chunks of H x W, batches of EBCC_HIP_MAX_BATCH on alternating engine sets.  0 ok, 1 error, 2 NaN/Inf

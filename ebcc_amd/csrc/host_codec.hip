@@ -528,6 +528,7 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 
 // The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
 // the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
+// Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
 int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
                    float *out, Prefault *prefault)
 {
@@ -536,7 +537,7 @@ int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap
         PhaseTimer pt;
         float *d = io_buffer(set, cap * n_pix * sizeof(float));
         pt.mark("host decode: device image");
-        const int r = tiles > 1 ? decode_tiled(set, rc, streams + lo, sizes + lo, k, tiles, d) : run_decode_slices(set, streams + lo, sizes + lo, k, d);
+        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc) : run_decode_slices(set, streams + lo, sizes + lo, k, d);
         if (r) return r;
         pt.mark("host decode: decode");
         if (prefault) prefault->join();
@@ -892,8 +893,7 @@ size_t ebcc_decode(uint8_t *data, size_t data_size, float **out_buffer)
         PhaseTimer pt;
         float *d = io_buffer(ctx, n_pix * sizeof(float));
         const uint8_t *sp = data;
-        int rcode = tiles > 1 ? decode_tiled(ctx, rc, &sp, &data_size, 1, tiles, d) : decode_batch(ctx, &sp, &data_size, 1, d);
-        if (rcode) return 0;
+        if (decode_batch(ctx, &sp, &data_size, 1, d, nullptr, tiles, rc)) return 0;
         pt.mark("ebcc_decode: decode_batch");
         // :1126-1128: honour a caller-provided buffer
         float *o = *out_buffer ? *out_buffer : (float *) malloc(n_pix * sizeof(float));

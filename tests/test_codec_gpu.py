@@ -142,6 +142,68 @@ def test_multi_frame_chunks_with_short_frames_are_refused():
     assert lib.ebcc_encode(x.ctypes.data, ctypes.byref(cfg), ctypes.byref(out)) == 0
 
 
+def _tile_parts(tail):
+    """where the tile-parts of a codestream start: the first SOT after the main header's marker segments, then Psot
+    bytes apart (T.800 A.4.2)"""
+    at = 2                                                            # (SOC)
+    while tail[at:at + 2] != b"\xff\x90":
+        at += 2 + int.from_bytes(tail[at + 2:at + 4], "big")
+    parts = []
+    while tail[at:at + 2] == b"\xff\x90":
+        parts.append(at)
+        at += int.from_bytes(tail[at + 6:at + 10], "big")
+    assert tail[at:] == b"\xff\xd9"                                   # (EOC)
+    return parts
+
+
+def test_multi_frame_chunk_streams_that_break_a_check_are_refused():
+    """Golden streams of several-frame chunks with a residual payload that does not decompress to its length, a tile
+    index out of range or repeated, the last tile-part cut short, and an EBCK container whose constant chunk has the
+    wrong sample count: each is refused (0), and the intact streams then decode on the same engines to their golden
+    fields."""
+    import struct
+    lib = L.product()
+    frames = _tiled["frames"]
+    resid = frames["waves_2x64x96_cr20_m1_q0.1+nofallback"]             # 2 tiles, residual layer
+    tiled = frames["odd_3x37x70_cr5_m1_qNone"]                          # 3 tiles, a geometry per tile position
+    const = frames["const_2x32x32_cr5_m1_qNone"]
+
+    def refused(blob, fn="ebcc_decode"):
+        b = ctypes.create_string_buffer(bytes(blob), len(blob))
+        out = ctypes.c_void_p()
+        return getattr(lib, fn)(b, len(blob), ctypes.byref(out)) == 0
+
+    def with_tail(stream, tail):
+        """the stream with another codestream and the header's tail_size to match"""
+        z = int.from_bytes(stream[32:40], "little")
+        return stream[:40] + struct.pack("<Q", len(tail)) + stream[48:48 + z] + tail
+
+    r = bytes.fromhex(resid["stream_hex"])
+    assert int.from_bytes(r[16:24], "little") > 0
+    assert refused(r[:16] + struct.pack("<Q", int.from_bytes(r[16:24], "little") + 1) + r[24:])
+    t = bytes.fromhex(tiled["stream_hex"])
+    tail = t[48 + int.from_bytes(t[32:40], "little"):]
+    parts = _tile_parts(tail)
+    assert len(parts) == 3
+    for isot in (3, 0):                                                 # out of range; tile 0's again
+        bad = bytearray(tail)
+        bad[parts[1] + 4:parts[1] + 6] = isot.to_bytes(2, "big")
+        assert refused(with_tail(t, bytes(bad))), isot
+    psot = int.from_bytes(tail[parts[2] + 6:parts[2] + 10], "big")
+    assert refused(with_tail(t, tail[:parts[2] + psot // 2]))
+    c = bytes.fromhex(const["stream_hex"])
+    assert c[5] & 1 and int.from_bytes(c[48:56], "little") == 2 * 32 * 32
+
+    def container(streams):
+        hd = b"EBCK" + struct.pack("<III3Q3QQQ", 1, 3, 0, 2 * len(streams), 32, 32, 2, 32, 32, len(streams), 2 * 32 * 32)
+        return hd + b"".join(struct.pack("<Q", len(s)) + s for s in streams)
+    assert refused(container([c, c[:48] + struct.pack("<Q", 2 * 32 * 32 - 1), c]), "ebcc_decode_chunking")
+    for case, s in ((resid, r), (tiled, t)):
+        assert sha(api_decode(s).tobytes()) == case["decoded_sha256"]
+    d = api_decode(container([c, c, c]), "ebcc_decode_chunking")
+    assert [sha(d[k * 2048:(k + 1) * 2048].tobytes()) for k in range(3)] == [const["decoded_sha256"]] * 3
+
+
 def full_size_formula_frame():
     """the 721 x 1440 input of tests/golden/codec_big.json"""
     y, x = np.mgrid[0:721, 0:1440]
@@ -294,18 +356,32 @@ def test_tuning_knobs_do_not_change_results(monkeypatch):
         assert np.array_equal(np.asarray(L.orc_decode(fast[f])).ravel(), ref_dec[f].ravel())
 
 
-@pytest.mark.parametrize("chunk", [(1, 96, 160), (1, 64, 96), (1, 96, 100)], ids=str)
-def test_chunking_entry_points_on_many_chunks(chunk):
+@pytest.mark.parametrize("chunk", [(1, 96, 160), (1, 64, 96), (1, 96, 100), (4, 96, 160), (5, 64, 96)], ids=str)
+def test_chunking_entry_points_on_many_chunks(chunk, monkeypatch):
     """ebcc_encode_chunking / ebcc_decode_chunking on an array of enough chunks for the sliced path (every slice
     uploads / downloads its own frames): whole-frame chunks used in place, smaller chunks gathered by rows with
-    clamped padding at the edges (reference :311-370) - container and decoded array identical to the oracle's."""
+    clamped padding at the edges (reference :311-370) - container and decoded array identical to the oracle's.
+    Chunks of several frames (96 rows: a tile geometry per position; 64 rows: one geometry, padded edges) on one device:
+    a single decode call takes constant chunks, chunks with a residual layer and chunks without one."""
     shape = (20, 96, 160)
     data = np.stack([L.era5_like(96, 160, 300 + s, 1.0 + 0.1 * (s % 4), 0.6) for s in range(shape[0])]).astype(np.float32)
+    k = chunk[0]
+    if k > 1:
+        # the first chunks constant, the next ones nearly flat (their base layer alone keeps the bound), the rest with a
+        # loose base layer and no pure base-layer fallback (a residual layer)
+        data[:k] = 7.0
+        data[k:2 * k] = np.float32(250.0) + (data[k:2 * k] - np.float32(250.0)) * np.float32(1e-4)
+        monkeypatch.setenv("EBCC_INIT_BASE_ERROR_QUANTILE", "0.02")
+        monkeypatch.setenv("EBCC_DISABLE_PURE_BASE_COMPRESSION_FALLBACK", "1")
+        monkeypatch.setenv("EBCC_HIP_DEVICES", "0")
     cfg = L.make_config(shape, chunk, base_cr=15.0, error=0.05, residual_type=L.MAX_ERROR)
     L.oracle().orc_set_j2k_backend(0)
     want = L.orc_encode(data, cfg, "orc_ebcc_encode_chunking")
     got = api_encode(data, cfg, "ebcc_encode_chunking")
     assert len(got) == len(want) and got == want
+    if k > 1:
+        kinds = ["const" if s[5] & 1 else "residual" if int.from_bytes(s[16:24], "little") else "base" for s in _ebck_streams(got)]
+        assert set(kinds) == {"const", "residual", "base"}, kinds
     dec = api_decode(got, "ebcc_decode_chunking")
     assert np.array_equal(dec, np.asarray(L.orc_decode(want, "orc_ebcc_decode_chunking")).ravel())
     # (the reference's mean-error adjustment shifts the field after the bound was checked: a few percent of slack)
