@@ -898,7 +898,7 @@ bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf)
 // tile-parts of one tiled codestream (reference :121-125) - and its residual layer one frame of `rctx` (== ctx for
 // one-frame chunks).
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx)
+                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, const DecodeWindow *win)
 {
     struct Release { SliceGate *g; ~Release() { if (g) g->release(); } } release_on_exit{next};
     ebcc_hip_ctx *const rc = rctx ? rctx : ctx;
@@ -906,6 +906,23 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     hipStream_t s = ctx->stream;
     const size_t nt = n * tiles, n_pix = ctx->n_pix * tiles;         // frames of ctx; pixels of a chunk
     const J2kGeom &g = jb.geom;
+    // window decode: the cone of the window and, per code-block of a frame, whether it holds it
+    J2kWindow cone;
+    std::vector<uint8_t> keep;
+    if (win) {
+        if (tiles != 1 || g.period != 1) { set_error("window decode: chunks of several frames are not supported"); return 1; }
+        if (!j2k_window_supported(g)) { set_error("window decode: frames of %d x %d are not supported (fewer than 3 columns)", g.H, g.W); return 1; }
+        if (!j2k_window_plan(g, win->row0, win->col0, win->rows, win->cols, cone)) {
+            set_error("window decode: the window is empty or not inside the %d x %d frame", g.H, g.W);
+            return 1;
+        }
+        std::vector<J2kBlock> blocks;
+        make_j2k_geom(g.H, g.W, blocks);
+        keep.resize(blocks.size());
+        int rect[4];
+        for (size_t b = 0; b < blocks.size(); b++) keep[b] = j2k_window_keeps(g, blocks[b], cone, rect) ? 1 : 0;
+    }
+    const size_t out_pix = win ? win->pixels() : n_pix;               // samples a chunk puts out
     int *const table = ctx->h_table;                                  // (pinned)
     const size_t table_ints = nt * (size_t) g.stride * 4;
     memset(table, 0, table_ints * sizeof(int));
@@ -958,6 +975,8 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
         if (tiles == 1) {
             if (hd.tail_size > jb.stream_cap) { log_fatal("codestream larger than the device slot"); return false; }
             if (!j2k_parse_codestream(hd.tail, hd.tail_size, g, rows)) return false;
+            for (size_t b = 0; b < keep.size(); b++)                   // (window decode) a zeroed entry is a code-block without data
+                if (!keep[b]) rows[4 * b] = rows[4 * b + 1] = rows[4 * b + 2] = rows[4 * b + 3] = 0;
             piece[c] = hd.tail_size;
         } else {
             if (!j2k_parse_tiled(hd.tail, hd.tail_size, jb, (int) tiles, rows, &src_off[c * tiles], &piece[c * tiles])) {
@@ -1031,21 +1050,24 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     // the decoded field is written where the caller wants it ([n][tiles][tile pixels] == [n][chunk pixels]; the engine's own
     // field buffer and a 1 GB device-to-device copy per 256 frames only for an output that is not aligned the way the
     // engine's buffers are)
-    const bool direct = ((uintptr_t) d_out & 255u) == 0;
+    // (a window always goes straight to the caller's compact array: its kernels store single samples where pairs are not aligned)
+    const bool direct = win || ((uintptr_t) d_out & 255u) == 0;
     J2kBuffers view = jb;
-    if (direct) view.DEC = d_out;
-    launch_j2k_decode(view, (int) nt, s, table);
+    if (direct && !win) view.DEC = d_out;
+    launch_j2k_decode(view, (int) nt, s, table, win ? &cone : nullptr, win ? d_out : nullptr);
     if (next) { next->release(); release_on_exit.g = nullptr; }     // host parsing done, kernels queued
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
-        launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s);     // last row pass: field += residual
+        // last row pass: field += residual (of a window: its rows alone)
+        if (win) launch_synthesis_tail_add_window(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
+        else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s);
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
     // constant chunks: fill on the host side of the copy (rare path)
     for (size_t c = 0; c < n; c++)
         if (rc->h_fs[c].const_field) {
-            std::vector<float> v(n_pix, rc->h_fs[c].minv);
-            EBCC_HIP_CHECK(hipMemcpyAsync(d_out + c * n_pix, v.data(), n_pix * sizeof(float), hipMemcpyHostToDevice, s));
+            std::vector<float> v(out_pix, rc->h_fs[c].minv);
+            EBCC_HIP_CHECK(hipMemcpyAsync(d_out + c * out_pix, v.data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
             wait_stream(s);
         }
     wait_stream(s);

@@ -280,9 +280,14 @@ struct ParsedFrame {
 };
 bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf);
 // ebcc_decode for a batch of `n` chunk streams of `tiles` frames each, as encode_batch codes them -> device buffer
-// d_out [n][tiles * H * W].  Returns 0 or 1 (error).
+// d_out [n][tiles * H * W].  Returns 0 or 1 (error).  `win` (one-frame chunks only): the window [row0, row0 + rows) x
+// [col0, col0 + cols) of every frame alone, d_out [n][rows][cols], from the code-blocks its dependency cone holds (J2kWindow).
+struct DecodeWindow {
+    size_t row0, col0, rows, cols;
+    size_t pixels() const { return rows * cols; }
+};
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out, SliceGate *next = nullptr,
-                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr);
+                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, const DecodeWindow *win = nullptr);
 // chunks of several frames (one tiled codestream per chunk): frame heights such a chunk can have, and heights for which
 // every tile has the geometry of a tile at the origin
 bool tile_height_supported(size_t h);

@@ -380,11 +380,12 @@ int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,
 // the decode counterpart (decode overlaps its two layers on the engine's two streams, decode_batch; a second slice hides
 // the host side - parsing, zstd, uploads - of one half behind the kernels of the other when there are hardware queues
 // for four streams)
-int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out)
+// (`win`: the frames' window alone, d_out [n_frames][rows][cols])
+int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeWindow *win = nullptr)
 {
-    const size_t n_pix = ctx->n_pix;
+    const size_t n_pix = win ? win->pixels() : ctx->n_pix;
     return run_slices(ctx, n_frames, [&](ebcc_hip_ctx *c, size_t lo, size_t cnt, SliceGate *next, unsigned) {
-        return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + lo * n_pix, next);
+        return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + lo * n_pix, next, 1, nullptr, win);
     }, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);
 }
 
@@ -529,15 +530,16 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 // The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
 // the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
 // Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
+// `win` (one-frame chunks): the frames' window alone - `out` is [n][rows][cols], and only that crosses to the host.
 int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
-                   float *out, Prefault *prefault)
+                   float *out, Prefault *prefault, const DecodeWindow *win = nullptr)
 {
-    const size_t n_pix = ctx->n_pix * tiles;
+    const size_t n_pix = win ? win->pixels() : ctx->n_pix * tiles;
     auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
         PhaseTimer pt;
         float *d = io_buffer(set, cap * n_pix * sizeof(float));
         pt.mark("host decode: device image");
-        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc) : run_decode_slices(set, streams + lo, sizes + lo, k, d);
+        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, win) : run_decode_slices(set, streams + lo, sizes + lo, k, d, win);
         if (r) return r;
         pt.mark("host decode: decode");
         if (prefault) prefault->join();
@@ -622,14 +624,29 @@ int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, s
         return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * ctx->n_pix; });
     });
 }
-int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out)
+int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
+                    const DecodeWindow *win = nullptr)
 {
     if (!ctx || !streams || !sizes || !d_out || n < 1) { set_error("%s: bad arguments", who); return 1; }
+    const size_t out_pix = win ? win->pixels() : ctx->n_pix;
     return on_codec(ctx->device, 1, [&] {
         return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-            return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + lo * ctx->n_pix);
+            return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + lo * out_pix, win);
         });
     });
+}
+// the window of a window-decode entry point, checked against the context's frames before anything runs (nothing is written
+// for a window that is refused)
+bool window_of(const char *who, const ebcc_hip_ctx *ctx, size_t row0, size_t col0, size_t rows, size_t cols, DecodeWindow &w)
+{
+    if (!ctx) { set_error("%s: bad arguments", who); return false; }
+    const size_t H = (size_t) ctx->height, W = (size_t) ctx->width;
+    if (rows < 1 || cols < 1 || row0 >= H || col0 >= W || rows > H - row0 || cols > W - col0) {
+        set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is empty or not inside the %zu x %zu frame", who, row0, rows, col0, cols, H, W);
+        return false;
+    }
+    w = DecodeWindow{row0, col0, rows, cols};
+    return true;
 }
 
 }  // namespace
@@ -760,6 +777,35 @@ int ebcc_hip_decode_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams
     return on_codec(ctx->device, 1, [&] {
         Prefault prefault(h_frames_out, n_frames * ctx->n_pix * sizeof(float));
         return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_frames_out, &prefault);
+    });
+}
+
+// Window decode: the box [row0, row0 + rows) x [col0, col0 + cols) of every frame, bit for bit the crop of what the entry
+// point without a window gives, from the code-blocks the box depends on (J2kWindow, j2k.hpp); output [n][rows][cols].
+int ebcc_hip_decode_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                                  size_t rows, size_t cols, float *d_out)
+{
+    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames_window: bad batch"); return 1; }
+    DecodeWindow w;
+    if (!window_of("ebcc_hip_decode_frames_window", ctx, row0, col0, rows, cols, w)) return 1;
+    return decode_resident("ebcc_hip_decode_frames_window", ctx, streams, sizes, n_frames, d_out, &w);
+}
+int ebcc_hip_decode_shard_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                                 size_t rows, size_t cols, float *d_out)
+{
+    DecodeWindow w;
+    if (!window_of("ebcc_hip_decode_shard_window", ctx, row0, col0, rows, cols, w)) return 1;
+    return decode_resident("ebcc_hip_decode_shard_window", ctx, streams, sizes, n_frames, d_out, &w);
+}
+int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                                       size_t rows, size_t cols, float *h_out)
+{
+    if (!ctx || !streams || !sizes || !h_out || n_frames < 1) { set_error("ebcc_hip_decode_host_frames_window: bad arguments"); return 1; }
+    DecodeWindow w;
+    if (!window_of("ebcc_hip_decode_host_frames_window", ctx, row0, col0, rows, cols, w)) return 1;
+    return on_codec(ctx->device, 1, [&] {
+        Prefault prefault(h_out, n_frames * w.pixels() * sizeof(float));
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_out, &prefault, &w);
     });
 }
 

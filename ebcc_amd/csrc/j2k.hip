@@ -351,11 +351,90 @@ bool j2k_parse_tiled(const uint8_t *cs, size_t n, const J2kBuffers &jb, int tile
     return true;
 }
 
+// ================================================================================================
+// window decode: the code-blocks a box of the frame depends on (J2kWindow, j2k.hpp)
+// ================================================================================================
+namespace {
+// one inverse level along one axis: the outputs [a, b) of n interleaved samples (sn low-pass ones first in the band layout)
+// need the low-pass samples [l0, l1) and the high-pass samples [h0, h1)
+void cone_axis(int n, int a, int b, int &l0, int &l1, int &h0, int &h1)
+{
+    const int sn = (n + 1) / 2, dn = n - sn;
+    if (a >= b) { l0 = l1 = h0 = h1 = 0; return; }
+    const int last = b - 1;
+    const int lo = std::max(0, a - ((a & 1) ? 4 : 3)), hi = std::min(n - 1, last + ((last & 1) ? 4 : 3));   // interleaved positions, inclusive
+    l0 = (lo + 1) / 2; l1 = std::min(sn, hi / 2 + 1);                  // even positions 2k
+    h0 = lo / 2; h1 = std::min(dn, (hi + 1) / 2);                      // odd positions 2k + 1
+    if (l1 < l0) l1 = l0;
+    if (h1 <= h0) h0 = h1 = 0;
+}
+}  // namespace
+
+bool j2k_window_plan(const J2kGeom &g, size_t row0, size_t col0, size_t rows, size_t cols, J2kWindow &w)
+{
+    const size_t H = (size_t) g.H, W = (size_t) g.W;
+    if (rows < 1 || cols < 1 || row0 >= H || col0 >= W || rows > H - row0 || cols > W - col0) return false;   // (no sums: they may overflow)
+    w = J2kWindow{};
+    w.row0 = (int) row0; w.col0 = (int) col0; w.rows = (int) rows; w.cols = (int) cols;
+    int x0 = w.col0, x1 = w.col0 + w.cols, y0 = w.row0, y1 = w.row0 + w.rows;
+    for (int r = kJ2kRes - 1; r >= 1; r--) {
+        w.rx0[r] = x0; w.rx1[r] = x1; w.ry0[r] = y0; w.ry1[r] = y1;
+        int lx0, lx1, hx0, hx1, ly0, ly1, hy0, hy1;
+        cone_axis(g.rw[r], x0, x1, lx0, lx1, hx0, hx1);
+        cone_axis(g.rh[r], y0, y1, ly0, ly1, hy0, hy1);
+        const int b = 3 * (r - 1) + 1;                                  // HL, LH, HH of this resolution
+        const int need[3][4] = {{hx0, hx1, ly0, ly1}, {lx0, lx1, hy0, hy1}, {hx0, hx1, hy0, hy1}};
+        for (int k = 0; k < 3; k++) {
+            const bool none = need[k][0] >= need[k][1] || need[k][2] >= need[k][3];
+            for (int q = 0; q < 4; q++) w.band[b + k][q] = none ? 0 : need[k][q];
+        }
+        x0 = lx0; x1 = lx1; y0 = ly0; y1 = ly1;
+    }
+    w.rx0[0] = x0; w.rx1[0] = x1; w.ry0[0] = y0; w.ry1[0] = y1;
+    w.band[0][0] = x0; w.band[0][1] = x1; w.band[0][2] = y0; w.band[0][3] = y1;
+    return true;
+}
+
+bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, int rect[4])
+{
+    const J2kBand &bd = g.bands[b.band];
+    rect[0] = b.x - bd.offx + bd.x0; rect[1] = rect[0] + b.w;
+    rect[2] = b.y - bd.offy + bd.y0; rect[3] = rect[2] + b.h;
+    const int *n = w.band[b.band];
+    return n[0] < n[1] && n[2] < n[3] && rect[0] < n[1] && n[0] < rect[1] && rect[2] < n[3] && n[2] < rect[3];
+}
+
 }  // namespace ebcc
 
 using namespace ebcc;
 
 extern "C" {
+
+// The code-blocks a window decode needs (include/ebcc_hip.h; host only, no device work).
+__attribute__((visibility("default"))) int ebcc_hip_window_plan(size_t height, size_t width, size_t row0, size_t col0, size_t rows, size_t cols,
+                                                                int *bands, int *blocks, size_t max_blocks)
+{
+    EBCC_API_TRY
+    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("ebcc_hip_window_plan: bad geometry"); return -1; }
+    std::vector<J2kBlock> blk;
+    const J2kGeom g = make_j2k_geom((int) height, (int) width, blk);
+    J2kWindow w;
+    if (!j2k_window_plan(g, row0, col0, rows, cols, w)) { set_error("ebcc_hip_window_plan: the window is empty or not inside the frame"); return -1; }
+    if (bands) {
+        for (int b = 0; b < kJ2kBands; b++)
+            for (int q = 0; q < 4; q++) bands[4 * b + q] = w.band[b][q];
+    }
+    if (blocks) {
+        for (size_t i = 0; i < blk.size() && i < max_blocks; i++) {
+            int rect[4];
+            const bool keep = j2k_window_keeps(g, blk[i], w, rect);
+            int *o = blocks + 6 * i;
+            o[0] = blk[i].band; o[1] = rect[0]; o[2] = rect[1]; o[3] = rect[2]; o[4] = rect[3]; o[5] = keep ? 1 : 0;
+        }
+    }
+    return g.nblocks;
+    EBCC_API_CATCH(-1)
+}
 
 // Host-only check of the codestream parser (no device work): parses `cs` as a one-tile codestream of height x width
 // and verifies that every code-block entry it would hand to the device kernels lies inside the stream.  0 = accepted,

@@ -180,6 +180,24 @@ enum T1Kernel { T1_ENCODE = 0, T1_MQ = 1, T1_RESUME = 2, T1_DECODE = 3 };
 int t1_lanes_per_wave(int kernel, int total_blocks = 0);   // (total_blocks: code-blocks in the launch, for the encoder kernels)
 
 J2kGeom make_j2k_geom(int H, int W, std::vector<J2kBlock> &blocks, int ty0 = 0);
+
+// A window [row0, row0 + rows) x [col0, col0 + cols) of a frame at the origin and the dependency cone of the five inverse
+// 9/7 levels above it (j2k_window_plan, j2k.hip).  One level is four lifting steps, each reaching one interleaved neighbour:
+// an even output sample depends on the interleaved positions within +-3, an odd one on those within +-4, and the mirrored
+// forms at the frame's edges stay inside that range.  The needed interleaved range splits by parity into the low-pass range -
+// the next lower level's output range - and the high-pass range; rows and columns are independent, so a sub-band's needed
+// rectangle is the product of its two ranges.  All coordinates are those of the full frame: the boundary forms of the lifting
+// depend on the position in the frame, not in the window.  Ranges are [x0, x1) (x0 == x1: nothing needed).
+struct J2kWindow {
+    int row0, col0, rows, cols;
+    int rx0[kJ2kRes], rx1[kJ2kRes], ry0[kJ2kRes], ry1[kJ2kRes];   // samples of resolution r the cone holds (r = 5: the window itself)
+    int band[kJ2kBands][4];                                       // x0, x1, y0, y1 of every sub-band, in its own coordinates
+};
+// false: the window is empty or not inside the frame
+bool j2k_window_plan(const J2kGeom &g, size_t row0, size_t col0, size_t rows, size_t cols, J2kWindow &w);
+bool j2k_window_supported(const J2kGeom &g);    // frames a window decode takes (j2k_analysis.hip)
+// the code-block's rectangle {x0, x1, y0, y1} in its sub-band's coordinates; true if it meets the band's needed rectangle
+bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, int rect[4]);
 int j2k_selfcheck_div65535();   // mismatches of the division-free s / 65535.0f of the fused inverse level (0 expected)
 
 // ---- launchers (asynchronous on s) ---------------------------------------------------------------
@@ -211,7 +229,10 @@ void launch_j2k_probe_decode(const float *data, const J2kBuffers &jb, int n_fram
 // true decode of codestreams whose packet headers were parsed on the host into jb.dec_table
 // (fs[f].minv/maxv must hold the header's values); result in jb.DEC.  host_table: the host's copy of jb.dec_table, from
 // which the launch sizes its waves (null: the fixed tiers tuned for 256 frames)
-void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr);
+// `win`: only the window of the field, to win_out [n_frames][rows][cols] (jb.dec_table with the entries outside the window's
+// cone zeroed; host_table must be given; j2k_window_supported geometries); jb.DEC is not written
+void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kWindow *win = nullptr,
+                       float *win_out = nullptr);
 void plan_decode_lanes(const int *host_table, int total, int out[4]);   // (what launch_j2k_decode chooses; ebcc_hip_plan_decode_lanes)
 
 }  // namespace ebcc

@@ -841,6 +841,121 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO 
     }
 }
 
+// Window decode (J2kWindow): the pass of k_j2k_level5_fin over the part of a level a window's dependency cone holds - the
+// strips strip0 .. strip0 + strips - 1 and the vertical positions [pos0, pos1) in `pieces` pieces - with the same expressions
+// in the same order at the same frame coordinates, so that every sample it puts out has the bits the whole-frame pass gives
+// it.  A piece starts its column pipelines two positions early (as the pieces of the whole-frame pass do) and a strip
+// carries two pairs of halo on either side; positions outside the frame take the boundary forms, positions outside the cone
+// are read from wherever the clamped index points and their results are dropped.  FIN: the field goes straight to the
+// caller's compact [frame][rows][cols] array - rows of any alignment, so single stores unless pairs happen to be aligned;
+// no statistics.  FIN = false: the level's output goes to `io.out` at its frame coordinates like the whole-frame pass.
+struct J2kWinOut { float *out; int row0, col0, rows, cols; };
+template <bool FIN>
+__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_win(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
+                                                                     const FrameState *fs, J2kWinOut win, int strip0, int strips, int n_frames,
+                                                                     int pieces, int pos0, int pos1)
+{
+    const int lane = (int) threadIdx.x & 63, local = (int) blockIdx.x * ((int) blockDim.x >> 6) + ((int) threadIdx.x >> 6);
+    const int frame = (int) blockIdx.y % n_frames, piece = (int) blockIdx.y / n_frames;
+    if (local >= strips) return;                                        // (no barrier anywhere below)
+    if (fs[frame].const_field) return;
+    const int strip = strip0 + local;
+    const J2kGeom &g = j2k_frame_geom(geom, frame);
+    const int r = FIN ? kJ2kRes - 1 : io.r;
+    const int W = g.W, nh = g.rw[r], snh = g.rw[r - 1], dnh = nh - snh;
+    const int nv = g.rh[r], snv = g.rh[r - 1], dnv = nv - snv;
+    const size_t n_pix = (size_t) W * g.H;
+    const int i = strip * kL5Pairs + lane - 2;
+    const bool has_e = i >= 0 && i < snh, has_o = i >= 0 && i < dnh;
+    const bool owner = lane >= 2 && lane < 2 + kL5Pairs && has_e;
+    const float *b = io.ll ? io.ll + (size_t) frame * io.ll_frame : nullptr;
+    const unsigned lp = (unsigned) io.ll_pitch;
+    const int32_t *v = V + (size_t) frame * n_pix;
+    const float s_ll = 0.5f * g.bands[0].step_dec, s_hl = 0.5f * g.bands[3 * (r - 1) + 1].step_dec, s_lh = 0.5f * g.bands[3 * (r - 1) + 2].step_dec,
+                s_hh = 0.5f * g.bands[3 * (r - 1) + 3].step_dec;
+    float *d = FIN ? win.out + (size_t) frame * ((size_t) win.rows * (size_t) win.cols) : nullptr;
+    float *o = FIN ? nullptr : io.out + (size_t) frame * io.out_frame;
+    const float mn = fs[frame].minv, rng = fs[frame].maxv - fs[frame].minv;
+    const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
+    const bool first = i == 0, no_o = !(i < dnh), last_o = !(i + 1 < snh);
+    auto hsynth = [&](float e_raw, float o_raw, float &even, float &odd) {
+        const float e0 = has_e ? e_raw * kK : 0.0f, o0 = has_o ? o_raw * kTwoInvK : 0.0f;
+        const float o0l = lane_below(o0);
+        const float e1 = no_o ? e0 + (o0l * (c1 + c1)) : e0 + (((first ? o0 : o0l) + o0) * c1);
+        const float e1r = lane_above(e1);
+        const float o1 = last_o ? o0 + (e1 * (c2 + c2)) : o0 + ((e1 + e1r) * c2);
+        const float o1l = lane_below(o1);
+        const float e2 = no_o ? e1 + (o1l * (c3 + c3)) : e1 + (((first ? o1 : o1l) + o1) * c3);
+        const float e2r = lane_above(e2);
+        even = e2;
+        odd = last_o ? o1 + (e2 * (c4 + c4)) : o1 + ((e2 + e2r) * c4);
+    };
+    const int per = ceil_div(pos1 - pos0, pieces), ja = pos0 + piece * per, jb = min(pos1, ja + per);
+    if (ja >= jb) return;
+    const int jstart = max(ja - 2, 0);
+    ColPipe2 p0, p1;
+    const unsigned c_lo = (unsigned) min(max(i, 0), snh - 1), c_hi = (unsigned) snh + (unsigned) min(max(i, 0), max(dnh - 1, 0));
+    // 8-byte stores of a pair: the whole-frame condition for a lower level; for the field, a window of even position and
+    // width in an 8-byte aligned array (both samples of a pair are then inside the window or both outside)
+    const bool pair_io = FIN ? (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (nh & 1) == 0 && ((size_t) win.out & 7) == 0
+                             : (nh & 1) == 0 && ((size_t) o & 7) == 0 && (io.out_pitch & 1) == 0 && (io.out_frame & 1) == 0;
+    float in_ll, in_hl, in_lh, in_hh;
+    auto fetch = [&](int j, float &ll, float &hl, float &lh, float &hh) {
+        const unsigned jl = (unsigned) min(j, snv - 1), jh = (unsigned) (snv + min(j, max(dnv - 1, 0)));
+        const unsigned rl = jl * (unsigned) W, rh = jh * (unsigned) W;
+        ll = b ? b[jl * lp + c_lo] : (float) v[rl + c_lo] * s_ll;
+        hl = (float) v[rl + c_hi] * s_hl;
+        lh = (float) v[rh + c_lo] * s_lh;
+        hh = (float) v[rh + c_hi] * s_hh;
+    };
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    auto put_row = [&](bool emit, int y, float ev, float od, bool has_odd_col) {
+        if constexpr (!FIN) {
+            if (!emit) return;
+            float *q = o + (size_t) ((unsigned) y * (unsigned) io.out_pitch + 2u * (unsigned) i);
+            if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{ev, od};
+            else { q[0] = ev; if (has_odd_col) q[1] = od; }
+        } else {
+            const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
+            const int wy = y - win.row0, wx = 2 * i - win.col0;         // position in the window
+            if (!emit || wy < 0 || wy >= win.rows) return;
+            float *q = d + (size_t) wy * (size_t) win.cols;
+            if (pair_io) { if (wx >= 0 && wx < win.cols) *reinterpret_cast<f32x2 *>(q + wx) = f32x2{de, dq}; }
+            else {
+                if (wx >= 0 && wx < win.cols) q[wx] = de;
+                if (has_odd_col && wx + 1 >= 0 && wx + 1 < win.cols) q[wx + 1] = dq;
+            }
+        }
+    };
+    fetch(jstart, in_ll, in_hl, in_lh, in_hh);
+    for (int j = jstart; j < jb + 2; j++) {
+        float n_ll, n_hl, n_lh, n_hh;
+        fetch(j + 1, n_ll, n_hl, n_lh, n_hh);
+        const bool emit = owner && j - 2 >= ja;
+        float lo_even = 0, lo_odd = 0, hi_even = 0, hi_odd = 0;
+        if (j >= 2 && j < dnv) {
+            hsynth(in_ll, in_hl, lo_even, lo_odd);
+            hsynth(in_lh, in_hh, hi_even, hi_odd);
+            float a0, a1, b0, b1;
+            p0.interior(lo_even, hi_even, a0, a1);
+            p1.interior(lo_odd, hi_odd, b0, b1);
+            put_row(emit, 2 * (j - 2), a0, b0, has_o);
+            put_row(emit, 2 * (j - 2) + 1, a1, b1, has_o);
+        } else {
+            if (j < snv) hsynth(in_ll, in_hl, lo_even, lo_odd);
+            if (j < dnv) hsynth(in_lh, in_hh, hi_even, hi_odd);
+            float a0, a1, b0, b1;
+            bool he, ho, he1, ho1;
+            p0.edge(j, snv, dnv, lo_even, hi_even, a0, a1, he, ho);
+            p1.edge(j, snv, dnv, lo_odd, hi_odd, b0, b1, he1, ho1);
+            if (he) put_row(emit, 2 * (j - 2), a0, b0, has_o);
+            if (ho) put_row(emit, 2 * (j - 2) + 1, a1, b1, has_o);
+            (void) he1; (void) ho1;
+        }
+        in_ll = n_ll; in_hl = n_hl; in_lh = n_lh; in_hh = n_hh;
+    }
+}
+
 template <typename K>
 void big_lds(K k, size_t bytes)
 {
@@ -1760,8 +1875,11 @@ void launch_j2k_analysis(const float *data, const J2kBuffers &jb, int n_frames, 
 // dequantisation + inverse transform of the tier-1 decoder's output V through the tile buffers B to the decoded
 // field jb.DEC, with the error statistics against `data` (if given) left as partial sums per frame; used by both
 // decode flavours (j2k_rate.hip).  Returns the number of partials per frame.
+// `win` (decode only: no statistics, every frame active): the fused levels run over the window's dependency cone alone and the
+// top level writes the window of the field to win_out [n_frames][rows][cols] (k_j2k_level_win); lower levels that take the
+// separate passes run whole.  The top level has to be a fused one (j2k_window_supported).
 int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuffers &jb, int n_frames, const FrameState *fs,
-                    const int *active, hipStream_t s, int keep_field)
+                    const int *active, hipStream_t s, int keep_field, const J2kWindow *win, float *win_out)
 {
     int partials = 0;
     // plain frames: every level in one fused pass (k_j2k_level5_fin: horizontal synthesis in registers, vertical register
@@ -1775,6 +1893,7 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     };
     int first_fused = kJ2kRes;                                          // levels first_fused .. top are fused (sizes grow with r)
     for (int r = kJ2kRes - 1; r >= 1 && fusable(r); r--) first_fused = r;
+    if (win && first_fused == kJ2kRes) throw std::runtime_error("window decode: this geometry has no fused top level");
     const float *ll = nullptr;                                          // low-pass input of the next fused level (null: from V)
     float *spare = jb.B2;
     for (int r = 1; r < kJ2kRes; r++) {                                // opj_dwt_decode_tile_97: horizontal, then vertical
@@ -1790,6 +1909,25 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
             const int wg = std::min(strips, wave_cap), groups = ceil_div(strips, wg);
             if (r > 1 && !ll) ll = B;                                   // (the separate passes below left their result in B)
             J2kLevelIO io{ll, g.W, n_pix, nullptr, g.W, n_pix, r};
+            if (win) {
+                // the strips and vertical positions that hold the cone's samples of this resolution
+                const int strip0 = (win->rx0[r] / 2) / kL5Pairs, wstrips = ((win->rx1[r] - 1) / 2) / kL5Pairs - strip0 + 1;
+                const int pos0 = win->ry0[r] / 2, pos1 = (win->ry1[r] - 1) / 2 + 1;
+                int wpieces = std::max(1, std::min(r == kJ2kRes - 1 ? 8 : 4, (pos1 - pos0) / 16));
+                while (wpieces > 1 && (long long) n_frames * wpieces > 65535) wpieces--;
+                const int wwg = std::min(wstrips, wave_cap), wgroups = ceil_div(wstrips, wwg);
+                const J2kWinOut wo{win_out, win->row0, win->col0, win->rows, win->cols};
+                if (r == kJ2kRes - 1) {
+                    hipLaunchKernelGGL(k_j2k_level_win<true>, dim3((unsigned) wgroups, (unsigned) (n_frames * wpieces)), dim3(64 * wwg), 0, s, io, V, jb.d_geom, fs, wo,
+                                       strip0, wstrips, n_frames, wpieces, pos0, pos1);
+                } else {
+                    io.out = ll == spare ? B : spare;
+                    hipLaunchKernelGGL(k_j2k_level_win<false>, dim3((unsigned) wgroups, (unsigned) (n_frames * wpieces)), dim3(64 * wwg), 0, s, io, V, jb.d_geom, fs, wo,
+                                       strip0, wstrips, n_frames, wpieces, pos0, pos1);
+                    ll = io.out;
+                }
+                continue;
+            }
             if (r == kJ2kRes - 1) {
                 partials = strips * pieces;
                 hipLaunchKernelGGL(k_j2k_level5_fin<true>, dim3((unsigned) groups, (unsigned) (n_frames * pieces)), dim3(64 * wg), 0, s, io, V, jb.d_geom, fs, active,
@@ -1808,6 +1946,10 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     EBCC_HIP_LAUNCH_CHECK();
     return partials;
 }
+
+// A window decode writes the field from the fused top level (there is no whole field to crop): single-tile frames of at least
+// three columns - every legal frame (32 .. 2047 samples either way) is one.
+bool j2k_window_supported(const J2kGeom &g) { return g.period == 1 && g.ry0[kJ2kRes - 1] % 2 == 0 && g.rw[kJ2kRes - 2] >= 2 && g.rh[kJ2kRes - 2] >= 1; }
 
 // host check of div65535_exact against the division it replaces, for every value it is used on (ebcc_hip_selfcheck)
 int j2k_selfcheck_div65535()

@@ -18,7 +18,7 @@
 namespace ebcc {
 
 int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuffers &jb, int n_frames, const FrameState *fs,
-                    const int *active, hipStream_t s, int keep_field);
+                    const int *active, hipStream_t s, int keep_field, const J2kWindow *win = nullptr, float *win_out = nullptr);
 
 namespace {
 
@@ -1634,10 +1634,10 @@ void launch_j2k_write(const J2kBuffers &jb, int n_frames, const int *d_active, h
 }
 
 static void decode_tail(const float *data, const J2kBuffers &jb, int n_frames, const int *d_active, bool stats, hipStream_t s,
-                        int keep_field = 1)
+                        int keep_field = 1, const J2kWindow *win = nullptr, float *win_out = nullptr)
 {
     // dequantisation happens in the row passes, the mapping to the fp32 field and the statistics in the last column pass
-    const int partials = j2k_inverse_dwt(jb.B, jb.V, stats ? data : nullptr, jb, n_frames, jb.fs, d_active, s, keep_field);
+    const int partials = j2k_inverse_dwt(jb.B, jb.V, stats ? data : nullptr, jb, n_frames, jb.fs, d_active, s, keep_field, win, win_out);
     if (stats)
         hipLaunchKernelGGL(k_finish_reduce, dim3(ceil_div(n_frames, 64)), dim3(64), 0, s, jb.partial, jb.partial_u, jb.jf,
                            n_frames, partials, jb.fs, d_active);
@@ -1734,16 +1734,28 @@ void plan_decode_lanes(const int *host_table, int total, int out[4])
     out[3] = t.lanes[3];
 }
 
-void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table)
+void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table, const J2kWindow *win, float *win_out)
 {
     const size_t n_pix = (size_t) jb.geom.W * jb.geom.H;
     const int total = n_frames * jb.geom.stride;
     const size_t groups = ((size_t) total + 63) / 64;
+    // Window decode: the table entries of the code-blocks outside the window's cone have been zeroed.  Empty entries come last
+    // in the longest-first order, so the launch ends at the last entry with data (`live`), and the lanes per wave are planned
+    // from those entries alone: a small window has few, short chains and lands on the one-lane shape by the same model.
+    int live = total;
+    std::vector<int> live_table;
+    if (win && host_table) {
+        for (int i = 0; i < total; i++) {
+            const int *e = host_table + (size_t) i * 4;
+            if (e[3] > 0 && e[2] > 0) live_table.insert(live_table.end(), e, e + 4);
+        }
+        live = (int) (live_table.size() / 4);
+    }
     EBCC_HIP_CHECK(hipMemsetAsync(jb.V, 0, (size_t) n_frames * n_pix * sizeof(int32_t), s));
     int lpw = std::min(16, t1_lanes_per_wave(T1_DECODE));              // (the state row masks of a wave's code-blocks live in LDS: at most 16)
     // few code-blocks (a frame or a few decoded alone, e.g. from an HDF5 filter callback): there are wave slots to spare and
     // a wave per code-block ends soonest (one 721 x 1440 frame through ebcc_decode: 16.8 -> 8.6 ms)
-    const bool few_blocks = !getenv("EBCC_T1_LPW") && total <= 4096;
+    const bool few_blocks = !getenv("EBCC_T1_LPW") && live <= 4096;
     if (few_blocks) lpw = 1;
     if (getenv("EBCC_HIP_T1_STATS")) {                                   // diagnostics: the code-blocks with the longest segments
         std::vector<int> h((size_t) total * 4);
@@ -1754,7 +1766,7 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
         std::sort(idx.begin(), idx.end(), [&](int a, int b) { return h[(size_t) a * 4 + 1] > h[(size_t) b * 4 + 1]; });
         long long sum = 0;
         for (int i = 0; i < total; i++) sum += h[(size_t) i * 4 + 1];
-        fprintf(stderr, "ebcc-mi355x t1 decode: %d code-blocks, %lld bytes; longest:", total, sum);
+        fprintf(stderr, "ebcc-mi355x t1 decode: %d code-blocks, %lld bytes, %d of them launched; longest:", total, sum, live);
         for (int i = 0; i < std::min(total, 12); i++) fprintf(stderr, " [blk %d len %d P %d np %d]", idx[i] % jb.geom.stride, h[(size_t) idx[i] * 4 + 1], h[(size_t) idx[i] * 4 + 2], h[(size_t) idx[i] * 4 + 3]);
         fprintf(stderr, "; percentiles of len:");
         for (int q : {50, 90, 99}) fprintf(stderr, " p%d %d", q, h[(size_t) idx[(size_t) total * (100 - q) / 100] * 4 + 1]);
@@ -1779,6 +1791,7 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
         DecTiers tiers{{0, 0, 0}, {1, 2, 4, 4}};
         if (few_blocks) { tiers.lanes[3] = 1; }
         else if (getenv("EBCC_T1_LPW")) { tiers.lanes[3] = lpw; }
+        else if (win && host_table && !getenv("EBCC_T1_DEC_TIERS")) tiers = plan_dec_tiers(live_table.data(), live);
         else if (host_table && !getenv("EBCC_T1_DEC_TIERS")) tiers = plan_dec_tiers(host_table, total);
         else {
             int den[3] = {kDecTierDen0, kDecTierDen1, kDecTierDen2};
@@ -1790,23 +1803,24 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
             }
             int before = 0;
             for (int t = 0; t < 3; t++) {
-                const int upto = den[t] > 0 ? total / den[t] : 0;                  // (den 0: no such tier)
+                const int upto = den[t] > 0 ? live / den[t] : 0;                   // (den 0: no such tier)
                 const int n = std::max(0, upto - before) / tiers.lanes[t] * tiers.lanes[t];
                 tiers.n[t] = n; before += n;
             }
         }
         if (getenv("EBCC_HIP_T1_STATS")) fprintf(stderr, "ebcc-mi355x t1 decode tiers: %d code-blocks alone in their waves, %d in pairs, the rest %d to a wave\n", tiers.n[0], tiers.n[1], tiers.lanes[3]);
         unsigned waves = 0;
-        int rest = total;
+        int rest = live;
         for (int t = 0; t < 3; t++) { waves += (unsigned) (tiers.n[t] / tiers.lanes[t]); rest -= tiers.n[t]; }
         waves += (unsigned) ceil_div(rest, tiers.lanes[3]);
         const int max_lanes = std::max(std::max(tiers.n[0] ? tiers.lanes[0] : 1, tiers.n[1] ? tiers.lanes[1] : 1), std::max(tiers.n[2] ? tiers.lanes[2] : 1, rest > 0 ? tiers.lanes[3] : 1));
         ensure_ctx_tables();
+        if (waves)
         hipLaunchKernelGGL(k_t1_decode_lds, dim3(waves), dim3(64), (size_t) kDecStateRows * max_lanes * 8, s, jb.stream,
-                           jb.stream_cap, jb.dec_table, jb.dec_order, jb.V, jb.d_geom, jb.d_blocks, jb.fs, total, tiers);
+                           jb.stream_cap, jb.dec_table, jb.dec_order, jb.V, jb.d_geom, jb.d_blocks, jb.fs, live, tiers);
     }
     timing_end("t1_decode", s);
-    decode_tail(nullptr, jb, n_frames, nullptr, false, s);
+    decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, win, win_out);
     EBCC_HIP_LAUNCH_CHECK();
 }
 

@@ -242,6 +242,40 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
     }
 }
 
+// The addition form of k_rows_inv_use for a window of the field (window decode): the rows [row0, row0 + rows) alone, each
+// synthesised whole (a row is one lifting chain; its samples outside the window are its halo), and out += r for the columns
+// [col0, col0 + cols), with `out` the compact [frame][rows][cols] array.  Same expressions as the whole-frame pass.
+__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_window(const float *__restrict__ src, int stride, size_t frame_stride, int n,
+                                                                      const int *active, const FrameState *fs, float *out, int row0, int col0,
+                                                                      int rows, int cols)
+{
+    extern __shared__ float sm[];
+    const int frame = blockIdx.y;
+    if (active && !active[frame]) return;
+    const int half = n >> 1;
+    float *E = sm, *O = sm + half;
+    src += (size_t) frame * frame_stride;
+    const int tid = threadIdx.x;
+    float *o = out + (size_t) frame * ((size_t) rows * (size_t) cols);
+    const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
+    for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
+        const float *s = src + (size_t) (row0 + wy) * stride;
+        for (int k = tid; k < half; k += kRowThreads) {
+            E[k] = s[k];
+            O[k] = s[half + k];
+        }
+        __syncthreads();
+        lift_inverse_tile(E, O, half, 1, RowIdx(), tid, kRowThreads);
+        for (int wx = tid; wx < cols; wx += kRowThreads) {
+            const int xx = col0 + wx;
+            const float r = residual_value((xx & 1) ? O[xx >> 1] : E[xx >> 1], dc, rmin, rng);
+            const size_t i = (size_t) wy * (size_t) cols + (size_t) wx;
+            o[i] = o[i] + r;
+        }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(kRowThreads) void k_rows_inv(const float *__restrict__ src, float *__restrict__ dst,
                                                            int stride, size_t frame_stride, int n, int rows,
                                                            const int *active)
@@ -1300,6 +1334,16 @@ void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_fram
     RowUse u{};
     u.out = out;
     synthesis_tail(rb, n_frames, d_active, s, u);
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+// the same for the window [row0, row0 + rows) x [col0, col0 + cols) of the field; out: [n_frames][rows][cols]
+void launch_synthesis_tail_add_window(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
+                                      int rows, int cols)
+{
+    const Grid &g = rb.g;
+    hipLaunchKernelGGL(k_rows_inv_add_window, dim3(min(rows, 96), n_frames), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
+                       d_active, rb.fs, out, row0, col0, rows, cols);
     EBCC_HIP_LAUNCH_CHECK();
 }
 

@@ -63,6 +63,9 @@ class BatchCodec:
                                                     ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         lib.ebcc_hip_decode_host_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                                     ctypes.c_size_t, ctypes.c_void_p]
+        lib.ebcc_hip_decode_host_frames_window.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                                           ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                           ctypes.c_void_p]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -98,16 +101,28 @@ class BatchCodec:
             self.lib.free_buffer(outs[i])
         return res
 
-    def decode(self, streams, out=None):
+    def decode(self, streams, out=None, window=None):
         """list of EBCC frame streams (bytes), any number -> (n, H, W) float32; `out`: a C-contiguous float32 array to decode
         into (the frames cross PCIe straight into it; its pages are mapped while the GPU decodes, one batch is downloaded
-        beside the kernels of the next)."""
+        beside the kernels of the next).  `window` = (row0, col0, rows, cols): only that box of every frame, (n, rows, cols) -
+        bit for bit the crop of the full decode, from the code-blocks the box depends on; nothing else is decoded or
+        downloaded."""
         n = len(streams)
         assert n >= 1
         streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
         # (pointers into the bytes objects themselves: they stay alive in `streams` for the duration of the call)
         ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        if window is not None:
+            row0, col0, rows, cols = (int(v) for v in window)
+            if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > self.h or col0 + cols > self.w:
+                raise ValueError(f"window {tuple(window)} is empty or not inside the {self.h} x {self.w} frame")
+            if out is None:
+                out = np.empty((n, rows, cols), np.float32)
+            assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == n * rows * cols
+            if self.lib.ebcc_hip_decode_host_frames_window(self.ctx, ptrs, sizes, n, row0, col0, rows, cols, out.ctypes.data):
+                raise RuntimeError("ebcc_hip_decode_host_frames_window: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
+            return out
         if out is None:
             out = np.empty((n, self.h, self.w), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == n * self.h * self.w
@@ -182,15 +197,30 @@ def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, co
             dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
 
 
-def read_frames(dset, batch=256, codec=None):
+def _box(sl, n, what):
+    """(first, count) of a slice over an axis of n samples (None: all of it); step 1 and not empty"""
+    if sl is None:
+        return 0, n
+    if not isinstance(sl, slice):
+        raise TypeError(f"{what} must be a slice or None")
+    first, stop, step = sl.indices(n)
+    if step != 1 or stop <= first:
+        raise ValueError(f"{what}: a non-empty slice of step 1 is needed, got {sl}")
+    return first, stop - first
+
+
+def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
     """Read an EBCC-filtered one-frame-per-chunk dataset by decoding its raw chunks in device batches, several batches per
     call (they alternate between two engine sets: one is downloaded while the next decodes).  The raw chunks of the next
     call are fetched from the file (h5py, one call per chunk) on a helper thread meanwhile; the frames land straight in
-    their place in the result."""
+    their place in the result.  `rows` / `cols`: slices (step 1) over the frames' two axes - only that box of every frame is
+    decoded and downloaded, and the result has the shape lead + (rows, cols); it equals read_frames(dset)[..., rows, cols]."""
     h, w = dset.shape[-2:]
     lead = dset.shape[:-2]
     n = int(np.prod(lead)) if lead else 1
-    out = np.empty((n, h, w), np.float32)
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    window = None if (nrows, ncols) == (h, w) else (row0, col0, nrows, ncols)
+    out = np.empty((n, nrows, ncols), np.float32)
     codec = codec or cached_codec(h, w, min(batch, n))
     step = _SUPER * codec.max_frames
 
@@ -221,8 +251,8 @@ def read_frames(dset, batch=256, codec=None):
             t = threading.Thread(target=fetch, args=(lo + step, box))
             t.start()
         try:
-            codec.decode(raw, out=out[lo:lo + len(raw)])
+            codec.decode(raw, out=out[lo:lo + len(raw)], window=window)
         finally:
             if t:
                 t.join()
-    return out.reshape(dset.shape)
+    return out.reshape(tuple(lead) + (nrows, ncols))

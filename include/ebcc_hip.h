@@ -143,6 +143,40 @@ int ebcc_hip_encode_shard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_fra
 int ebcc_hip_decode_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                           float *d_frames_out);
 
+/* ---- window decode ---------------------------------------------------------------------------
+ * A box [row0, row0 + rows) x [col0, col0 + cols) of every frame - the regional subset of an archive of global fields -
+ * decoded from the code-blocks it depends on alone; the reference has no counterpart (ebcc_decode, src/ebcc_codec.h:42,
+ * returns whole frames).  The result is bit for bit the crop of what the entry point without a window gives.  Only the
+ * tier-1 decode of the needed 64 x 64 code-blocks, the parts of the inverse wavelet levels above the box and the box's rows
+ * of the residual layer's last pass run; the field is written straight into the compact output [n][rows][cols] (any 4-byte
+ * aligned address), and the host-array form downloads nothing else.  The residual layer's SPIHT decode is one serial chain
+ * per frame and runs whole.  Constant fields fill the box with their value; frames without a residual layer, legacy
+ * header-less streams and mixed batches work as in the full decode.  Return 0 = ok, 1 = error (ebcc_hip_last_error): an empty
+ * window or one not inside the frame is refused before anything is written, malformed streams are refused as by the full
+ * decode.
+ * Not covered: chunks of several frames (ebcc_decode_chunking's tiled chunks), ebcc_h5_read_frames, the encode side, and
+ * the reference-compatible entry points of ebcc_codec.h. */
+
+/* Which code-blocks of a height x width frame a decode of the window [row0,row0+rows) x [col0,col0+cols) needs: the dependency
+ * cone of the five inverse 9/7 levels (an even output sample of a level depends on the interleaved positions within +-3, an
+ * odd one on those within +-4; the range splits by parity into the low-pass range - the next level's outputs - and the
+ * high-pass range).  Host logic, no device work.
+ * bands: 16 x {x0, x1, y0, y1}, the needed rectangle of every sub-band in its own coordinates (order of J2kGeom::bands;
+ *        x0 == x1: nothing needed).  blocks (may be NULL): per code-block, in decode-table order,
+ *        {band, x0, x1, y0, y1, keep}.  Returns the number of code-blocks of the frame, -1 for a window that is empty
+ *        or not inside the frame, or a geometry ebcc_hip_create refuses. */
+int ebcc_hip_window_plan(size_t height, size_t width, size_t row0, size_t col0, size_t rows, size_t cols,
+                         int *bands, int *blocks, size_t max_blocks);
+/* ebcc_hip_decode_frames for a window: at most the context's capacity of frames, d_out [n_frames][rows][cols] on the device */
+int ebcc_hip_decode_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                  size_t row0, size_t col0, size_t rows, size_t cols, float *d_out);
+/* ebcc_hip_decode_shard for a window: any number of frames, batches on the two engine sets */
+int ebcc_hip_decode_shard_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                 size_t row0, size_t col0, size_t rows, size_t cols, float *d_out);
+/* ebcc_hip_decode_host_frames for a window: pageable host output [n_frames][rows][cols]; only the window crosses PCIe */
+int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                       size_t row0, size_t col0, size_t rows, size_t cols, float *h_out);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
