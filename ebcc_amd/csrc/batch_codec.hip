@@ -1059,8 +1059,8 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
         // last row pass: field += residual (of a window: its rows alone)
-        if (win) launch_synthesis_tail_add_window(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
-        else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s);
+        if (win) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
+        else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s, 0, 0, rc->rb.g.size_y, rc->rb.g.size_x);
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
     // constant chunks: fill on the host side of the copy (rare path)

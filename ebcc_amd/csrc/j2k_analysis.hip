@@ -491,6 +491,49 @@ __device__ inline float fin_map(float v, float rng, float mn)
     }
     return ((float) (int) q / 65535.0f) * rng + mn;
 }
+// The vertical half of an inverse level as a register pipeline two positions deep, one per column: a step takes the low- and
+// high-pass samples of vertical position j and hands out the finished samples of position j - 2 (rows 2 (j - 2) and the next).
+// e0/o0: scaled inputs; e1, o1, e2, odd: after lifting steps 1..4 (istep_lo -kD, istep_hi -kG, istep_lo -kB, istep_hi -kA)
+struct ColPipe {
+    float o0_prev = 0, e1_prev = 0, o1_prev = 0, e2_prev = 0;
+    // 2 <= j < dn: every neighbour exists, no boundary test
+    __device__ void interior(float lo_raw, float hi_raw, float &even, float &odd)
+    {
+        const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
+        const float e0 = lo_raw * kK, o0 = hi_raw * kTwoInvK;
+        const float e1 = e0 + ((o0_prev + o0) * c1);
+        const float o1 = o0_prev + ((e1_prev + e1) * c2);
+        const float e2 = e1_prev + ((o1_prev + o1) * c3);
+        even = e2_prev;
+        odd = o1_prev + ((e2_prev + e2) * c4);
+        o0_prev = o0; e1_prev = e1; o1_prev = o1; e2_prev = e2;
+    }
+    // any position, with the boundary forms (o1[-1] := o1[0] and so on); has_even / has_odd say which of the two samples exist
+    __device__ void edge(int j, int sn, int dn, float lo_raw, float hi_raw, float &even, float &odd, bool &has_even, bool &has_odd)
+    {
+        const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
+        float e1 = 0, o0 = 0;
+        if (j < sn) {
+            const float e0 = lo_raw * kK;
+            if (j < dn) o0 = hi_raw * kTwoInvK;
+            if (j < dn) e1 = e0 + (((j == 0 ? o0 : o0_prev) + o0) * c1);
+            else        e1 = e0 + (o0_prev * (c1 + c1));
+        }
+        // o1[j - 1] = o0[j - 1] + (e1[j - 1] + e1[j]) * c2, boundary form when e1[j] does not exist
+        float o1 = 0;
+        const int i1 = j - 1;
+        if (i1 >= 0 && i1 < dn) o1 = (i1 + 1 < sn) ? o0_prev + ((e1_prev + e1) * c2) : o0_prev + (e1_prev * (c2 + c2));
+        // e2[j - 1] = e1[j - 1] + (o1[j - 2] + o1[j - 1]) * c3
+        float e2 = 0;
+        if (i1 >= 0 && i1 < sn) e2 = (i1 < dn) ? e1_prev + (((i1 == 0 ? o1 : o1_prev) + o1) * c3) : e1_prev + (o1_prev * (c3 + c3));
+        // o2[j - 2] = o1[j - 2] + (e2[j - 2] + e2[j - 1]) * c4
+        const int i2 = j - 2;
+        has_even = i2 >= 0 && i2 < sn; has_odd = i2 >= 0 && i2 < dn;
+        even = e2_prev;
+        odd = (i2 + 1 < sn) ? o1_prev + ((e2_prev + e2) * c4) : o1_prev + (e2_prev * (c4 + c4));
+        o0_prev = o0; e1_prev = e1; o1_prev = o1; e2_prev = e2;
+    }
+};
 constexpr int kFinT = 128;           // columns per workgroup
 __global__ __launch_bounds__(kFinT) void k_j2k_cols_fin(const float *__restrict__ B, const J2kGeom *geom, int r, const FrameState *fs,
                                                          const int *active, J2kFinish fin)
@@ -508,7 +551,6 @@ __global__ __launch_bounds__(kFinT) void k_j2k_cols_fin(const float *__restrict_
     if (d && live) d += col;
     const float mn = fs[frame].minv, rng = fs[frame].maxv - fs[frame].minv;
     const float target = x ? fin.jf[frame].target : 0.0f;
-    const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
     double acc = 0;
     unsigned int bad = 0;
     auto out = [&](int y, float v) {
@@ -521,33 +563,19 @@ __global__ __launch_bounds__(kFinT) void k_j2k_cols_fin(const float *__restrict_
         }
     };
     if (live) {
-        // e0/o0: scaled inputs; e1, o1, e2, o2: after lifting steps 1..4 (istep_lo -kD, istep_hi -kG, istep_lo -kB, istep_hi -kA)
-        float o0_prev = 0, e1_prev = 0, o1_prev = 0, o1_prev2 = 0, e2_prev = 0;
+        ColPipe p;
         // j runs two past the end: position j enters the pipeline, position j - 2 leaves it
         for (int j = 0; j < sn + 2; j++) {
-            float e1 = 0, o0 = 0;
-            if (j < sn) {
-                const float e0 = lo[(size_t) j * W] * kK;
-                if (j < dn) o0 = hi[(size_t) j * W] * kTwoInvK;
-                if (j < dn) e1 = e0 + (((j == 0 ? o0 : o0_prev) + o0) * c1);
-                else        e1 = e0 + (o0_prev * (c1 + c1));
+            float lo_raw = 0, hi_raw = 0, even, odd;
+            bool has_even, has_odd;
+            if (j < sn) {                                                // (dn <= sn)
+                lo_raw = lo[(size_t) j * W];
+                if (j < dn) hi_raw = hi[(size_t) j * W];
             }
-            // o1[j - 1] = o0[j - 1] + (e1[j - 1] + e1[j]) * c2, boundary form when e1[j] does not exist
-            float o1 = 0;
-            const int i1 = j - 1;
-            if (i1 >= 0 && i1 < dn) o1 = (i1 + 1 < sn) ? o0_prev + ((e1_prev + e1) * c2) : o0_prev + (e1_prev * (c2 + c2));
-            // e2[j - 1] = e1[j - 1] + (o1[j - 2] + o1[j - 1]) * c3   (o1[-1] := o1[0])
-            float e2 = 0;
-            if (i1 >= 0 && i1 < sn) e2 = (i1 < dn) ? e1_prev + (((i1 == 0 ? o1 : o1_prev) + o1) * c3) : e1_prev + (o1_prev * (c3 + c3));
-            // o2[j - 2] = o1[j - 2] + (e2[j - 2] + e2[j - 1]) * c4
-            const int i2 = j - 2;
-            if (i2 >= 0) {
-                if (i2 < sn) out(2 * i2, e2_prev);
-                if (i2 < dn) out(2 * i2 + 1, (i2 + 1 < sn) ? o1_prev + ((e2_prev + e2) * c4) : o1_prev + (e2_prev * (c4 + c4)));
-            }
-            o0_prev = o0; e1_prev = e1; o1_prev2 = o1_prev; o1_prev = o1; e2_prev = e2;
+            p.edge(j, sn, dn, lo_raw, hi_raw, even, odd, has_even, has_odd);
+            if (has_even) out(2 * (j - 2), even);
+            if (has_odd) out(2 * (j - 2) + 1, odd);
         }
-        (void) o1_prev2;
     }
     if (x) {
         __shared__ double red[kFinT / 64];
@@ -565,63 +593,55 @@ __global__ __launch_bounds__(kFinT) void k_j2k_cols_fin(const float *__restrict_
     }
 }
 
-// The vertical half of the last inverse level as a two-deep register pipeline (see k_j2k_cols_fin): step(j) takes the low- and
-// high-pass samples of vertical position j and hands out the finished samples of position j - 2.
-struct ColPipe {
-    float o0_prev = 0, e1_prev = 0, o1_prev = 0, e2_prev = 0;
-    template <class Out>
-    __device__ void step(int j, int sn, int dn, float lo_raw, float hi_raw, Out out)
-    {
-        const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
-        float e1 = 0, o0 = 0;
-        if (j < sn) {
-            const float e0 = lo_raw * kK;
-            if (j < dn) o0 = hi_raw * kTwoInvK;
-            if (j < dn) e1 = e0 + (((j == 0 ? o0 : o0_prev) + o0) * c1);
-            else        e1 = e0 + (o0_prev * (c1 + c1));
-        }
-        float o1 = 0;
-        const int i1 = j - 1;
-        if (i1 >= 0 && i1 < dn) o1 = (i1 + 1 < sn) ? o0_prev + ((e1_prev + e1) * c2) : o0_prev + (e1_prev * (c2 + c2));
-        float e2 = 0;
-        if (i1 >= 0 && i1 < sn) e2 = (i1 < dn) ? e1_prev + (((i1 == 0 ? o1 : o1_prev) + o1) * c3) : e1_prev + (o1_prev * (c3 + c3));
-        const int i2 = j - 2;
-        if (i2 >= 0) {
-            if (i2 < sn) out(2 * i2, e2_prev);
-            if (i2 < dn) out(2 * i2 + 1, (i2 + 1 < sn) ? o1_prev + ((e2_prev + e2) * c4) : o1_prev + (e2_prev * (c4 + c4)));
-        }
-        o0_prev = o0; e1_prev = e1; o1_prev = o1; e2_prev = e2;
-    }
-};
-
-// The WHOLE last inverse level (horizontal then vertical, opj_dwt_decode_tile_97 at the top resolution) with
-// dequantisation, field mapping and statistics in one pass over the data: a wave owns 60 sample pairs of the width
-// (+ 2 pairs of halo on either side), one pair per lane; for every vertical position it synthesises the low-pass and
-// the high-pass row horizontally in registers (neighbours through DPP wave shifts) and feeds two ColPipes, one per
-// column of the pair.  Nothing is written but the fp32 field (if wanted) and the statistics: against the separate
-// row and column passes this saves one write and one read of the frame per probe.  cas == 0 frames only.
+// The WHOLE inverse level (horizontal then vertical, opj_dwt_decode_tile_97) with dequantisation in one pass over the
+// data, written once (j2k_strip_pass) and parameterised by a RANGE - the part of the level a launch covers - and a SINK -
+// what happens to the finished samples.  A wave owns a strip: 60 sample pairs of the width (+ 2 pairs of halo on either
+// side), one pair per lane; for every vertical position it synthesises the low-pass and the high-pass row horizontally in
+// registers (neighbours through DPP wave shifts) and feeds two ColPipes, one per column of the pair.  cas == 0 frames only.
 //
-// Round 3.  The kernel runs 34 times per frame and was thought to be HBM-bound with a 2x over-fetch; it was bound by
+// Range (J2kStripRange): the strips strip0 .. strip0 + strips - 1 and the vertical positions [pos0, pos1) in `pieces`
+// pieces.  A piece starts its column pipelines two positions early and a strip carries its halo, so whatever the range, a
+// sample is computed by the same expressions in the same order at the same frame coordinates and has the same bits: the
+// whole level, or the part a window's dependency cone holds (J2kWindow) - positions outside the frame take the boundary
+// forms, positions outside the cone are read from wherever the clamped index points and their results are dropped.
+//
+// Sinks:
+//   J2kSinkNextLevel  a lower level r: the samples go to `io.out` (pitch out_pitch) as they are, the next level's low-pass
+//                     band, at their frame coordinates.  Out of place: the level's output region covers its own LL input, so
+//                     the levels alternate between two buffers.  LL comes from `io.ll`, or for level 1 from the decoder's
+//                     output like the other bands.  (k_j2k_level5_fin<false>, whole frame and window alike)
+//   J2kSinkFrameTop   the top level of the whole frame: field mapping, then the fp32 field (if wanted) and/or the error
+//                     statistics against the frame - against the separate row and column passes this saves one write and
+//                     one read of the frame per probe.  (k_j2k_level5_fin<true>)
+//   J2kSinkWindowTop  the top level of a window decode: field mapping, then the caller's compact [frame][rows][cols] array -
+//                     rows of any alignment, so single stores unless pairs happen to be aligned; no statistics.
+//                     (k_j2k_level_win)
+//
+// Round 3.  The top-level kernel runs 34 times per frame and was thought to be HBM-bound with a 2x over-fetch; it was bound by
 // VALU issue (~600 wave-instructions per iteration of 240 samples: boundary tests on every step, 26 LDS-crossbar
 // shuffles, four correctly rounded divisions by 65535, four fp64 accumulations) AND moved 1.7-2x its bytes (the strips of
 // a frame are 240-byte column ranges with halo, not multiples of a 128-byte line: the lines two strips share were fetched
 // once per strip, because neighbouring strips ran as independent workgroups on different XCDs or microseconds apart).
 // Now: (1) neighbouring strips of a (frame, piece) tile are waves of one workgroup, four at a time - same CU, same
 // instruction stream, started together - so a line two of them share is fetched once; (2) the vertical positions away
-// from the top and bottom edge take a step without any boundary test (ColPipe::step_interior), (3) neighbours come
+// from the top and bottom edge take a step without any boundary test (ColPipe::interior), (3) neighbours come
 // through v_mov_dpp wave shifts, (4) s / 65535.0f is fmaf(s, K_hi, s * K_lo) - equal to the correctly rounded quotient for
 // every integer s in [0, 65535] (div65535_exact; checked exhaustively by ebcc_hip_selfcheck and tests/test_boundary.py),
 // (5) frame samples and field leave / arrive as 8-byte pairs.
 constexpr int kL5Pairs = 60;
 constexpr int kL5MaxWaves = 16;       // strips (waves) of one workgroup
-// FIN = false: the same pass for a lower level r - the synthesised samples go to `out` (pitch out_pitch) as they are, the
-// next level's low-pass band.  Out of place: the level's output region covers its own LL input, so the levels alternate
-// between two buffers.  LL comes from `ll` (pitch ll_pitch), or for level 1 from the decoder's output like the other bands.
 struct J2kLevelIO {
     const float *ll; int ll_pitch; size_t ll_frame;      // low-pass input (null: from V, level 1)
-    float *out; int out_pitch; size_t out_frame;         // FIN = false only
+    float *out; int out_pitch; size_t out_frame;         // J2kSinkNextLevel only
     int r;
 };
+struct J2kStripRange { int strip0, strips, pos0, pos1, pieces; };    // (pos1 is cut to the level's positions)
+constexpr int kToLevelEnd = 0x7fffffff;                  // pos1 of a range that runs to the level's last position
+struct J2kWinOut { float *out; int row0, col0, rows, cols; };
+// what a sink is told about its lane: the pair i (columns 2i, 2i + 1) of frame `frame`, the level's extent, and the
+// wave's number among the launch's (strip, piece) tiles of the frame
+struct J2kStripLane { int frame, lane, i, W, nh, snh, nv; size_t n_pix; int tile; };
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 // s / 65535.0f for an integer-valued s in [0, 65535], without the division: K_hi + K_lo = 1 / 65535 to 2^-49, one rounding
 // at the end; the quotient's binary expansion repeats with period 16, so it is never within 2^-40 of a rounding boundary.
 __host__ __device__ inline float div65535_exact(float s)
@@ -640,55 +660,165 @@ __device__ inline float fin_map_fast(float v, float rng, float mn)
     const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(v) + 32768.0f, 0.0f, 65535.0f);
     return div65535_exact(q) * rng + mn;
 }
-// the interior step of ColPipe: 2 <= j < dn (every neighbour exists); hands out the samples of position j - 2
-struct ColPipe2 {
-    float o0_prev = 0, e1_prev = 0, o1_prev = 0, e2_prev = 0;
-    __device__ void interior(float lo_raw, float hi_raw, float &even, float &odd)
+
+// A sink has: begin(lane, empty) - false: the wave leaves (empty: its piece holds no position); load(j, x00, x01, x10, x11) -
+// before step j is computed: the frame's samples at the four positions the step puts out, if the sink compares with them;
+// put(emit, y, even, odd, xe, xo, has_odd_col) - the two finished samples of output row y and the frame's beside them, to be
+// dropped unless `emit`; end() - after the last step.
+struct J2kSinkNextLevel {
+    J2kLevelIO io;
+    float *o;
+    unsigned col;
+    bool pair_io;                  // 8-byte stores of the pair: even widths and 8-byte aligned bases
+    __device__ bool begin(const J2kStripLane &l, bool empty)
     {
-        const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
-        const float e0 = lo_raw * kK, o0 = hi_raw * kTwoInvK;
-        const float e1 = e0 + ((o0_prev + o0) * c1);
-        const float o1 = o0_prev + ((e1_prev + e1) * c2);
-        const float e2 = e1_prev + ((o1_prev + o1) * c3);
-        even = e2_prev;
-        odd = o1_prev + ((e2_prev + e2) * c4);
-        o0_prev = o0; e1_prev = e1; o1_prev = o1; e2_prev = e2;
+        o = io.out + (size_t) l.frame * io.out_frame;
+        col = 2u * (unsigned) l.i;
+        pair_io = (l.nh & 1) == 0 && ((size_t) o & 7) == 0 && (io.out_pitch & 1) == 0 && (io.out_frame & 1) == 0;
+        return !empty;
     }
-    // any position (the edges): the forms of ColPipe::step; has_even / has_odd say which of the two samples exist
-    __device__ void edge(int j, int sn, int dn, float lo_raw, float hi_raw, float &even, float &odd, bool &has_even, bool &has_odd)
+    __device__ void load(int, float &, float &, float &, float &) {}
+    __device__ void put(bool emit, int y, float ev, float od, float, float, bool has_odd_col)
     {
-        const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
-        float e1 = 0, o0 = 0;
-        if (j < sn) {
-            const float e0 = lo_raw * kK;
-            if (j < dn) o0 = hi_raw * kTwoInvK;
-            if (j < dn) e1 = e0 + (((j == 0 ? o0 : o0_prev) + o0) * c1);
-            else        e1 = e0 + (o0_prev * (c1 + c1));
+        if (!emit) return;
+        float *q = o + (size_t) ((unsigned) y * (unsigned) io.out_pitch + col);
+        if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{ev, od};
+        else { q[0] = ev; if (has_odd_col) q[1] = od; }
+    }
+    __device__ void end() {}
+};
+struct J2kSinkFrameTop {
+    J2kFinish fin;
+    const FrameState *fs;
+    const float *x;                // the frame (null: no statistics)
+    float *d;                      // the field (null: statistics only)
+    float mn, rng, target;
+    unsigned int limit, bad;
+    double acc;
+    size_t part;                   // this wave's partial sums
+    int lane, frame;
+    unsigned W, nv, col, c0, c1x, cp;
+    bool pair_io;
+    __device__ bool begin(const J2kStripLane &l, bool empty)
+    {
+        acc = 0; bad = 0; limit = 0;
+        lane = l.lane; frame = l.frame; W = (unsigned) l.W; nv = (unsigned) l.nv; col = 2u * (unsigned) l.i;
+        x = fin.data ? fin.data + (size_t) frame * l.n_pix : nullptr;
+        d = fin.field(frame, l.n_pix);
+        mn = fs[frame].minv; rng = fs[frame].maxv - fs[frame].minv;
+        target = x ? fin.jf[frame].target : 0.0f;
+        part = (size_t) frame * kPartials + (size_t) l.tile;
+        if (empty) {                                                    // (more pieces than positions: nothing to put out)
+            if (x && lane == 0) { fin.partial[part] = 0.0; fin.partial_u[part] = 0; }
+            return false;
         }
-        float o1 = 0;
-        const int i1 = j - 1;
-        if (i1 >= 0 && i1 < dn) o1 = (i1 + 1 < sn) ? o0_prev + ((e1_prev + e1) * c2) : o0_prev + (e1_prev * (c2 + c2));
-        float e2 = 0;
-        if (i1 >= 0 && i1 < sn) e2 = (i1 < dn) ? e1_prev + (((i1 == 0 ? o1 : o1_prev) + o1) * c3) : e1_prev + (o1_prev * (c3 + c3));
-        const int i2 = j - 2;
-        has_even = i2 >= 0 && i2 < sn; has_odd = i2 >= 0 && i2 < dn;
-        even = e2_prev;
-        odd = (i2 + 1 < sn) ? o1_prev + ((e2_prev + e2) * c4) : o1_prev + (e2_prev * (c4 + c4));
-        o0_prev = o0; e1_prev = e1; o1_prev = o1; e2_prev = e2;
+        // statistics-only probes of the rate search stop once the frame has gathered bad_limit samples above the target
+        // (J2kFrame::bad_limit): the pieces are dispatched piece-major over all frames, so the later pieces of a frame that
+        // is clearly infeasible at this rate leave without reading their strip.
+        // (the error sum is taken by every probe: a search's result often rests on a probe that was made to steer it - the final
+        //  probe of the pure base-layer search is normally one already on record)
+        if (x && !d) {
+            limit = fin.jf[frame].bad_limit;
+            if (limit && __hip_atomic_load(&fin.jf[frame].bad_seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) {
+                if (lane == 0) { fin.partial[part] = 0.0; fin.partial_u[part] = 0; }
+                return false;
+            }
+        }
+        c0 = (unsigned) min(max(2 * l.i, 0), l.nh - 1); c1x = (unsigned) min(max(2 * l.i + 1, 0), l.nh - 1);
+        // the 8-byte form reads columns (cp, cp + 1) of a row: the PAIR index is clamped, so that cp + 1 <= nh - 1 (nh is even
+        // there) - clamping the column instead would let an out-of-range halo lane read one sample past the end of the row,
+        // and on the last row of the last frame past the end of the caller's buffer
+        cp = 2u * (unsigned) min(max(l.i, 0), l.snh - 1);
+        // 8-byte accesses of the output pair and of the frame's samples beside it: even widths and 8-byte aligned bases
+        pair_io = (l.W & 1) == 0 && (l.nh & 1) == 0 && (l.n_pix & 1) == 0 && (((size_t) x | (size_t) d) & 7) == 0;
+        return true;
+    }
+    // rows 2 (j - 2) and the next, this pair's columns
+    __device__ void load(int j, float &x00, float &x01, float &x10, float &x11)
+    {
+        if (!x) return;
+        const unsigned y0 = (unsigned) min(max(2 * (j - 2), 0), (int) nv - 1), y1 = (unsigned) min(max(2 * (j - 2) + 1, 0), (int) nv - 1);
+        if (pair_io) {
+            const f32x2 a = *reinterpret_cast<const f32x2 *>(x + (y0 * W + cp)), c = *reinterpret_cast<const f32x2 *>(x + (y1 * W + cp));
+            x00 = a.x; x01 = a.y; x10 = c.x; x11 = c.y;
+        } else {
+            x00 = x[y0 * W + c0]; x01 = x[y0 * W + c1x]; x10 = x[y1 * W + c0]; x11 = x[y1 * W + c1x];
+        }
+    }
+    __device__ void put(bool emit, int y, float ev, float od, float xe, float xo, bool has_odd_col)
+    {
+        const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
+        if (d && emit) {
+            float *q = d + ((unsigned) y * W + col);
+            if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{de, dq};
+            else { q[0] = de; if (has_odd_col) q[1] = dq; }
+        }
+        if (x) {
+            const float e0 = xe - (de + 0.0f), e1 = xo - (dq + 0.0f);
+            const bool m0 = emit, m1 = emit && has_odd_col;
+            bad += (m0 && fabsf(e0) > target) ? 1u : 0u;
+            bad += (m1 && fabsf(e1) > target) ? 1u : 0u;
+            acc += m0 ? (double) e0 : 0.0; acc += m1 ? (double) e1 : 0.0;
+        }
+    }
+    __device__ void end()
+    {
+        if (!x) return;
+        for (int k = 32; k >= 1; k >>= 1) { acc += __shfl_xor(acc, k); bad += __shfl_xor(bad, k); }
+        if (lane == 0) {
+            fin.partial[part] = acc;
+            fin.partial_u[part] = bad;
+            if (limit && bad) atomicAdd(&fin.jf[frame].bad_seen, bad);
+        }
     }
 };
-template <bool FIN>
-__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
-                                                        const FrameState *fs, const int *active, J2kFinish fin, int strips, int n_frames, int pieces)
+struct J2kSinkWindowTop {
+    J2kWinOut win;
+    const FrameState *fs;
+    float *d;
+    float mn, rng;
+    int wx;                        // column 2i in the window
+    // 8-byte stores of a pair: a window of even position and width in an 8-byte aligned array (both samples of a pair are
+    // then inside the window or both outside)
+    bool pair_io;
+    __device__ bool begin(const J2kStripLane &l, bool empty)
+    {
+        d = win.out + (size_t) l.frame * ((size_t) win.rows * (size_t) win.cols);
+        mn = fs[l.frame].minv; rng = fs[l.frame].maxv - fs[l.frame].minv;
+        wx = 2 * l.i - win.col0;
+        pair_io = (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (l.nh & 1) == 0 && ((size_t) win.out & 7) == 0;
+        return !empty;
+    }
+    __device__ void load(int, float &, float &, float &, float &) {}
+    __device__ void put(bool emit, int y, float ev, float od, float, float, bool has_odd_col)
+    {
+        const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
+        const int wy = y - win.row0;
+        if (!emit || wy < 0 || wy >= win.rows) return;
+        float *q = d + (size_t) wy * (size_t) win.cols;
+        if (pair_io) { if (wx >= 0 && wx < win.cols) *reinterpret_cast<f32x2 *>(q + wx) = f32x2{de, dq}; }
+        else {
+            if (wx >= 0 && wx < win.cols) q[wx] = de;
+            if (has_odd_col && wx + 1 >= 0 && wx + 1 < win.cols) q[wx + 1] = dq;
+        }
+    }
+    __device__ void end() {}
+};
+
+// (io, range and sink by value: the compiler optimises this function on its own before it inlines it, and behind a reference
+//  they are memory that the pass's stores may alias - the whole-frame top level then takes 7 VGPRs more)
+template <class Sink>
+__device__ __forceinline__ void j2k_strip_pass(const J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom, const FrameState *fs,
+                                               const int *active, const int r, const J2kStripRange range, const int n_frames, Sink sink)
 {
-    // workgroup = the strips (up to 16, one per wave) of tile blockIdx.y = piece * n_frames + frame: piece-major, so that
-    // every frame's first pieces are dispatched first (the early exit below relies on that order for speed only)
-    const int lane = (int) threadIdx.x & 63, strip = (int) blockIdx.x * ((int) blockDim.x >> 6) + ((int) threadIdx.x >> 6);
+    // workgroup = neighbouring strips (up to 16, one per wave) of tile blockIdx.y = piece * n_frames + frame: piece-major, so
+    // that every frame's first pieces are dispatched first (J2kSinkFrameTop's early exit relies on that order for speed only)
+    const int lane = (int) threadIdx.x & 63, local = (int) blockIdx.x * ((int) blockDim.x >> 6) + ((int) threadIdx.x >> 6);
     const int frame = (int) blockIdx.y % n_frames, piece = (int) blockIdx.y / n_frames;
-    if (strip >= strips) return;                                        // (no barrier anywhere below)
+    if (local >= range.strips) return;                                  // (no barrier anywhere below)
     if ((active && !active[frame]) || (fs && fs[frame].const_field)) return;
+    const int strip = range.strip0 + local;
     const J2kGeom &g = j2k_frame_geom(geom, frame);
-    const int r = FIN ? kJ2kRes - 1 : io.r;
     const int W = g.W, nh = g.rw[r], snh = g.rw[r - 1], dnh = nh - snh;          // horizontal: samples, low-pass, high-pass
     const int nv = g.rh[r], snv = g.rh[r - 1], dnv = nv - snv;                   // vertical
     const size_t n_pix = (size_t) W * g.H;
@@ -700,11 +830,6 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO 
     const int32_t *v = V + (size_t) frame * n_pix;
     const float s_ll = 0.5f * g.bands[0].step_dec, s_hl = 0.5f * g.bands[3 * (r - 1) + 1].step_dec, s_lh = 0.5f * g.bands[3 * (r - 1) + 2].step_dec,
                 s_hh = 0.5f * g.bands[3 * (r - 1) + 3].step_dec;
-    const float *x = FIN && fin.data ? fin.data + (size_t) frame * n_pix : nullptr;
-    float *d = FIN ? fin.field(frame, n_pix) : nullptr;
-    float *o = FIN ? nullptr : io.out + (size_t) frame * io.out_frame;
-    const float mn = fs[frame].minv, rng = fs[frame].maxv - fs[frame].minv;
-    const float target = x ? fin.jf[frame].target : 0.0f;
     const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
     const bool first = i == 0, no_o = !(i < dnh), last_o = !(i + 1 < snh);
     // horizontal synthesis of one row: the pair's low-/high-pass inputs -> its two output samples (idwt_tile, cas 0)
@@ -720,44 +845,15 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO 
         even = e2;
         odd = last_o ? o1 + (e2 * (c4 + c4)) : o1 + ((e2 + e2r) * c4);
     };
-    const int per = ceil_div(snv, pieces), ja = piece * per, jb = min(snv, ja + per);
-    const size_t part = (size_t) frame * kPartials + (size_t) (strip + strips * piece);   // this wave's partial sums
-    if (ja >= jb) {                                                     // (more pieces than positions: nothing to put out)
-        if (FIN && x && lane == 0) { fin.partial[part] = 0.0; fin.partial_u[part] = 0; }
-        return;
-    }
+    const int pos1 = min(range.pos1, snv);
+    const int per = ceil_div(pos1 - range.pos0, range.pieces), ja = range.pos0 + piece * per, jb = min(pos1, ja + per);
+    if (!sink.begin(J2kStripLane{frame, lane, i, W, nh, snh, nv, n_pix, local + range.strips * piece}, ja >= jb)) return;
     const int jstart = max(ja - 2, 0);
-    // statistics-only probes of the rate search stop once the frame has gathered bad_limit samples above the target
-    // (J2kFrame::bad_limit): the pieces are dispatched piece-major over all frames, so the later pieces of a frame that
-    // is clearly infeasible at this rate leave without reading their strip.
-    unsigned int limit = 0;
-    // (the error sum is taken by every probe: a search's result often rests on a probe that was made to steer it - the final
-    //  probe of the pure base-layer search is normally one already on record)
-    const bool need_sum = true;
-    if constexpr (FIN) {
-        if (x && !d) {
-            limit = fin.jf[frame].bad_limit;
-            if (limit && __hip_atomic_load(&fin.jf[frame].bad_seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) {
-                if (lane == 0) { fin.partial[part] = 0.0; fin.partial_u[part] = 0; }
-                return;
-            }
-        }
-    }
-    double acc = 0;
-    unsigned int bad = 0;
-    ColPipe2 p0, p1;
+    ColPipe p0, p1;
     // every lane loads every step (halo and out-of-range lanes from clamped positions, their results are dropped), and
     // the inputs of step j + 1 are requested before step j is computed: no divergent control flow around the memory
     // accesses, one row of latency in flight.  32-bit offsets from uniform bases.
     const unsigned c_lo = (unsigned) min(max(i, 0), snh - 1), c_hi = (unsigned) snh + (unsigned) min(max(i, 0), max(dnh - 1, 0));
-    const unsigned c0 = (unsigned) min(max(2 * i, 0), nh - 1), c1x = (unsigned) min(max(2 * i + 1, 0), nh - 1);
-    // the 8-byte form reads columns (cp, cp + 1) of a row: the PAIR index is clamped, so that cp + 1 <= nh - 1 (nh is even
-    // there) - clamping the column instead would let an out-of-range halo lane read one sample past the end of the row,
-    // and on the last row of the last frame past the end of the caller's buffer
-    const unsigned cp = 2u * (unsigned) min(max(i, 0), snh - 1);
-    // 8-byte accesses of the output pair (and of the frame's samples beside it): even widths and 8-byte aligned bases
-    const bool pair_io = (W & 1) == 0 && (nh & 1) == 0 && (n_pix & 1) == 0 && (((size_t) x | (size_t) d | (size_t) o) & 7) == 0 &&
-                         (!FIN ? (io.out_pitch & 1) == 0 && (io.out_frame & 1) == 0 : true);
     float in_ll, in_hl, in_lh, in_hh;
     auto fetch = [&](int j, float &ll, float &hl, float &lh, float &hh) {
         const unsigned jl = (unsigned) min(j, snv - 1), jh = (unsigned) (snv + min(j, max(dnv - 1, 0)));
@@ -767,193 +863,56 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO 
         lh = (float) v[rh + c_lo] * s_lh;
         hh = (float) v[rh + c_hi] * s_hh;
     };
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    // what happens to the two finished samples (columns 2i, 2i + 1) of output row y
-    auto put_row = [&](bool emit, int y, float ev, float od, float xe, float xo, bool has_odd_col) {
-        if constexpr (!FIN) {
-            if (!emit) return;
-            float *q = o + (size_t) ((unsigned) y * (unsigned) io.out_pitch + 2u * (unsigned) i);
-            if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{ev, od};
-            else { q[0] = ev; if (has_odd_col) q[1] = od; }
-            return;
-        } else {
-            const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
-            if (d && emit) {
-                float *q = d + ((unsigned) y * (unsigned) W + 2u * (unsigned) i);
-                if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{de, dq};
-                else { q[0] = de; if (has_odd_col) q[1] = dq; }
-            }
-            if (x) {
-                const float e0 = xe - (de + 0.0f), e1 = xo - (dq + 0.0f);
-                const bool m0 = emit, m1 = emit && has_odd_col;
-                bad += (m0 && fabsf(e0) > target) ? 1u : 0u;
-                bad += (m1 && fabsf(e1) > target) ? 1u : 0u;
-                if (need_sum) { acc += m0 ? (double) e0 : 0.0; acc += m1 ? (double) e1 : 0.0; }
-            }
-        }
-    };
     fetch(jstart, in_ll, in_hl, in_lh, in_hh);
     for (int j = jstart; j < jb + 2; j++) {
         float n_ll, n_hl, n_lh, n_hh;
         fetch(j + 1, n_ll, n_hl, n_lh, n_hh);
-        // the frame's samples at the four positions this step puts out (rows 2 (j - 2) and the next, this pair's columns)
         float x00 = 0, x01 = 0, x10 = 0, x11 = 0;
-        if (x) {
-            const unsigned y0 = (unsigned) min(max(2 * (j - 2), 0), nv - 1), y1 = (unsigned) min(max(2 * (j - 2) + 1, 0), nv - 1);
-            if (pair_io) {
-                const f32x2 a = *reinterpret_cast<const f32x2 *>(x + (y0 * (unsigned) W + cp)), c = *reinterpret_cast<const f32x2 *>(x + (y1 * (unsigned) W + cp));
-                x00 = a.x; x01 = a.y; x10 = c.x; x11 = c.y;
-            } else {
-                x00 = x[y0 * (unsigned) W + c0]; x01 = x[y0 * (unsigned) W + c1x]; x10 = x[y1 * (unsigned) W + c0]; x11 = x[y1 * (unsigned) W + c1x];
-            }
-        }
+        sink.load(j, x00, x01, x10, x11);
         const bool emit = owner && j - 2 >= ja;                          // (positions before the piece belong to its neighbour)
         float lo_even = 0, lo_odd = 0, hi_even = 0, hi_odd = 0;
+        float a0, a1, b0, b1;                                            // column 2i: rows 2 (j - 2), 2 (j - 2) + 1; column 2i + 1
         if (j >= 2 && j < dnv) {                                         // (uniform) every vertical neighbour exists: no boundary forms
             hsynth(in_ll, in_hl, lo_even, lo_odd);                       // low-pass row j: LL from the previous level, HL from the decoder
             hsynth(in_lh, in_hh, hi_even, hi_odd);                       // high-pass row j: LH, HH
-            float a0, a1, b0, b1;
-            p0.interior(lo_even, hi_even, a0, a1);                       // column 2i: rows 2 (j - 2), 2 (j - 2) + 1
-            p1.interior(lo_odd, hi_odd, b0, b1);                         // column 2i + 1
-            put_row(emit, 2 * (j - 2), a0, b0, x00, x01, has_o);
-            put_row(emit, 2 * (j - 2) + 1, a1, b1, x10, x11, has_o);
-        } else {
-            if (j < snv) hsynth(in_ll, in_hl, lo_even, lo_odd);
-            if (j < dnv) hsynth(in_lh, in_hh, hi_even, hi_odd);
-            float a0, a1, b0, b1;
-            bool he, ho, he1, ho1;
-            p0.edge(j, snv, dnv, lo_even, hi_even, a0, a1, he, ho);
-            p1.edge(j, snv, dnv, lo_odd, hi_odd, b0, b1, he1, ho1);
-            // (he / ho are uniform: whether rows 2 (j - 2) and 2 (j - 2) + 1 exist)
-            if (he) put_row(emit, 2 * (j - 2), a0, b0, x00, x01, has_o);
-            if (ho) put_row(emit, 2 * (j - 2) + 1, a1, b1, x10, x11, has_o);
-            (void) he1; (void) ho1;
-        }
-        in_ll = n_ll; in_hl = n_hl; in_lh = n_lh; in_hh = n_hh;
-    }
-    if (x) {
-        for (int k = 32; k >= 1; k >>= 1) { acc += __shfl_xor(acc, k); bad += __shfl_xor(bad, k); }
-        if (lane == 0) {
-            fin.partial[part] = acc;
-            fin.partial_u[part] = bad;
-            if (limit && bad) atomicAdd(&fin.jf[frame].bad_seen, bad);
-        }
-    }
-}
-
-// Window decode (J2kWindow): the pass of k_j2k_level5_fin over the part of a level a window's dependency cone holds - the
-// strips strip0 .. strip0 + strips - 1 and the vertical positions [pos0, pos1) in `pieces` pieces - with the same expressions
-// in the same order at the same frame coordinates, so that every sample it puts out has the bits the whole-frame pass gives
-// it.  A piece starts its column pipelines two positions early (as the pieces of the whole-frame pass do) and a strip
-// carries two pairs of halo on either side; positions outside the frame take the boundary forms, positions outside the cone
-// are read from wherever the clamped index points and their results are dropped.  FIN: the field goes straight to the
-// caller's compact [frame][rows][cols] array - rows of any alignment, so single stores unless pairs happen to be aligned;
-// no statistics.  FIN = false: the level's output goes to `io.out` at its frame coordinates like the whole-frame pass.
-struct J2kWinOut { float *out; int row0, col0, rows, cols; };
-template <bool FIN>
-__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_win(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
-                                                                     const FrameState *fs, J2kWinOut win, int strip0, int strips, int n_frames,
-                                                                     int pieces, int pos0, int pos1)
-{
-    const int lane = (int) threadIdx.x & 63, local = (int) blockIdx.x * ((int) blockDim.x >> 6) + ((int) threadIdx.x >> 6);
-    const int frame = (int) blockIdx.y % n_frames, piece = (int) blockIdx.y / n_frames;
-    if (local >= strips) return;                                        // (no barrier anywhere below)
-    if (fs[frame].const_field) return;
-    const int strip = strip0 + local;
-    const J2kGeom &g = j2k_frame_geom(geom, frame);
-    const int r = FIN ? kJ2kRes - 1 : io.r;
-    const int W = g.W, nh = g.rw[r], snh = g.rw[r - 1], dnh = nh - snh;
-    const int nv = g.rh[r], snv = g.rh[r - 1], dnv = nv - snv;
-    const size_t n_pix = (size_t) W * g.H;
-    const int i = strip * kL5Pairs + lane - 2;
-    const bool has_e = i >= 0 && i < snh, has_o = i >= 0 && i < dnh;
-    const bool owner = lane >= 2 && lane < 2 + kL5Pairs && has_e;
-    const float *b = io.ll ? io.ll + (size_t) frame * io.ll_frame : nullptr;
-    const unsigned lp = (unsigned) io.ll_pitch;
-    const int32_t *v = V + (size_t) frame * n_pix;
-    const float s_ll = 0.5f * g.bands[0].step_dec, s_hl = 0.5f * g.bands[3 * (r - 1) + 1].step_dec, s_lh = 0.5f * g.bands[3 * (r - 1) + 2].step_dec,
-                s_hh = 0.5f * g.bands[3 * (r - 1) + 3].step_dec;
-    float *d = FIN ? win.out + (size_t) frame * ((size_t) win.rows * (size_t) win.cols) : nullptr;
-    float *o = FIN ? nullptr : io.out + (size_t) frame * io.out_frame;
-    const float mn = fs[frame].minv, rng = fs[frame].maxv - fs[frame].minv;
-    const float c1 = -kD, c2 = -kG, c3 = -kB, c4 = -kA;
-    const bool first = i == 0, no_o = !(i < dnh), last_o = !(i + 1 < snh);
-    auto hsynth = [&](float e_raw, float o_raw, float &even, float &odd) {
-        const float e0 = has_e ? e_raw * kK : 0.0f, o0 = has_o ? o_raw * kTwoInvK : 0.0f;
-        const float o0l = lane_below(o0);
-        const float e1 = no_o ? e0 + (o0l * (c1 + c1)) : e0 + (((first ? o0 : o0l) + o0) * c1);
-        const float e1r = lane_above(e1);
-        const float o1 = last_o ? o0 + (e1 * (c2 + c2)) : o0 + ((e1 + e1r) * c2);
-        const float o1l = lane_below(o1);
-        const float e2 = no_o ? e1 + (o1l * (c3 + c3)) : e1 + (((first ? o1 : o1l) + o1) * c3);
-        const float e2r = lane_above(e2);
-        even = e2;
-        odd = last_o ? o1 + (e2 * (c4 + c4)) : o1 + ((e2 + e2r) * c4);
-    };
-    const int per = ceil_div(pos1 - pos0, pieces), ja = pos0 + piece * per, jb = min(pos1, ja + per);
-    if (ja >= jb) return;
-    const int jstart = max(ja - 2, 0);
-    ColPipe2 p0, p1;
-    const unsigned c_lo = (unsigned) min(max(i, 0), snh - 1), c_hi = (unsigned) snh + (unsigned) min(max(i, 0), max(dnh - 1, 0));
-    // 8-byte stores of a pair: the whole-frame condition for a lower level; for the field, a window of even position and
-    // width in an 8-byte aligned array (both samples of a pair are then inside the window or both outside)
-    const bool pair_io = FIN ? (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (nh & 1) == 0 && ((size_t) win.out & 7) == 0
-                             : (nh & 1) == 0 && ((size_t) o & 7) == 0 && (io.out_pitch & 1) == 0 && (io.out_frame & 1) == 0;
-    float in_ll, in_hl, in_lh, in_hh;
-    auto fetch = [&](int j, float &ll, float &hl, float &lh, float &hh) {
-        const unsigned jl = (unsigned) min(j, snv - 1), jh = (unsigned) (snv + min(j, max(dnv - 1, 0)));
-        const unsigned rl = jl * (unsigned) W, rh = jh * (unsigned) W;
-        ll = b ? b[jl * lp + c_lo] : (float) v[rl + c_lo] * s_ll;
-        hl = (float) v[rl + c_hi] * s_hl;
-        lh = (float) v[rh + c_lo] * s_lh;
-        hh = (float) v[rh + c_hi] * s_hh;
-    };
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    auto put_row = [&](bool emit, int y, float ev, float od, bool has_odd_col) {
-        if constexpr (!FIN) {
-            if (!emit) return;
-            float *q = o + (size_t) ((unsigned) y * (unsigned) io.out_pitch + 2u * (unsigned) i);
-            if (pair_io) *reinterpret_cast<f32x2 *>(q) = f32x2{ev, od};
-            else { q[0] = ev; if (has_odd_col) q[1] = od; }
-        } else {
-            const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
-            const int wy = y - win.row0, wx = 2 * i - win.col0;         // position in the window
-            if (!emit || wy < 0 || wy >= win.rows) return;
-            float *q = d + (size_t) wy * (size_t) win.cols;
-            if (pair_io) { if (wx >= 0 && wx < win.cols) *reinterpret_cast<f32x2 *>(q + wx) = f32x2{de, dq}; }
-            else {
-                if (wx >= 0 && wx < win.cols) q[wx] = de;
-                if (has_odd_col && wx + 1 >= 0 && wx + 1 < win.cols) q[wx + 1] = dq;
-            }
-        }
-    };
-    fetch(jstart, in_ll, in_hl, in_lh, in_hh);
-    for (int j = jstart; j < jb + 2; j++) {
-        float n_ll, n_hl, n_lh, n_hh;
-        fetch(j + 1, n_ll, n_hl, n_lh, n_hh);
-        const bool emit = owner && j - 2 >= ja;
-        float lo_even = 0, lo_odd = 0, hi_even = 0, hi_odd = 0;
-        if (j >= 2 && j < dnv) {
-            hsynth(in_ll, in_hl, lo_even, lo_odd);
-            hsynth(in_lh, in_hh, hi_even, hi_odd);
-            float a0, a1, b0, b1;
             p0.interior(lo_even, hi_even, a0, a1);
             p1.interior(lo_odd, hi_odd, b0, b1);
-            put_row(emit, 2 * (j - 2), a0, b0, has_o);
-            put_row(emit, 2 * (j - 2) + 1, a1, b1, has_o);
+            sink.put(emit, 2 * (j - 2), a0, b0, x00, x01, has_o);
+            sink.put(emit, 2 * (j - 2) + 1, a1, b1, x10, x11, has_o);
         } else {
             if (j < snv) hsynth(in_ll, in_hl, lo_even, lo_odd);
             if (j < dnv) hsynth(in_lh, in_hh, hi_even, hi_odd);
-            float a0, a1, b0, b1;
-            bool he, ho, he1, ho1;
+            bool he, ho;                                                 // (uniform: whether rows 2 (j - 2) and 2 (j - 2) + 1 exist)
             p0.edge(j, snv, dnv, lo_even, hi_even, a0, a1, he, ho);
-            p1.edge(j, snv, dnv, lo_odd, hi_odd, b0, b1, he1, ho1);
-            if (he) put_row(emit, 2 * (j - 2), a0, b0, has_o);
-            if (ho) put_row(emit, 2 * (j - 2) + 1, a1, b1, has_o);
-            (void) he1; (void) ho1;
+            p1.edge(j, snv, dnv, lo_odd, hi_odd, b0, b1, he, ho);
+            if (he) sink.put(emit, 2 * (j - 2), a0, b0, x00, x01, has_o);
+            if (ho) sink.put(emit, 2 * (j - 2) + 1, a1, b1, x10, x11, has_o);
         }
         in_ll = n_ll; in_hl = n_hl; in_lh = n_lh; in_hh = n_hh;
     }
+    sink.end();
+}
+
+// FIN: the top level of the whole frame - always the whole level, so its range is one of compile-time constants and only
+// the strip and piece counts are taken from `range`.  FIN = false: level io.r over `range`.
+template <bool FIN>
+__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
+                                                        const FrameState *fs, const int *active, J2kFinish fin, J2kStripRange range, int n_frames)
+{
+    if constexpr (FIN) {
+        J2kSinkFrameTop sink{fin, fs};
+        j2k_strip_pass(io, V, geom, fs, active, kJ2kRes - 1, J2kStripRange{0, range.strips, 0, kToLevelEnd, range.pieces}, n_frames, sink);
+    } else {
+        J2kSinkNextLevel sink{io};
+        j2k_strip_pass(io, V, geom, fs, active, io.r, range, n_frames, sink);
+    }
+}
+// the top level of a window decode (every frame active)
+__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_win(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
+                                                                     const FrameState *fs, J2kWinOut win, J2kStripRange range, int n_frames)
+{
+    J2kSinkWindowTop sink{win, fs};
+    j2k_strip_pass(io, V, geom, fs, nullptr, kJ2kRes - 1, range, n_frames, sink);
 }
 
 template <typename K>
@@ -1876,12 +1835,13 @@ void launch_j2k_analysis(const float *data, const J2kBuffers &jb, int n_frames, 
 // field jb.DEC, with the error statistics against `data` (if given) left as partial sums per frame; used by both
 // decode flavours (j2k_rate.hip).  Returns the number of partials per frame.
 // `win` (decode only: no statistics, every frame active): the fused levels run over the window's dependency cone alone and the
-// top level writes the window of the field to win_out [n_frames][rows][cols] (k_j2k_level_win); lower levels that take the
+// top level writes the window of the field to win_out [n_frames][rows][cols] (J2kStripRange, k_j2k_level_win); lower levels that take the
 // separate passes run whole.  The top level has to be a fused one (j2k_window_supported).
 int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuffers &jb, int n_frames, const FrameState *fs,
                     const int *active, hipStream_t s, int keep_field, const J2kWindow *win, float *win_out)
 {
     int partials = 0;
+    const J2kFinish fin{data, keep_field ? jb.DEC : nullptr, jb.jf, jb.partial, jb.partial_u, keep_field == 2};
     // plain frames: every level in one fused pass (k_j2k_level5_fin: horizontal synthesis in registers, vertical register
     // pipeline), alternating between the tile buffer and jb.B2 from the first level that is large enough; the levels
     // below it and tiles at odd offsets use the separate LDS-staged row / column passes in place.
@@ -1898,50 +1858,41 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     float *spare = jb.B2;
     for (int r = 1; r < kJ2kRes; r++) {                                // opj_dwt_decode_tile_97: horizontal, then vertical
         if (r >= first_fused) {
-            const int strips = ceil_div(g.rw[r - 1], kL5Pairs);
+            const bool top = r == kJ2kRes - 1;
+            // the part of the level to run: all of it, or the strips and vertical positions that hold the window's cone
+            J2kStripRange range{0, ceil_div(g.rw[r - 1], kL5Pairs), 0, g.rh[r - 1], 1};
+            if (win) {
+                range.strip0 = (win->rx0[r] / 2) / kL5Pairs; range.strips = ((win->rx1[r] - 1) / 2) / kL5Pairs - range.strip0 + 1;
+                range.pos0 = win->ry0[r] / 2; range.pos1 = (win->ry1[r] - 1) / 2 + 1;
+            }
+            const int piece_cap = win ? kPartials : kPartials / range.strips;   // (whole frame: a statistics partial per strip and piece)
             // (the top level in more, shorter pieces: a piece is what an infeasible probe can skip)
-            int pieces = std::max(1, std::min({r == kJ2kRes - 1 ? 8 : 4, kPartials / strips, g.rh[r - 1] / 16}));
-            while (pieces > 1 && (long long) n_frames * pieces > 65535) pieces--;            // (grid y)
+            range.pieces = std::max(1, std::min({top ? 8 : 4, piece_cap, (range.pos1 - range.pos0) / 16}));
+            while (range.pieces > 1 && (long long) n_frames * range.pieces > 65535) range.pieces--;   // (grid y)
             // neighbouring strips of a tile as the waves of one workgroup, four at a time (measured per 128-frame probe round,
             // tools/gpu/kstat.sh: 1 wave 231 us, 4 waves 220, 6 waves 258, all 12 strips 264 - a large workgroup needs all
             // its wave slots free on one CU at once)
             const int wave_cap = 4;
-            const int wg = std::min(strips, wave_cap), groups = ceil_div(strips, wg);
+            const int wg = std::min(range.strips, wave_cap);
+            const dim3 grid((unsigned) ceil_div(range.strips, wg), (unsigned) (n_frames * range.pieces)), block(64 * wg);
             if (r > 1 && !ll) ll = B;                                   // (the separate passes below left their result in B)
             J2kLevelIO io{ll, g.W, n_pix, nullptr, g.W, n_pix, r};
-            if (win) {
-                // the strips and vertical positions that hold the cone's samples of this resolution
-                const int strip0 = (win->rx0[r] / 2) / kL5Pairs, wstrips = ((win->rx1[r] - 1) / 2) / kL5Pairs - strip0 + 1;
-                const int pos0 = win->ry0[r] / 2, pos1 = (win->ry1[r] - 1) / 2 + 1;
-                int wpieces = std::max(1, std::min(r == kJ2kRes - 1 ? 8 : 4, (pos1 - pos0) / 16));
-                while (wpieces > 1 && (long long) n_frames * wpieces > 65535) wpieces--;
-                const int wwg = std::min(wstrips, wave_cap), wgroups = ceil_div(wstrips, wwg);
-                const J2kWinOut wo{win_out, win->row0, win->col0, win->rows, win->cols};
-                if (r == kJ2kRes - 1) {
-                    hipLaunchKernelGGL(k_j2k_level_win<true>, dim3((unsigned) wgroups, (unsigned) (n_frames * wpieces)), dim3(64 * wwg), 0, s, io, V, jb.d_geom, fs, wo,
-                                       strip0, wstrips, n_frames, wpieces, pos0, pos1);
-                } else {
-                    io.out = ll == spare ? B : spare;
-                    hipLaunchKernelGGL(k_j2k_level_win<false>, dim3((unsigned) wgroups, (unsigned) (n_frames * wpieces)), dim3(64 * wwg), 0, s, io, V, jb.d_geom, fs, wo,
-                                       strip0, wstrips, n_frames, wpieces, pos0, pos1);
-                    ll = io.out;
-                }
-                continue;
-            }
-            if (r == kJ2kRes - 1) {
-                partials = strips * pieces;
-                hipLaunchKernelGGL(k_j2k_level5_fin<true>, dim3((unsigned) groups, (unsigned) (n_frames * pieces)), dim3(64 * wg), 0, s, io, V, jb.d_geom, fs, active,
-                                   J2kFinish{data, keep_field ? jb.DEC : nullptr, jb.jf, jb.partial, jb.partial_u, keep_field == 2}, strips, n_frames, pieces);
-            } else {
+            if (!top) {
                 io.out = ll == spare ? B : spare;                         // never the buffer the level reads from
-                hipLaunchKernelGGL(k_j2k_level5_fin<false>, dim3((unsigned) groups, (unsigned) (n_frames * pieces)), dim3(64 * wg), 0, s, io, V, jb.d_geom, fs, active, J2kFinish{}, strips, n_frames, pieces);
+                hipLaunchKernelGGL(k_j2k_level5_fin<false>, grid, block, 0, s, io, V, jb.d_geom, fs, active, J2kFinish{}, range, n_frames);
                 ll = io.out;
+            } else if (win) {
+                hipLaunchKernelGGL(k_j2k_level_win, grid, block, 0, s, io, V, jb.d_geom, fs, J2kWinOut{win_out, win->row0, win->col0, win->rows, win->cols},
+                                   range, n_frames);
+            } else {
+                partials = range.strips * range.pieces;
+                hipLaunchKernelGGL(k_j2k_level5_fin<true>, grid, block, 0, s, io, V, jb.d_geom, fs, active, fin, range, n_frames);
             }
             continue;
         }
         dwt_rows<false>(B, V, jb, r, n_frames, fs, active, s);
         if (r + 1 < kJ2kRes) dwt_cols<false>(B, jb, r, n_frames, fs, active, s);
-        else partials = dwt_cols<false, true>(B, jb, r, n_frames, fs, active, s, J2kFinish{data, keep_field ? jb.DEC : nullptr, jb.jf, jb.partial, jb.partial_u, keep_field == 2});
+        else partials = dwt_cols<false, true>(B, jb, r, n_frames, fs, active, s, fin);
     }
     EBCC_HIP_LAUNCH_CHECK();
     return partials;

@@ -129,10 +129,10 @@ void launch_synthesis(const ResidualBuffers &rb, int n_frames, const int *d_acti
 void launch_synthesis_stats(const float *data, const float *decoded, const ResidualBuffers &rb, int n_frames, const int *d_active,
                             hipStream_t s);
 void launch_synthesis_head(const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s);
-void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s);
-// _tail_add for the window [row0, row0 + rows) x [col0, col0 + cols) of the field alone; out: [n_frames][rows][cols]
-void launch_synthesis_tail_add_window(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
-                                      int rows, int cols);
+// the last row pass as field += residual for the box [row0, row0 + rows) x [col0, col0 + cols) of the field - all of it, or a
+// window; out: [n_frames][rows][cols]
+void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
+                               int rows, int cols);
 
 // plain spiht_decode output image in [0,1] (spiht_re.c:508-516) for the unit entry point
 void launch_emit_image(float *image_out, const ResidualBuffers &rb, int n_frames, hipStream_t s);

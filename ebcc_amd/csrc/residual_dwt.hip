@@ -172,14 +172,12 @@ __device__ inline float residual_value(float a, float dc, float rmin, float rng)
     return rn * rng + rmin;
 }
 
-// What the last synthesis pass does with its rows instead of storing the grid (k_rows_inv_use):
-//   statistics (data != nullptr): max |x - (decoded + r)| and the sum of x - (decoded + r) per frame
-//                                 (ebcc_codec.c:481,498), one partial sum per workgroup;
-//   addition   (data == nullptr): out += r (ebcc_codec.c:1307).
+// What the last synthesis pass of a probe does with its rows instead of storing the grid (k_rows_inv_use, k_finest_inv_use):
+// the statistics max |x - (decoded + r)| and the sum of x - (decoded + r) per frame (ebcc_codec.c:481,498), one partial sum
+// per workgroup.  (The decoder's last pass adds the rows to the field instead: k_rows_inv_add.)
 struct RowUse {
     const float *data;
-    const float *decoded;          // statistics: the base layer's field; addition: unused
-    float *out;                    // addition: the field the residual is added to
+    const float *decoded;          // the base layer's field
     int size_x, size_y;            // the image inside the padded grid
     size_t n_pix;
     FrameState *fs;
@@ -198,11 +196,8 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
     float *E = sm, *O = sm + half;
     src += (size_t) frame * frame_stride;
     const int tid = threadIdx.x;
-    const bool stats = u.data != nullptr;
-    const float *x = stats ? u.data + (size_t) frame * u.n_pix : nullptr;
-    const float *d = stats ? u.decoded + (size_t) frame * u.n_pix : nullptr;
-    float *o = stats ? nullptr : u.out + (size_t) frame * u.n_pix;
-    const float dc = stats ? u.fs[frame].dc : (float) u.fs[frame].dec_dc, rmin = u.fs[frame].rmin, rng = u.fs[frame].rmax - u.fs[frame].rmin;
+    const float *x = u.data + (size_t) frame * u.n_pix, *d = u.decoded + (size_t) frame * u.n_pix;
+    const float dc = u.fs[frame].dc, rmin = u.fs[frame].rmin, rng = u.fs[frame].rmax - u.fs[frame].rmin;
     double acc = 0;
     float mx = 0;
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
@@ -217,19 +212,14 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
             for (int xx = tid; xx < u.size_x; xx += kRowThreads) {
                 const float r = residual_value((xx & 1) ? O[xx >> 1] : E[xx >> 1], dc, rmin, rng);
                 const size_t i = (size_t) row * u.size_x + xx;
-                if (stats) {
-                    const float t = x[i] - (d[i] + r);
-                    acc += (double) t;
-                    const float e = fabsf(t);
-                    mx = e > mx ? e : mx;
-                } else {
-                    o[i] = o[i] + r;
-                }
+                const float t = x[i] - (d[i] + r);
+                acc += (double) t;
+                const float e = fabsf(t);
+                mx = e > mx ? e : mx;
             }
         }
         __syncthreads();
     }
-    if (!stats) return;
     for (int k = 32; k >= 1; k >>= 1) { acc += __shfl_xor(acc, k); mx = fmaxf(mx, __shfl_xor(mx, k)); }
     if ((tid & 63) == 0) { red[tid >> 6] = acc; redm[tid >> 6] = mx; }
     __syncthreads();
@@ -242,12 +232,13 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
     }
 }
 
-// The addition form of k_rows_inv_use for a window of the field (window decode): the rows [row0, row0 + rows) alone, each
-// synthesised whole (a row is one lifting chain; its samples outside the window are its halo), and out += r for the columns
-// [col0, col0 + cols), with `out` the compact [frame][rows][cols] array.  Same expressions as the whole-frame pass.
-__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_window(const float *__restrict__ src, int stride, size_t frame_stride, int n,
-                                                                      const int *active, const FrameState *fs, float *out, int row0, int col0,
-                                                                      int rows, int cols)
+// The decoder's last synthesis pass: out += r (ebcc_codec.c:1307) for the box [row0, row0 + rows) x [col0, col0 + cols) of the
+// image - all of it, or the window of a window decode - with `out` the compact [frame][rows][cols] array.  Only the box's rows
+// are synthesised, each of them whole (a row is one lifting chain; its samples outside the box are its halo), so a sample
+// has the same bits whatever the box.
+__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__restrict__ src, int stride, size_t frame_stride, int n,
+                                                               const int *active, const FrameState *fs, float *out, int row0, int col0,
+                                                               int rows, int cols)
 {
     extern __shared__ float sm[];
     const int frame = blockIdx.y;
@@ -1153,8 +1144,6 @@ void launch_synthesis(const ResidualBuffers &rb, int n_frames, const int *d_acti
     EBCC_HIP_LAUNCH_CHECK();
 }
 
-// the synthesis whose last row pass consumes the rows (RowUse) instead of storing the grid; returns the workgroups
-// per frame of that pass (= partial sums per frame)
 // every pass of the synthesis but the last row pass (result in rb.T)
 void launch_synthesis_head(const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s)
 {
@@ -1168,6 +1157,8 @@ void launch_synthesis_head(const ResidualBuffers &rb, int n_frames, const int *d
     EBCC_HIP_LAUNCH_CHECK();
 }
 
+// the last row pass as one that consumes the rows (RowUse) instead of storing the grid; returns its workgroups per frame
+// (= partial sums per frame)
 static int synthesis_tail(const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, RowUse u)
 {
     const Grid &g = rb.g;
@@ -1328,21 +1319,13 @@ void launch_prefix_synthesis_slots(const float *data, const float *decoded, cons
     EBCC_HIP_LAUNCH_CHECK();
 }
 
-// after launch_synthesis_head: the last row pass with out += residual (ebcc_codec.c:1307) instead of a stored grid
-void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s)
-{
-    RowUse u{};
-    u.out = out;
-    synthesis_tail(rb, n_frames, d_active, s, u);
-    EBCC_HIP_LAUNCH_CHECK();
-}
-
-// the same for the window [row0, row0 + rows) x [col0, col0 + cols) of the field; out: [n_frames][rows][cols]
-void launch_synthesis_tail_add_window(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
-                                      int rows, int cols)
+// after launch_synthesis_head: the last row pass with out += residual (ebcc_codec.c:1307) instead of a stored grid, for the
+// box [row0, row0 + rows) x [col0, col0 + cols) of the field (all of it, or a window); out: [n_frames][rows][cols]
+void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
+                               int rows, int cols)
 {
     const Grid &g = rb.g;
-    hipLaunchKernelGGL(k_rows_inv_add_window, dim3(min(rows, 96), n_frames), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
+    hipLaunchKernelGGL(k_rows_inv_add, dim3(min(rows, 96), n_frames), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
                        d_active, rb.fs, out, row0, col0, rows, cols);
     EBCC_HIP_LAUNCH_CHECK();
 }

@@ -56,6 +56,7 @@ def algo_bytes(kernel, rank, nkeys):
         return 8 * (NX >> lv) * (NY >> lv), f"level {3 - lv}: read + write {(NX >> lv)}x{(NY >> lv)} fp32"
     if k == "k_cols_inv_stream": return 12 * 3 * (NX * NY // 4) + 4 * (NX * NY // 4) + 4 * NX * NY, "finest level columns: three detail bands from the bookkeeping (coefficient + two ordinals), LL read, grid written"
     if k == "k_rows_inv_use": return 4 * NX * NY + 8 * PIX, "read the grid, the frame and the decoded field (statistics only)"
+    if k == "k_rows_inv_add": return 4 * NX * H + 8 * PIX, "read the image's rows of the grid, read and write the decoded field (field += residual)"
     if k == "k_truncate": return 8 * NX * NY, "read fp32 grid, write int32 coefficients"
     if k == "k_descmax":
         # one launch per level, coarsest parents last: level l reads the 2^-l x 2^-l grid of coefficients (or of maxima) and writes a quarter of it twice

@@ -1,7 +1,22 @@
 #!/bin/bash
-# VGPR / SGPR / scratch of the tier-1 kernels (development aid): tools/vgpr.sh
+# VGPR / SGPR / scratch / spills of the kernels whose name matches a pattern (development aid; needs no GPU):
+#   tools/vgpr.sh                                          the tier-1 kernels (t1_)
+#   tools/vgpr.sh 'j2k_level|j2k_cols_fin|rows_inv'        the fused inverse levels and the last residual row passes
+# Compiled with the Makefile's code-generation flags; run it at two commits to compare their register use.
+pat="${1:-t1_}"
 cd "$(dirname "$0")/../ebcc_amd/csrc"
-for f in j2k_analysis j2k_rate; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -I../../include -S --cuda-device-only -o /tmp/$f.s $f.hip 2>/dev/null
-  awk '/\.name:/{n=$2} /\.vgpr_count:/{v=$2} /\.sgpr_count:/{s=$2} /\.private_segment_fixed_size:/{p=$2} /\.vgpr_spill_count:/{ if (n ~ /t1_/) printf "%-28s vgpr %s sgpr %s scratch %s spill %s\n", substr(n, index(n,"k_t1"), 20), v, s, p, $2}' /tmp/$f.s
+HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
+filt="$(dirname "$HIPCC")/../llvm/bin/llvm-cxxfilt"
+[ -x "$filt" ] || filt=c++filt
+tmp=$(mktemp -d)
+trap 'rm -rf "$tmp"' EXIT
+for f in j2k_analysis j2k_rate residual_dwt; do
+  "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -I../../include -S --cuda-device-only -o "$tmp/$f.s" $f.hip 2>/dev/null
+  awk '/\.name:/{n=$2} /\.vgpr_count:/{v=$2} /\.sgpr_count:/{s=$2} /\.private_segment_fixed_size:/{p=$2} /\.vgpr_spill_count:/{print n, v, s, p, $2}' "$tmp/$f.s" |
+  while read -r n v s p sp; do
+    d=$("$filt" "$n")
+    [[ $d =~ k_[A-Za-z0-9_]+(\<[^\>]*\>)? ]] && d=${BASH_REMATCH[0]}
+    [[ $d =~ $pat ]] && printf "%-32s vgpr %s sgpr %s scratch %s spill %s\n" "$d" "$v" "$s" "$p" "$sp"
+  done
 done
+exit 0
