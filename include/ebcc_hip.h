@@ -10,6 +10,13 @@
  * Conventions: return 0 on success, non-zero on error (message on stderr); "d_" pointers are HIP
  * device pointers on the context's device; all other pointers are host memory; work is enqueued on
  * the context's stream and the call returns after the stream has been synchronised unless stated.
+ *
+ * Caller buffers: device and host frame pointers (d_frames, d_images, d_out, h_frames, ...) need 4-byte alignment only - a
+ * frame inside a larger tensor is passed as it lies.  Exactly [n_frames][height][width] floats are read from an input (it
+ * is never written) or written to an output: nothing in front of it, behind it, or behind frame n_frames of a partial
+ * batch is touched, also by a call that fails.  Results do not depend on the alignment; the kernels use wider accesses
+ * where base and frame size allow them, and a decode output on a 256-byte boundary is written directly instead of through
+ * one device-to-device copy of the batch.  (tests/test_caller_buffers_gpu.py)
  */
 #ifndef EBCC_HIP_H
 #define EBCC_HIP_H
