@@ -898,7 +898,7 @@ bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf)
 // tile-parts of one tiled codestream (reference :121-125) - and its residual layer one frame of `rctx` (== ctx for
 // one-frame chunks).
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, const DecodeWindow *win)
+                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, const DecodeWindow *win, const DecodeBoxes *boxes)
 {
     struct Release { SliceGate *g; ~Release() { if (g) g->release(); } } release_on_exit{next};
     ebcc_hip_ctx *const rc = rctx ? rctx : ctx;
@@ -922,7 +922,35 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
         int rect[4];
         for (size_t b = 0; b < blocks.size(); b++) keep[b] = j2k_window_keeps(g, blocks[b], cone, rect) ? 1 : 0;
     }
-    const size_t out_pix = win ? win->pixels() : n_pix;               // samples a chunk puts out
+    // box list: per frame, the union of the code-blocks its boxes hold; the entry table with what the caller says of a box
+    // (launch_j2k_box_levels adds slot and ranges)
+    J2kBoxList list{};
+    const size_t keep_row = boxes ? (size_t) g.nblocks : 0;            // (keep: one row per frame; a window: one row for all)
+    if (boxes) {
+        if (win || tiles != 1 || g.period != 1) { set_error("box decode: chunks of several frames are not supported"); return 1; }
+        std::vector<ebcc_hip_box> local(boxes->boxes, boxes->boxes + boxes->n);
+        for (ebcc_hip_box &b : local) b.frame -= boxes->frame0;
+        keep.resize(n * keep_row);
+        if (!j2k_boxes_check("box decode", g, n, local.data(), local.size(), boxes->rows, boxes->cols, keep.data())) return 1;
+        if (boxes->n > ctx->boxes_cap) {                               // grow (rare: sized by the longest list seen)
+            void *h_old = ctx->h_boxes, *d_old = ctx->d_boxes;
+            ctx->h_boxes = nullptr; ctx->d_boxes = nullptr; ctx->boxes_cap = 0;
+            if (h_old) hipHostFree(h_old);
+            if (d_old) hipFree(d_old);
+            const size_t cap = boxes->n + boxes->n / 2 + 64;
+            void *h_new = nullptr, *d_new = nullptr;
+            EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap * sizeof(J2kBoxEntry)));
+            const hipError_t e = device_malloc(&d_new, cap * sizeof(J2kBoxEntry));
+            if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
+            ctx->h_boxes = h_new; ctx->d_boxes = d_new; ctx->boxes_cap = cap;
+        }
+        list = J2kBoxList{static_cast<J2kBoxEntry *>(ctx->h_boxes), static_cast<J2kBoxEntry *>(ctx->d_boxes), boxes->n, (int) boxes->rows, (int) boxes->cols, d_out};
+        for (size_t e = 0; e < local.size(); e++) {
+            J2kBoxEntry &b = list.h_table[e];
+            b.frame = (int) local[e].frame; b.out = (int) e; b.row0 = (int) local[e].row0; b.col0 = (int) local[e].col0;
+        }
+    }
+    const size_t out_pix = win ? win->pixels() : boxes ? boxes->pixels() : n_pix;   // samples a chunk (a box) puts out
     int *const table = ctx->h_table;                                  // (pinned)
     const size_t table_ints = nt * (size_t) g.stride * 4;
     memset(table, 0, table_ints * sizeof(int));
@@ -975,8 +1003,9 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
         if (tiles == 1) {
             if (hd.tail_size > jb.stream_cap) { log_fatal("codestream larger than the device slot"); return false; }
             if (!j2k_parse_codestream(hd.tail, hd.tail_size, g, rows)) return false;
-            for (size_t b = 0; b < keep.size(); b++)                   // (window decode) a zeroed entry is a code-block without data
-                if (!keep[b]) rows[4 * b] = rows[4 * b + 1] = rows[4 * b + 2] = rows[4 * b + 3] = 0;
+            const uint8_t *const kept = keep.data() + c * keep_row;    // (window / box decode) a zeroed entry is a code-block without data
+            for (size_t b = 0; b < (keep.empty() ? (size_t) 0 : (size_t) g.nblocks); b++)
+                if (!kept[b]) rows[4 * b] = rows[4 * b + 1] = rows[4 * b + 2] = rows[4 * b + 3] = 0;
             piece[c] = hd.tail_size;
         } else {
             if (!j2k_parse_tiled(hd.tail, hd.tail_size, jb, (int) tiles, rows, &src_off[c * tiles], &piece[c * tiles])) {
@@ -1051,20 +1080,30 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     // field buffer and a 1 GB device-to-device copy per 256 frames only for an output that is not aligned the way the
     // engine's buffers are)
     // (a window always goes straight to the caller's compact array: its kernels store single samples where pairs are not aligned)
-    const bool direct = win || ((uintptr_t) d_out & 255u) == 0;
+    const bool direct = win || boxes || ((uintptr_t) d_out & 255u) == 0;
     J2kBuffers view = jb;
-    if (direct && !win) view.DEC = d_out;
-    launch_j2k_decode(view, (int) nt, s, table, win ? &cone : nullptr, win ? d_out : nullptr);
+    if (direct && !win && !boxes) view.DEC = d_out;
+    launch_j2k_decode(view, (int) nt, s, table, win ? &cone : nullptr, win ? d_out : nullptr, boxes ? &list : nullptr);
     if (next) { next->release(); release_on_exit.g = nullptr; }     // host parsing done, kernels queued
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
         // last row pass: field += residual (of a window: its rows alone)
-        if (win) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
+        if (boxes) launch_synthesis_tail_add_boxes(d_out, rc->rb, list.table, list.n, rc->d_active, s, list.rows, list.cols);
+        else if (win) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
         else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s, 0, 0, rc->rb.g.size_y, rc->rb.g.size_x);
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
     // constant chunks: fill on the host side of the copy (rare path)
-    for (size_t c = 0; c < n; c++)
+    // (a box list: one host image per constant frame, kept until the one wait below, whatever the number of its boxes)
+    std::vector<std::vector<float>> fills;
+    for (size_t e = 0, last = (size_t) -1; boxes && e < list.n; e++) {
+        const size_t f = (size_t) list.h_table[e].frame;
+        if (!rc->h_fs[f].const_field) continue;
+        if (f != last) { fills.emplace_back(out_pix, rc->h_fs[f].minv); last = f; }      // (the boxes are in the order of their frames)
+        EBCC_HIP_CHECK(hipMemcpyAsync(d_out + e * out_pix, fills.back().data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    if (!fills.empty()) wait_stream(s);
+    for (size_t c = 0; c < n && !boxes; c++)
         if (rc->h_fs[c].const_field) {
             std::vector<float> v(out_pix, rc->h_fs[c].minv);
             EBCC_HIP_CHECK(hipMemcpyAsync(d_out + c * out_pix, v.data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));

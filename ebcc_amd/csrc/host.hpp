@@ -286,8 +286,24 @@ struct DecodeWindow {
     size_t row0, col0, rows, cols;
     size_t pixels() const { return rows * cols; }
 };
+// `boxes` (one-frame chunks only, instead of `win`): a box list - boxes of rows x cols in non-decreasing order of their frames,
+// which count from the batch's stream `frame0`; every stream of the batch is named by a box; d_out [n][rows][cols], box e
+// at index e.  part(lo, cnt): the boxes of the streams lo .. lo + cnt - 1 of the batch, as the list of that part.
+struct DecodeBoxes {
+    const ebcc_hip_box *boxes;
+    size_t n, rows, cols, frame0;
+    size_t pixels() const { return rows * cols; }
+    DecodeBoxes part(size_t lo, size_t cnt, size_t *first = nullptr) const
+    {
+        auto before = [](const ebcc_hip_box &x, size_t frame) { return x.frame < frame; };     // (the list is sorted by frame)
+        const size_t a = (size_t) (std::lower_bound(boxes, boxes + n, frame0 + lo, before) - boxes);
+        const size_t b = (size_t) (std::lower_bound(boxes + a, boxes + n, frame0 + lo + cnt, before) - boxes);
+        if (first) *first = a;
+        return DecodeBoxes{boxes + a, b - a, rows, cols, frame0 + lo};
+    }
+};
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out, SliceGate *next = nullptr,
-                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, const DecodeWindow *win = nullptr);
+                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr);
 // chunks of several frames (one tiled codestream per chunk): frame heights such a chunk can have, and heights for which
 // every tile has the geometry of a tile at the origin
 bool tile_height_supported(size_t h);

@@ -380,11 +380,18 @@ int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,
 // the decode counterpart (decode overlaps its two layers on the engine's two streams, decode_batch; a second slice hides
 // the host side - parsing, zstd, uploads - of one half behind the kernels of the other when there are hardware queues
 // for four streams)
-// (`win`: the frames' window alone, d_out [n_frames][rows][cols])
-int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeWindow *win = nullptr)
+// (`win`: the frames' window alone, d_out [n_frames][rows][cols]; `boxes`: the boxes of a box list, d_out [boxes][rows][cols] -
+//  they are in the order of their frames, so a slice's boxes are a contiguous part of the list and of the output)
+int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeWindow *win = nullptr,
+                      const DecodeBoxes *boxes = nullptr)
 {
     const size_t n_pix = win ? win->pixels() : ctx->n_pix;
     return run_slices(ctx, n_frames, [&](ebcc_hip_ctx *c, size_t lo, size_t cnt, SliceGate *next, unsigned) {
+        if (boxes) {
+            size_t first = 0;
+            const DecodeBoxes part = boxes->part(lo, cnt, &first);
+            return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + first * boxes->pixels(), next, 1, nullptr, nullptr, &part);
+        }
         return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + lo * n_pix, next, 1, nullptr, win);
     }, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);
 }
@@ -532,19 +539,27 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 // Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
 // `win` (one-frame chunks): the frames' window alone - `out` is [n][rows][cols], and only that crosses to the host.
 int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
-                   float *out, Prefault *prefault, const DecodeWindow *win = nullptr)
+                   float *out, Prefault *prefault, const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr)
 {
-    const size_t n_pix = win ? win->pixels() : ctx->n_pix * tiles;
+    const size_t n_pix = win ? win->pixels() : boxes ? boxes->pixels() : ctx->n_pix * tiles;
+    // (`boxes`, one-frame chunks: `out` is [boxes][rows][cols]; a batch's boxes are a contiguous part of it, and the device image
+    //  holds the most boxes any batch has)
+    size_t most = cap;
+    for (size_t lo = 0; boxes && lo < n; lo += cap) most = std::max(most, boxes->part(lo, std::min(cap, n - lo)).n);
     auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
         PhaseTimer pt;
-        float *d = io_buffer(set, cap * n_pix * sizeof(float));
+        size_t first = lo, count = k;
+        DecodeBoxes part{};
+        if (boxes) { part = boxes->part(lo, k, &first); count = part.n; }
+        float *d = io_buffer(set, most * n_pix * sizeof(float));
         pt.mark("host decode: device image");
-        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, win) : run_decode_slices(set, streams + lo, sizes + lo, k, d, win);
+        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, win)
+                                : run_decode_slices(set, streams + lo, sizes + lo, k, d, win, boxes ? &part : nullptr);
         if (r) return r;
         pt.mark("host decode: decode");
         if (prefault) prefault->join();
         pt.mark("host decode: output pages");
-        copy_pageable(set, out + lo * n_pix, d, k * n_pix * sizeof(float), true);
+        copy_pageable(set, out + first * n_pix, d, count * n_pix * sizeof(float), true);
         pt.mark("host decode: download");
         return 0;
     };
@@ -625,12 +640,17 @@ int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, s
     });
 }
 int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                    const DecodeWindow *win = nullptr)
+                    const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr)
 {
     if (!ctx || !streams || !sizes || !d_out || n < 1) { set_error("%s: bad arguments", who); return 1; }
     const size_t out_pix = win ? win->pixels() : ctx->n_pix;
     return on_codec(ctx->device, 1, [&] {
         return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            if (boxes) {
+                size_t first = 0;
+                const DecodeBoxes part = boxes->part(lo, k, &first);
+                return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + first * boxes->pixels(), nullptr, &part);
+            }
             return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + lo * out_pix, win);
         });
     });
@@ -646,6 +666,30 @@ bool window_of(const char *who, const ebcc_hip_ctx *ctx, size_t row0, size_t col
         return false;
     }
     w = DecodeWindow{row0, col0, rows, cols};
+    return true;
+}
+
+// The box list of a box-list entry point, checked against the context's frames before anything runs (nothing is written for
+// a list that is refused), and the call it stands for: the streams of the frames the boxes name, in their order, with the
+// boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
+struct BoxCall {
+    std::vector<const uint8_t *> streams;
+    std::vector<size_t> sizes;
+    std::vector<ebcc_hip_box> boxes;
+    DecodeBoxes list{};
+};
+bool boxes_of(const char *who, const ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
+              size_t n_boxes, size_t rows, size_t cols, const void *out, BoxCall &call)
+{
+    if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return false; }
+    if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return false; }
+    if (!j2k_boxes_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, boxes, n_boxes, rows, cols)) return false;
+    call.boxes.assign(boxes, boxes + n_boxes);
+    for (size_t e = 0; e < n_boxes; e++) {
+        if (e == 0 || boxes[e].frame != boxes[e - 1].frame) { call.streams.push_back(streams[boxes[e].frame]); call.sizes.push_back(sizes[boxes[e].frame]); }
+        call.boxes[e].frame = call.streams.size() - 1;
+    }
+    call.list = DecodeBoxes{call.boxes.data(), n_boxes, rows, cols, 0};
     return true;
 }
 
@@ -807,6 +851,40 @@ int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *
         Prefault prefault(h_out, n_frames * w.pixels() * sizeof(float));
         return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_out, &prefault, &w);
     });
+}
+
+// Box-list decode: boxes of rows x cols, each from the frame it names, bit for bit the crops of what the entry points without
+// boxes give; output [n_boxes][rows][cols].  The named frames are decoded as the batches of a call of their own (BoxCall).
+int ebcc_hip_decode_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
+                                 size_t n_boxes, size_t rows, size_t cols, float *d_out)
+{
+    EBCC_API_TRY
+    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames_boxes: bad batch"); return 1; }
+    BoxCall call;
+    if (!boxes_of("ebcc_hip_decode_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, call)) return 1;
+    return decode_resident("ebcc_hip_decode_frames_boxes", ctx, call.streams.data(), call.sizes.data(), call.streams.size(), d_out, nullptr, &call.list);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_decode_shard_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
+                                size_t n_boxes, size_t rows, size_t cols, float *d_out)
+{
+    EBCC_API_TRY
+    BoxCall call;
+    if (!boxes_of("ebcc_hip_decode_shard_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, call)) return 1;
+    return decode_resident("ebcc_hip_decode_shard_boxes", ctx, call.streams.data(), call.sizes.data(), call.streams.size(), d_out, nullptr, &call.list);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
+                                      size_t n_boxes, size_t rows, size_t cols, float *h_out)
+{
+    EBCC_API_TRY
+    BoxCall call;
+    if (!boxes_of("ebcc_hip_decode_host_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, h_out, call)) return 1;
+    return on_codec(ctx->device, 1, [&] {
+        Prefault prefault(h_out, n_boxes * call.list.pixels() * sizeof(float));
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, call.streams.data(), call.sizes.data(), call.streams.size(), h_out, &prefault, nullptr, &call.list);
+    });
+    EBCC_API_CATCH(1)
 }
 
 // The engines the reference-compatible entry points keep between calls (one per device and frame geometry, with their slice

@@ -404,11 +404,61 @@ bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, i
     return n[0] < n[1] && n[2] < n[3] && rect[0] < n[1] && n[0] < rect[1] && rect[2] < n[3] && n[2] < rect[3];
 }
 
+bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
+                     uint8_t *keep)
+{
+    const size_t H = (size_t) g.H, W = (size_t) g.W;
+    if (!boxes || n_boxes < 1 || rows < 1 || cols < 1) { set_error("%s: an empty box list or empty boxes", who); return false; }
+    if (!j2k_window_supported(g)) { set_error("%s: frames of %d x %d are not supported (fewer than 3 columns)", who, g.H, g.W); return false; }
+    if (rows > H || cols > W) { set_error("%s: boxes of %zu x %zu are not inside the %zu x %zu frame", who, rows, cols, H, W); return false; }
+    for (size_t e = 0; e < n_boxes; e++) {
+        const ebcc_hip_box &b = boxes[e];
+        if (b.frame >= n_frames) { set_error("%s: box %zu names frame %zu of %zu", who, e, b.frame, n_frames); return false; }
+        if (e && b.frame < boxes[e - 1].frame) { set_error("%s: box %zu: the boxes are not in the order of their frames", who, e); return false; }
+        if (b.row0 > H - rows || b.col0 > W - cols) {                   // (no sums: they may overflow)
+            set_error("%s: box %zu, [%zu, +%zu) x [%zu, +%zu), is not inside the %zu x %zu frame", who, e, b.row0, rows, b.col0, cols, H, W);
+            return false;
+        }
+    }
+    if (!keep) return true;
+    std::vector<J2kBlock> blk;
+    make_j2k_geom(g.H, g.W, blk);
+    memset(keep, 0, n_frames * blk.size());
+    for (size_t e = 0; e < n_boxes; e++) {
+        const ebcc_hip_box &b = boxes[e];
+        if (e && b.frame == boxes[e - 1].frame && b.row0 == boxes[e - 1].row0 && b.col0 == boxes[e - 1].col0) continue;   // (a repeat)
+        J2kWindow w;
+        if (!j2k_window_plan(g, b.row0, b.col0, rows, cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
+        uint8_t *row = keep + b.frame * blk.size();
+        int rect[4];
+        for (size_t i = 0; i < blk.size(); i++)
+            if (!row[i] && j2k_window_keeps(g, blk[i], w, rect)) row[i] = 1;
+    }
+    return true;
+}
+
 }  // namespace ebcc
 
 using namespace ebcc;
 
 extern "C" {
+
+// The code-blocks a box-list decode needs (include/ebcc_hip.h; host only, no device work).
+__attribute__((visibility("default"))) int ebcc_hip_boxes_plan(size_t height, size_t width, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes,
+                                                               size_t rows, size_t cols, uint8_t *keep, size_t max_blocks)
+{
+    EBCC_API_TRY
+    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("ebcc_hip_boxes_plan: bad geometry"); return -1; }
+    std::vector<J2kBlock> blk;
+    J2kGeom g = make_j2k_geom((int) height, (int) width, blk);
+    g.period = 1; g.stride = g.nblocks;
+    if (keep && max_blocks < blk.size()) { set_error("ebcc_hip_boxes_plan: keep has room for %zu of %zu code-blocks a frame", max_blocks, blk.size()); return -1; }
+    std::vector<uint8_t> flags(keep ? n_frames * blk.size() : 0);      // (keep is not written by a call that refuses)
+    if (!j2k_boxes_check("ebcc_hip_boxes_plan", g, n_frames, boxes, n_boxes, rows, cols, keep ? flags.data() : nullptr)) return -1;
+    if (keep) memcpy(keep, flags.data(), flags.size());
+    return g.nblocks;
+    EBCC_API_CATCH(-1)
+}
 
 // The code-blocks a window decode needs (include/ebcc_hip.h; host only, no device work).
 __attribute__((visibility("default"))) int ebcc_hip_window_plan(size_t height, size_t width, size_t row0, size_t col0, size_t rows, size_t cols,

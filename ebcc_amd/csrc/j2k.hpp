@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "../../include/ebcc_hip.h"
 #include "common.hpp"
 #include "residual.hpp"
 
@@ -198,6 +199,27 @@ bool j2k_window_plan(const J2kGeom &g, size_t row0, size_t col0, size_t rows, si
 bool j2k_window_supported(const J2kGeom &g);    // frames a window decode takes (j2k_analysis.hip)
 // the code-block's rectangle {x0, x1, y0, y1} in its sub-band's coordinates; true if it meets the band's needed rectangle
 bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, int rect[4]);
+// Box-list decode: boxes of one size, each cut from the frame it names (j2k_analysis.hip: launch_j2k_box_levels).  A record of
+// the device table is one box of the current round: the frame its code-blocks were decoded for, the slot of jb.B2 that holds
+// its intermediate low-pass bands, its index in the caller's [n_boxes][rows][cols] array, its origin, and for every level the
+// strips and vertical positions its dependency cone holds (J2kStripRange without the piece count, which is the launch's).
+struct J2kBoxEntry {
+    int frame, slot, out, row0, col0;
+    int strip0[kJ2kRes], strips[kJ2kRes], pos0[kJ2kRes], pos1[kJ2kRes];
+    int pad[3];
+};
+// the boxes of a batch (host): entry[e] with frame, out, row0, col0 set, in any order of frames; `table` / `h_table`: device
+// and pinned room for `n` records
+struct J2kBoxList {
+    J2kBoxEntry *h_table, *table;
+    size_t n;
+    int rows, cols;
+    float *out;
+};
+// the box list of a box-list entry point against frames of geometry g (include/ebcc_hip.h); false: refused, message set.
+// keep (may be null): [n_frames][g.nblocks], row f the OR of j2k_window_keeps over the boxes of frame f
+bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
+                     uint8_t *keep = nullptr);
 int j2k_selfcheck_div65535();   // mismatches of the division-free s / 65535.0f of the fused inverse level (0 expected)
 
 // ---- launchers (asynchronous on s) ---------------------------------------------------------------
@@ -231,8 +253,12 @@ void launch_j2k_probe_decode(const float *data, const J2kBuffers &jb, int n_fram
 // which the launch sizes its waves (null: the fixed tiers tuned for 256 frames)
 // `win`: only the window of the field, to win_out [n_frames][rows][cols] (jb.dec_table with the entries outside the window's
 // cone zeroed; host_table must be given; j2k_window_supported geometries); jb.DEC is not written
+// `boxes` (instead of `win`): the boxes of a box list, each from the frame it names, to boxes->out [n][rows][cols]; the table
+// entries outside the union of the cones of a frame's boxes have been zeroed
 void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kWindow *win = nullptr,
-                       float *win_out = nullptr);
+                       float *win_out = nullptr, const J2kBoxList *boxes = nullptr);
+// the inverse levels of a box list over the tier-1 decoder's output jb.V (j2k_analysis.hip)
+void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &boxes, hipStream_t s);
 void plan_decode_lanes(const int *host_table, int total, int out[4]);   // (what launch_j2k_decode chooses; ebcc_hip_plan_decode_lanes)
 
 }  // namespace ebcc

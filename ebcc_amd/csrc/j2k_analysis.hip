@@ -640,7 +640,18 @@ constexpr int kToLevelEnd = 0x7fffffff;                  // pos1 of a range that
 struct J2kWinOut { float *out; int row0, col0, rows, cols; };
 // what a sink is told about its lane: the pair i (columns 2i, 2i + 1) of frame `frame`, the level's extent, and the
 // wave's number among the launch's (strip, piece) tiles of the frame
-struct J2kStripLane { int frame, lane, i, W, nh, snh, nv; size_t n_pix; int tile; };
+struct J2kStripLane { int frame, slot, lane, i, W, nh, snh, nv; size_t n_pix; int tile; };
+// where a workgroup's tile is: the frame whose coefficients it reads (V, fs, geometry), its vertical piece, and which frame-sized
+// slots of io.ll / io.out hold its low-pass input / its output.  Whole frames and uniform windows: all three are the frame
+// (j2k_tile_of_frame); a box of a box list: the record of its entry (k_j2k_level_box).
+struct J2kStripTile { int frame, piece, ll_at, slot; };
+__device__ __forceinline__ J2kStripTile j2k_tile_of_frame(int n_frames)
+{
+    // tile blockIdx.y = piece * n_frames + frame: piece-major, so that every frame's first pieces are dispatched first
+    // (J2kSinkFrameTop's early exit relies on that order for speed only)
+    const int frame = (int) blockIdx.y % n_frames, piece = (int) blockIdx.y / n_frames;
+    return J2kStripTile{frame, piece, frame, frame};
+}
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // s / 65535.0f for an integer-valued s in [0, 65535], without the division: K_hi + K_lo = 1 / 65535 to 2^-49, one rounding
 // at the end; the quotient's binary expansion repeats with period 16, so it is never within 2^-40 of a rounding boundary.
@@ -672,7 +683,7 @@ struct J2kSinkNextLevel {
     bool pair_io;                  // 8-byte stores of the pair: even widths and 8-byte aligned bases
     __device__ bool begin(const J2kStripLane &l, bool empty)
     {
-        o = io.out + (size_t) l.frame * io.out_frame;
+        o = io.out + (size_t) l.slot * io.out_frame;
         col = 2u * (unsigned) l.i;
         pair_io = (l.nh & 1) == 0 && ((size_t) o & 7) == 0 && (io.out_pitch & 1) == 0 && (io.out_frame & 1) == 0;
         return !empty;
@@ -804,17 +815,29 @@ struct J2kSinkWindowTop {
     }
     __device__ void end() {}
 };
+// the top level of one box of a box list: J2kSinkWindowTop with the box's own origin, at index `out_index` of the caller's
+// [n_boxes][rows][cols] array (the 8-byte form is decided per box)
+struct J2kSinkBoxTop : J2kSinkWindowTop {
+    int out_index;
+    __device__ bool begin(const J2kStripLane &l, bool empty)
+    {
+        d = win.out + (size_t) out_index * ((size_t) win.rows * (size_t) win.cols);
+        mn = fs[l.frame].minv; rng = fs[l.frame].maxv - fs[l.frame].minv;
+        wx = 2 * l.i - win.col0;
+        pair_io = (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (l.nh & 1) == 0 && ((size_t) d & 7) == 0;
+        return !empty;
+    }
+};
 
 // (io, range and sink by value: the compiler optimises this function on its own before it inlines it, and behind a reference
 //  they are memory that the pass's stores may alias - the whole-frame top level then takes 7 VGPRs more)
 template <class Sink>
 __device__ __forceinline__ void j2k_strip_pass(const J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom, const FrameState *fs,
-                                               const int *active, const int r, const J2kStripRange range, const int n_frames, Sink sink)
+                                               const int *active, const int r, const J2kStripRange range, const J2kStripTile tile, Sink sink)
 {
-    // workgroup = neighbouring strips (up to 16, one per wave) of tile blockIdx.y = piece * n_frames + frame: piece-major, so
-    // that every frame's first pieces are dispatched first (J2kSinkFrameTop's early exit relies on that order for speed only)
+    // workgroup = neighbouring strips (up to 16, one per wave) of one tile (J2kStripTile)
     const int lane = (int) threadIdx.x & 63, local = (int) blockIdx.x * ((int) blockDim.x >> 6) + ((int) threadIdx.x >> 6);
-    const int frame = (int) blockIdx.y % n_frames, piece = (int) blockIdx.y / n_frames;
+    const int frame = tile.frame, piece = tile.piece;
     if (local >= range.strips) return;                                  // (no barrier anywhere below)
     if ((active && !active[frame]) || (fs && fs[frame].const_field)) return;
     const int strip = range.strip0 + local;
@@ -825,7 +848,7 @@ __device__ __forceinline__ void j2k_strip_pass(const J2kLevelIO io, const int32_
     const int i = strip * kL5Pairs + lane - 2;                                   // this lane's pair
     const bool has_e = i >= 0 && i < snh, has_o = i >= 0 && i < dnh;
     const bool owner = lane >= 2 && lane < 2 + kL5Pairs && has_e;                // (halo lanes compute, owners put out)
-    const float *b = io.ll ? io.ll + (size_t) frame * io.ll_frame : nullptr;
+    const float *b = io.ll ? io.ll + (size_t) tile.ll_at * io.ll_frame : nullptr;
     const unsigned lp = (unsigned) io.ll_pitch;
     const int32_t *v = V + (size_t) frame * n_pix;
     const float s_ll = 0.5f * g.bands[0].step_dec, s_hl = 0.5f * g.bands[3 * (r - 1) + 1].step_dec, s_lh = 0.5f * g.bands[3 * (r - 1) + 2].step_dec,
@@ -847,7 +870,7 @@ __device__ __forceinline__ void j2k_strip_pass(const J2kLevelIO io, const int32_
     };
     const int pos1 = min(range.pos1, snv);
     const int per = ceil_div(pos1 - range.pos0, range.pieces), ja = range.pos0 + piece * per, jb = min(pos1, ja + per);
-    if (!sink.begin(J2kStripLane{frame, lane, i, W, nh, snh, nv, n_pix, local + range.strips * piece}, ja >= jb)) return;
+    if (!sink.begin(J2kStripLane{frame, tile.slot, lane, i, W, nh, snh, nv, n_pix, local + range.strips * piece}, ja >= jb)) return;
     const int jstart = max(ja - 2, 0);
     ColPipe p0, p1;
     // every lane loads every step (halo and out-of-range lanes from clamped positions, their results are dropped), and
@@ -901,10 +924,10 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level5_fin(J2kLevelIO 
 {
     if constexpr (FIN) {
         J2kSinkFrameTop sink{fin, fs};
-        j2k_strip_pass(io, V, geom, fs, active, kJ2kRes - 1, J2kStripRange{0, range.strips, 0, kToLevelEnd, range.pieces}, n_frames, sink);
+        j2k_strip_pass(io, V, geom, fs, active, kJ2kRes - 1, J2kStripRange{0, range.strips, 0, kToLevelEnd, range.pieces}, j2k_tile_of_frame(n_frames), sink);
     } else {
         J2kSinkNextLevel sink{io};
-        j2k_strip_pass(io, V, geom, fs, active, io.r, range, n_frames, sink);
+        j2k_strip_pass(io, V, geom, fs, active, io.r, range, j2k_tile_of_frame(n_frames), sink);
     }
 }
 // the top level of a window decode (every frame active)
@@ -912,7 +935,30 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_win(J2kLevelIO i
                                                                      const FrameState *fs, J2kWinOut win, J2kStripRange range, int n_frames)
 {
     J2kSinkWindowTop sink{win, fs};
-    j2k_strip_pass(io, V, geom, fs, nullptr, kJ2kRes - 1, range, n_frames, sink);
+    j2k_strip_pass(io, V, geom, fs, nullptr, kJ2kRes - 1, range, j2k_tile_of_frame(n_frames), sink);
+}
+// Level io.r of the boxes of one round of a box list (launch_j2k_box_levels): tile blockIdx.y = piece * n_entries + entry, and
+// the entry's record (uniform loads) says which frame it reads, which strips and positions its cone holds at this level and
+// where its bands live.  The grid is sized for the round's largest strip count and `pieces` is the launch's: an entry with
+// fewer strips leaves at the strip pass's first test, one with fewer positions has empty pieces.  TOP: the field's box to
+// `out`; else the level's samples to the entry's slot of io.out.  ll_by_frame: io.ll is the frames' buffer (the band the
+// separate passes left, shared by every box of the frame), not the entries'.
+template <bool TOP>
+__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_box(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
+                                                                     const FrameState *fs, const J2kBoxEntry *__restrict__ entries, int n_entries,
+                                                                     int pieces, int ll_by_frame, float *out, int rows, int cols)
+{
+    const J2kBoxEntry &e = entries[(int) blockIdx.y % n_entries];
+    const int r = TOP ? kJ2kRes - 1 : io.r;
+    const J2kStripRange range{e.strip0[r], e.strips[r], e.pos0[r], e.pos1[r], pieces};
+    const J2kStripTile tile{e.frame, (int) blockIdx.y / n_entries, ll_by_frame ? e.frame : e.slot, e.slot};
+    if constexpr (TOP) {
+        J2kSinkBoxTop sink{{J2kWinOut{out, e.row0, e.col0, rows, cols}, fs}, e.out};
+        j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
+    } else {
+        J2kSinkNextLevel sink{io};
+        j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
+    }
 }
 
 template <typename K>
@@ -1896,6 +1942,76 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     }
     EBCC_HIP_LAUNCH_CHECK();
     return partials;
+}
+
+// Box-list decode (J2kBoxList): after the tier-1 decode of the batch, the fused levels of every box.  Levels below the first
+// fused one run whole, once, in jb.B (every box of a frame, in every round, reads that band: nothing here writes jb.B).  An
+// entry keeps the outputs of its fused levels below the top in its slot of jb.B2, each level in a region of its own (rows of
+// even pitch at frame coordinates; together under half a frame), so two boxes of one frame never share a band.  More boxes
+// than slots run as rounds of jb.max_frames entries: five launches a round, on one stream, so a slot is reused only after the
+// round before has read it - what an earlier entry left outside the new cone is read and dropped like any position outside
+// a cone.  The records of all rounds are made here and sent as one copy.
+void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &bl, hipStream_t s)
+{
+    const J2kGeom &g = jb.geom;
+    const size_t n_pix = (size_t) g.W * g.H;
+    const int32_t *V = jb.V;
+    const FrameState *fs = jb.fs;
+    auto fusable = [&](int r) {
+        return g.period == 1 && g.ry0[r] % 2 == 0 && g.rw[r - 1] >= 2 && g.rh[r - 1] >= 1 &&
+               (r == kJ2kRes - 1 ? ceil_div(g.rw[r - 1], kL5Pairs) <= kPartials : jb.B2 != nullptr);
+    };
+    int first_fused = kJ2kRes;
+    for (int r = kJ2kRes - 1; r >= 1 && fusable(r); r--) first_fused = r;
+    if (first_fused == kJ2kRes) throw std::runtime_error("box decode: this geometry has no fused top level");
+    for (int r = 1; r < first_fused; r++) {
+        dwt_rows<false>(jb.B, V, jb, r, n_frames, fs, nullptr, s);
+        dwt_cols<false>(jb.B, jb, r, n_frames, fs, nullptr, s);
+    }
+    int pitch[kJ2kRes] = {0};
+    size_t off[kJ2kRes] = {0}, used = 0;
+    for (int r = first_fused; r < kJ2kRes - 1; r++) {
+        pitch[r] = g.rw[r] + (g.rw[r] & 1);
+        off[r] = used;
+        used += (size_t) pitch[r] * (size_t) g.rh[r];
+    }
+    if (used > n_pix) throw std::runtime_error("box decode: the level bands of a box do not fit its slot");
+    const size_t cap = (size_t) jb.max_frames;
+    for (size_t e = 0; e < bl.n; e++) {
+        J2kBoxEntry &b = bl.h_table[e];
+        J2kWindow w;
+        if (!j2k_window_plan(g, (size_t) b.row0, (size_t) b.col0, (size_t) bl.rows, (size_t) bl.cols, w)) throw std::runtime_error("box decode: a box is not inside the frame");
+        b.slot = (int) (e % cap);
+        for (int r = 0; r < kJ2kRes; r++) {
+            b.strip0[r] = b.strips[r] = b.pos0[r] = b.pos1[r] = 0;
+            if (r < first_fused) continue;
+            b.strip0[r] = (w.rx0[r] / 2) / kL5Pairs; b.strips[r] = ((w.rx1[r] - 1) / 2) / kL5Pairs - b.strip0[r] + 1;
+            b.pos0[r] = w.ry0[r] / 2; b.pos1[r] = (w.ry1[r] - 1) / 2 + 1;
+        }
+        b.pad[0] = b.pad[1] = b.pad[2] = 0;
+    }
+    EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * sizeof(J2kBoxEntry), hipMemcpyHostToDevice, s));
+    for (size_t lo = 0; lo < bl.n; lo += cap) {
+        const int n = (int) std::min(cap, bl.n - lo);
+        for (int r = first_fused; r < kJ2kRes; r++) {
+            const bool top = r == kJ2kRes - 1;
+            int strips = 1, span = 1;
+            for (int e = 0; e < n; e++) {
+                const J2kBoxEntry &b = bl.h_table[lo + e];
+                strips = std::max(strips, b.strips[r]); span = std::max(span, b.pos1[r] - b.pos0[r]);
+            }
+            int pieces = std::max(1, std::min({top ? 8 : 4, kPartials, span / 16}));
+            while (pieces > 1 && (long long) n * pieces > 65535) pieces--;   // (grid y)
+            const int wg = std::min(strips, 4);                              // (wave_cap of j2k_inverse_dwt)
+            const dim3 grid((unsigned) ceil_div(strips, wg), (unsigned) (n * pieces)), block(64 * wg);
+            const bool from_frames = r == first_fused;                       // (its low-pass input: V, or the band in jb.B)
+            J2kLevelIO io{from_frames ? (r > 1 ? jb.B : nullptr) : jb.B2 + off[r - 1], from_frames ? g.W : pitch[r - 1], n_pix,
+                          top ? nullptr : jb.B2 + off[r], top ? g.W : pitch[r], n_pix, r};
+            if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, grid, block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, pieces, from_frames ? 1 : 0, bl.out, bl.rows, bl.cols);
+            else hipLaunchKernelGGL(k_j2k_level_box<false>, grid, block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, pieces, from_frames ? 1 : 0, bl.out, bl.rows, bl.cols);
+        }
+    }
+    EBCC_HIP_LAUNCH_CHECK();
 }
 
 // A window decode writes the field from the fused top level (there is no whole field to crop): single-tile frames of at least

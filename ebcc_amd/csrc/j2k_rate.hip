@@ -1734,17 +1734,19 @@ void plan_decode_lanes(const int *host_table, int total, int out[4])
     out[3] = t.lanes[3];
 }
 
-void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table, const J2kWindow *win, float *win_out)
+void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table, const J2kWindow *win, float *win_out,
+                       const J2kBoxList *boxes)
 {
     const size_t n_pix = (size_t) jb.geom.W * jb.geom.H;
     const int total = n_frames * jb.geom.stride;
     const size_t groups = ((size_t) total + 63) / 64;
-    // Window decode: the table entries of the code-blocks outside the window's cone have been zeroed.  Empty entries come last
+    // Window and box-list decode: the table entries of the code-blocks outside the window's cone (the cones of the frame's boxes) have been zeroed.  Empty entries come last
     // in the longest-first order, so the launch ends at the last entry with data (`live`), and the lanes per wave are planned
     // from those entries alone: a small window has few, short chains and lands on the one-lane shape by the same model.
     int live = total;
     std::vector<int> live_table;
-    if (win && host_table) {
+    const bool part = win || boxes;
+    if (part && host_table) {
         for (int i = 0; i < total; i++) {
             const int *e = host_table + (size_t) i * 4;
             if (e[3] > 0 && e[2] > 0) live_table.insert(live_table.end(), e, e + 4);
@@ -1791,7 +1793,7 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
         DecTiers tiers{{0, 0, 0}, {1, 2, 4, 4}};
         if (few_blocks) { tiers.lanes[3] = 1; }
         else if (getenv("EBCC_T1_LPW")) { tiers.lanes[3] = lpw; }
-        else if (win && host_table && !getenv("EBCC_T1_DEC_TIERS")) tiers = plan_dec_tiers(live_table.data(), live);
+        else if (part && host_table && !getenv("EBCC_T1_DEC_TIERS")) tiers = plan_dec_tiers(live_table.data(), live);
         else if (host_table && !getenv("EBCC_T1_DEC_TIERS")) tiers = plan_dec_tiers(host_table, total);
         else {
             int den[3] = {kDecTierDen0, kDecTierDen1, kDecTierDen2};
@@ -1820,7 +1822,8 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
                            jb.stream_cap, jb.dec_table, jb.dec_order, jb.V, jb.d_geom, jb.d_blocks, jb.fs, live, tiers);
     }
     timing_end("t1_decode", s);
-    decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, win, win_out);
+    if (boxes) launch_j2k_box_levels(jb, n_frames, *boxes, s);
+    else decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, win, win_out);
     EBCC_HIP_LAUNCH_CHECK();
 }
 

@@ -134,6 +134,12 @@ void launch_synthesis_head(const ResidualBuffers &rb, int n_frames, const int *d
 void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
                                int rows, int cols);
 
+// the same for the boxes of a box list (j2k.hpp: J2kBoxEntry - frame, output index and origin are the record's):
+// out [n_boxes][rows][cols]; boxes of frames without a residual layer are left as they are
+struct J2kBoxEntry;
+void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, size_t n_boxes, const int *d_active,
+                                     hipStream_t s, int rows, int cols);
+
 // plain spiht_decode output image in [0,1] (spiht_re.c:508-516) for the unit entry point
 void launch_emit_image(float *image_out, const ResidualBuffers &rb, int n_frames, hipStream_t s);
 

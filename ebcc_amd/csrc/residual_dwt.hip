@@ -14,6 +14,7 @@
 #include <mutex>
 #include "residual.hpp"
 #include "residual_device.hpp"
+#include "j2k.hpp"
 
 namespace ebcc {
 
@@ -248,6 +249,41 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__res
     src += (size_t) frame * frame_stride;
     const int tid = threadIdx.x;
     float *o = out + (size_t) frame * ((size_t) rows * (size_t) cols);
+    const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
+    for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
+        const float *s = src + (size_t) (row0 + wy) * stride;
+        for (int k = tid; k < half; k += kRowThreads) {
+            E[k] = s[k];
+            O[k] = s[half + k];
+        }
+        __syncthreads();
+        lift_inverse_tile(E, O, half, 1, RowIdx(), tid, kRowThreads);
+        for (int wx = tid; wx < cols; wx += kRowThreads) {
+            const int xx = col0 + wx;
+            const float r = residual_value((xx & 1) ? O[xx >> 1] : E[xx >> 1], dc, rmin, rng);
+            const size_t i = (size_t) wy * (size_t) cols + (size_t) wx;
+            o[i] = o[i] + r;
+        }
+        __syncthreads();
+    }
+}
+
+// k_rows_inv_add for the boxes of a box list: workgroups (x, e) synthesise the rows of box e - rows row0 .. row0 + rows - 1 of
+// the grid of the frame the record names - and add the record's columns to box out[e.out].  The same row, the same chain, the
+// same bits as in the whole frame.
+__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_box(const float *__restrict__ src, int stride, size_t frame_stride, int n,
+                                                                   const int *active, const FrameState *fs, float *out,
+                                                                   const J2kBoxEntry *__restrict__ boxes, int rows, int cols)
+{
+    extern __shared__ float sm[];
+    const J2kBoxEntry &e = boxes[blockIdx.y];
+    const int frame = e.frame, row0 = e.row0, col0 = e.col0;
+    if (active && !active[frame]) return;
+    const int half = n >> 1;
+    float *E = sm, *O = sm + half;
+    src += (size_t) frame * frame_stride;
+    const int tid = threadIdx.x;
+    float *o = out + (size_t) e.out * ((size_t) rows * (size_t) cols);
     const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
     for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
         const float *s = src + (size_t) (row0 + wy) * stride;
@@ -1327,6 +1363,20 @@ void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_fram
     const Grid &g = rb.g;
     hipLaunchKernelGGL(k_rows_inv_add, dim3(min(rows, 96), n_frames), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
                        d_active, rb.fs, out, row0, col0, rows, cols);
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+// (one workgroup row per box and at most 65535 boxes a launch.  Two records may name the same output samples only if they are
+//  the same box of the same frame - the caller's indices are all different - so no two workgroups add to one sample.)
+void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, size_t n_boxes, const int *d_active,
+                                     hipStream_t s, int rows, int cols)
+{
+    const Grid &g = rb.g;
+    for (size_t lo = 0; lo < n_boxes; lo += 65535) {
+        const unsigned n = (unsigned) std::min<size_t>(65535, n_boxes - lo);
+        hipLaunchKernelGGL(k_rows_inv_add_box, dim3(min(rows, 96), n), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
+                           d_active, rb.fs, out, d_boxes + lo, rows, cols);
+    }
     EBCC_HIP_LAUNCH_CHECK();
 }
 

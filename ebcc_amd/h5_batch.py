@@ -66,6 +66,9 @@ class BatchCodec:
         lib.ebcc_hip_decode_host_frames_window.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                                            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
                                                            ctypes.c_void_p]
+        lib.ebcc_hip_decode_host_frames_boxes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                          ctypes.c_void_p]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -131,6 +134,40 @@ class BatchCodec:
             raise RuntimeError("ebcc_hip_decode_host_frames: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
         if os.environ.get("EBCC_H5_TIMING"):
             print(f"h5_batch.decode: {n} frames decoded and downloaded in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
+        return out
+
+    def decode_boxes(self, streams, boxes, rows, cols, out=None):
+        """Any boxes of any frames: `boxes` is an int array (k, 3) of (frame, row0, col0) in non-decreasing order of frame,
+        every box rows x cols -> (k, rows, cols) float32, box e bit for bit streams[frame_e] decoded and cropped to
+        [row0, row0 + rows) x [col0, col0 + cols).  A frame is decoded once, from the code-blocks its boxes depend on; a
+        frame no box names is not read (its entry of `streams` may be None).  Repeated and overlapping boxes are fine and k
+        is not limited by the engine's capacity.  ValueError for a list the engine refuses (checked here, before the call);
+        RuntimeError for what the call itself reports, such as a malformed stream."""
+        n = len(streams)
+        rows, cols = int(rows), int(cols)
+        b = np.asarray(boxes)
+        if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
+            raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
+        b = b.astype(np.int64)
+        if rows < 1 or cols < 1 or rows > self.h or cols > self.w:
+            raise ValueError(f"boxes of {rows} x {cols} are empty or not inside the {self.h} x {self.w} frame")
+        if b.min() < 0 or (b[:, 0] >= n).any():
+            raise ValueError(f"a box names a frame outside the {n} streams, or has a negative origin")
+        if (b[:, 1] > self.h - rows).any() or (b[:, 2] > self.w - cols).any():
+            raise ValueError(f"a box of {rows} x {cols} is not inside the {self.h} x {self.w} frame")
+        if (np.diff(b[:, 0]) < 0).any():
+            raise ValueError("boxes must be in non-decreasing order of their frames")
+        k = len(b)
+        named = set(int(f) for f in np.unique(b[:, 0]))
+        streams = [None if i not in named else (s if isinstance(s, bytes) else bytes(s)) for i, s in enumerate(streams)]
+        ptrs = (ctypes.c_void_p * n)(*[None if s is None else ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
+        sizes = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in streams])
+        table = np.ascontiguousarray(b, np.uint64)                       # == ebcc_hip_box[k]
+        if out is None:
+            out = np.empty((k, rows, cols), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == k * rows * cols
+        if self.lib.ebcc_hip_decode_host_frames_boxes(self.ctx, ptrs, sizes, n, table.ctypes.data, k, rows, cols, out.ctypes.data):
+            raise RuntimeError("ebcc_hip_decode_host_frames_boxes: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
         return out
 
 
@@ -256,3 +293,64 @@ def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
             if t:
                 t.join()
     return out.reshape(tuple(lead) + (nrows, ncols))
+
+
+def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):
+    """Boxes of rows x cols out of an EBCC-filtered one-frame-per-chunk dataset: `boxes` is an int array (k, 3) of
+    (frame, row0, col0), the frame counted in C order over the leading axes, in any order -> (k, rows, cols), box e equal to
+    read_frames(dset).reshape(-1, H, W)[frame_e, row0:row0 + rows, col0:col0 + cols].  Only the chunks of the frames the boxes
+    name are fetched from the file, and each of them is decoded once (BatchCodec.decode_boxes)."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    b = np.asarray(boxes)
+    if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
+        raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
+    b = b.astype(np.int64)
+    if b[:, 0].min() < 0 or b[:, 0].max() >= n:
+        raise ValueError(f"a box names a frame outside the {n} frames of the dataset")
+    order = np.argsort(b[:, 0], kind="stable")
+    b = b[order]
+    frames = np.unique(b[:, 0])                                         # (sorted)
+    codec = codec or cached_codec(h, w, min(batch, len(frames)))
+    out = np.empty((len(b), int(rows), int(cols)), np.float32)
+    step = _SUPER * codec.max_frames
+    for lo in range(0, len(frames), step):
+        part = frames[lo:lo + step]
+        raw = []
+        for f in part:
+            idx = np.unravel_index(int(f), lead) if lead else ()
+            mask, chunk = dset.id.read_direct_chunk(tuple(int(v) for v in idx) + (0, 0))
+            if mask:
+                raise ValueError(f"chunk {idx} was stored with filters disabled (mask {mask})")
+            raw.append(chunk)
+        e0, e1 = np.searchsorted(b[:, 0], part[0], "left"), np.searchsorted(b[:, 0], part[-1], "right")
+        local = b[e0:e1].copy()
+        local[:, 0] = np.searchsorted(part, local[:, 0])
+        codec.decode_boxes(raw, local, rows, cols, out=out[e0:e1])
+    res = np.empty_like(out)
+    res[order] = out
+    return res
+
+
+def read_points(dset, rows_idx, cols_idx, batch=256, codec=None):
+    """The series of K samples through every frame - stations - as lead + (K,): read_frames(dset)[..., rows_idx, cols_idx] for
+    two integer sequences of length K, from 1 x 1 boxes (read_boxes): every frame is decoded once, from the few code-blocks
+    its K points depend on."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    r, c = np.asarray(rows_idx), np.asarray(cols_idx)
+    if r.ndim != 1 or r.shape != c.shape or len(r) < 1 or r.dtype.kind not in "iu" or c.dtype.kind not in "iu":
+        raise ValueError("rows_idx and cols_idx must be integer sequences of one length")
+    r, c = r.astype(np.int64), c.astype(np.int64)
+    r, c = np.where(r < 0, r + h, r), np.where(c < 0, c + w, c)          # (negative indices as numpy counts them)
+    if r.min() < 0 or r.max() >= h or c.min() < 0 or c.max() >= w:
+        raise IndexError(f"a point is outside the {h} x {w} frame")
+    k = len(r)
+    boxes = np.empty((n, k, 3), np.int64)
+    boxes[:, :, 0] = np.arange(n)[:, None]
+    boxes[:, :, 1] = r[None, :]
+    boxes[:, :, 2] = c[None, :]
+    got = read_boxes(dset, boxes.reshape(-1, 3), 1, 1, batch=batch, codec=codec)
+    return got.reshape(tuple(lead) + (k,))

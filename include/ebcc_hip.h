@@ -184,6 +184,39 @@ int ebcc_hip_decode_shard_window(ebcc_hip_ctx *ctx, const uint8_t *const *stream
 int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                                        size_t row0, size_t col0, size_t rows, size_t cols, float *h_out);
 
+/* ---- box-list decode -------------------------------------------------------------------------
+ * Any boxes of any frames in one call: a list of boxes of one size rows x cols, each naming the frame it is cut from - the
+ * series of K stations through every time step (K boxes per frame), a box that follows a cyclone (one box per frame at a
+ * moving origin), random crops of training samples.  Box e is, bit for bit, the crop [row0, row0 + rows) x [col0, col0 + cols)
+ * of what ebcc_hip_decode_frames gives for frame `frame`; the output is [n_boxes][rows][cols], box e at index e, at any 4-byte
+ * aligned address, and nothing outside it is written, also by a call that fails.
+ * A frame is decoded once, from the union of the code-blocks its boxes need, and its residual layer's SPIHT chain runs once
+ * whatever the number of its boxes.  A frame that no box names is not read at all: its streams[f] may be NULL with size 0,
+ * and nothing of it is parsed, uploaded, decompressed or decoded (it takes no slot of a batch either: the batches of the
+ * shard and host forms are cut over the named frames).  Streams of named frames are checked and refused exactly as the
+ * full decode does.  Constant fields, frames without a residual layer, legacy streams and mixed batches as in the window decode.
+ * `boxes` must be in non-decreasing order of `frame`; repeats, overlaps and identical boxes are allowed, and n_boxes is not
+ * limited by the context's capacity (more boxes than it holds frames run as rounds of the inverse wavelet levels over one
+ * tier-1 and one SPIHT decode).  Refused with return value 1, a message (ebcc_hip_last_error) and nothing written: n_boxes,
+ * rows or cols zero, a box not inside the frame, frame >= n_frames, frames out of order.  One-frame chunks only. */
+typedef struct { size_t frame, row0, col0; } ebcc_hip_box;
+/* at most the context's capacity of frames (n_frames), d_out on the device */
+int ebcc_hip_decode_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                 const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols, float *d_out);
+/* any number of frames, batches on the two engine sets; every batch owns a contiguous part of the output */
+int ebcc_hip_decode_shard_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols, float *d_out);
+/* pageable host output; only the boxes cross PCIe, batch by batch */
+int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                      const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols, float *h_out);
+/* Which code-blocks a box-list decode of n_frames frames of height x width reads (host logic, no device work): row f of
+ * keep [n_frames][code-blocks] (may be NULL: the call then only counts and checks) is the OR of the keep flags
+ * ebcc_hip_window_plan gives for the boxes of frame f, all zero for a frame no box names.  max_blocks: code-blocks a row of
+ * keep has room for - fewer than the frame has is refused.  Returns the number of code-blocks of a frame, -1 for anything
+ * the decode calls refuse (then keep is not written). */
+int ebcc_hip_boxes_plan(size_t height, size_t width, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes,
+                        size_t rows, size_t cols, uint8_t *keep, size_t max_blocks);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is

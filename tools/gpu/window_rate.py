@@ -2,13 +2,17 @@
 721x1440, base_cr 30, MAX_ERROR 0.5, seeded as bench.py seeds them - is decoded whole and as windows of 360x720, 128x256
 (centred and at a corner) and 32x32, device-resident (ebcc_hip_decode_frames[_window]) and into a pageable host array
 (ebcc_hip_decode_host_frames[_window]): ms per call, the t1_decode span (ebcc_hip_timing_read), and the share of code-blocks
-and of segment bytes each window keeps.
+and of segment bytes each window keeps.  Then the box lists (ebcc_hip_decode_*_boxes), each next to the only way without them:
+stations (64 seeded points of every frame in one call, against 64 window calls), a track (a 128x256 box that moves over the 256
+frames, against the uniform window of its bounding box), a sparse list (the centred 128x256 box on every eighth frame, against
+the same window on those 32 streams), and the four uniform windows as box lists of one box per frame (DESIGN section 2.8:
+one path or two).
 
     python tools/gpu/window_rate.py [--rounds 3] [--reps 5] [--parent-lib PATH]
 
 Every measurement is a child process under its own time limit, and nothing more is started after one fails.  With
---parent-lib (the library of the parent commit, built elsewhere) a child that times that library's ebcc_hip_decode_frames
-alternates with the children of this build, as tools/gpu/ab_multi.sh alternates settings on one box."""
+--parent-lib (the library of the parent commit, built elsewhere) a child that times that library's full decode and uniform
+windows alternates with the children of this build, as tools/gpu/ab_multi.sh alternates settings on one box."""
 import argparse
 import ctypes
 import json
@@ -40,6 +44,11 @@ def child(args):
     lib.ebcc_hip_prepare.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
     lib.ebcc_hip_decode_host_frames.argtypes = [ctypes.c_void_p, L.c_void_pp, L.c_size_p, ctypes.c_size_t, ctypes.c_void_p]
     sig = [ctypes.c_void_p, L.c_void_pp, L.c_size_p, ctypes.c_size_t] + [ctypes.c_size_t] * 4 + [ctypes.c_void_p]
+    bsig = [ctypes.c_void_p, L.c_void_pp, L.c_size_p, ctypes.c_size_t, ctypes.c_void_p] + [ctypes.c_size_t] * 3 + [ctypes.c_void_p]
+    if not args.no_boxes:
+        lib.ebcc_hip_decode_frames_boxes.argtypes = bsig
+        lib.ebcc_hip_decode_host_frames_boxes.argtypes = bsig
+        lib.ebcc_hip_boxes_plan.argtypes = [ctypes.c_size_t] * 3 + [ctypes.c_void_p] + [ctypes.c_size_t] * 3 + [ctypes.c_void_p, ctypes.c_size_t]
     if not args.full_only:
         lib.ebcc_hip_decode_frames_window.argtypes = sig
         lib.ebcc_hip_decode_host_frames_window.argtypes = sig
@@ -55,20 +64,63 @@ def child(args):
     assert lib.ebcc_hip_encode_frames(ctx, frames.data_ptr(), n, ctypes.byref(cfg), outs, sizes) == 0, lib.ebcc_hip_last_error()
     d_out = torch.empty_like(frames)
     res = {}
-    for name, win in CASES if not args.full_only else CASES[:1]:
-        pix = H * W if win is None else win[2] * win[3]
+
+    def ok(rc):
+        assert rc == 0, lib.ebcc_hip_last_error()
+
+    def window_calls(wins, streams=outs, lens=sizes, count=n):
+        """one uniform-window call per window of the list, outputs one behind the other: (resident, host, floats put out)"""
+        pix = [H * W if w is None else w[2] * w[3] for w in wins]
 
         def resident():
-            rc = (lib.ebcc_hip_decode_frames(ctx, outs, sizes, n, d_out.data_ptr()) if win is None else
-                  lib.ebcc_hip_decode_frames_window(ctx, outs, sizes, n, *win, d_out.data_ptr()))
-            assert rc == 0, lib.ebcc_hip_last_error()
+            at = 0
+            for w, p in zip(wins, pix):
+                d = d_out.data_ptr() + 4 * at
+                ok(lib.ebcc_hip_decode_frames(ctx, streams, lens, count, d) if w is None else lib.ebcc_hip_decode_frames_window(ctx, streams, lens, count, *w, d))
+                at += count * p
+
+        def host(h_out):
+            at = 0
+            for w, p in zip(wins, pix):
+                d = h_out.ctypes.data + 4 * at
+                ok(lib.ebcc_hip_decode_host_frames(ctx, streams, lens, count, d) if w is None else
+                   lib.ebcc_hip_decode_host_frames_window(ctx, streams, lens, count, *w, d))
+                at += count * p
+        return resident, host, count * sum(pix)
+
+    def box_call(boxes, rows, cols):
+        table = np.ascontiguousarray(np.asarray(boxes, np.uint64).reshape(-1, 3))
+
+        def resident():
+            ok(lib.ebcc_hip_decode_frames_boxes(ctx, outs, sizes, n, table.ctypes.data, len(table), rows, cols, d_out.data_ptr()))
+
+        def host(h_out):
+            ok(lib.ebcc_hip_decode_host_frames_boxes(ctx, outs, sizes, n, table.ctypes.data, len(table), rows, cols, h_out.ctypes.data))
+        return resident, host, len(table) * rows * cols
+
+    cases = [(name, window_calls([win]), win, None) for name, win in (CASES if not args.full_only else CASES[:1])]
+    if not args.no_boxes:
+        rng = np.random.default_rng(64)
+        pts = [(int(rng.integers(0, H)), int(rng.integers(0, W))) for _ in range(64)]
+        track = [(f, 250 + (100 * f) // max(1, n - 1), ((W - 256) * f) // max(1, n - 1)) for f in range(n)]
+        some = list(range(0, n, 8))
+        s_outs, s_sizes = (ctypes.c_void_p * len(some))(*[outs[f] for f in some]), (ctypes.c_size_t * len(some))(*[sizes[f] for f in some])
+        centre = CASES[2][1]
+        cases += [("stations: 64 windows", window_calls([(r, c, 1, 1) for r, c in pts]), "64 calls", None),
+                  ("stations: box list", box_call([(f, r, c) for f in range(n) for r, c in pts], 1, 1), None, ([(f, r, c) for f in range(n) for r, c in pts], 1, 1)),
+                  ("track: bounding window", window_calls([(250, 0, 228, W)]), (250, 0, 228, W), None),
+                  ("track: box list", box_call(track, 128, 256), None, (track, 128, 256)),
+                  ("sparse: 32 streams", window_calls([centre], s_outs, s_sizes, len(some)), centre, None),
+                  ("sparse: box list", box_call([(f, centre[0], centre[1]) for f in some], 128, 256), None, ([(f, centre[0], centre[1]) for f in some], 128, 256))]
+        for name, win in CASES[1:]:                                      # (one path or two: the uniform windows through the box kernels)
+            as_boxes = [(f, win[0], win[1]) for f in range(n)]
+            cases.append((name + " as boxes", box_call(as_boxes, win[2], win[3]), None, (as_boxes, win[2], win[3])))
+    for name, (resident, host_into, floats), win, listed in cases:
 
         def host():
-            h_out = np.empty(n * pix, np.float32)                      # (a fresh pageable array every call, as a reader has)
+            h_out = np.empty(floats, np.float32)                       # (a fresh pageable array every call, as a reader has)
             t0 = time.perf_counter()
-            rc = (lib.ebcc_hip_decode_host_frames(ctx, outs, sizes, n, h_out.ctypes.data) if win is None else
-                  lib.ebcc_hip_decode_host_frames_window(ctx, outs, sizes, n, *win, h_out.ctypes.data))
-            assert rc == 0, lib.ebcc_hip_last_error()
+            host_into(h_out)
             return time.perf_counter() - t0
 
         r = {}
@@ -88,7 +140,22 @@ def child(args):
         host()
         r["host_ms"] = [round(1e3 * host(), 3) for _ in range(args.reps)]
         if not args.full_only:
-            if win is None:
+            if listed is not None:
+                boxes, rows, cols = listed
+                table = np.ascontiguousarray(np.asarray(boxes, np.uint64).reshape(-1, 3))
+                keep = np.zeros((n, 298), np.uint8)
+                nb = lib.ebcc_hip_boxes_plan(H, W, n, table.ctypes.data, len(table), rows, cols, keep.ctypes.data, 298)
+                assert nb == 298
+                named = int(keep.any(axis=1).sum())
+                # (code-blocks per named frame.  Rounds and launches are DERIVED from the code, not counted in the run: one decode
+                #  slice - the default - of a context with n slots, the five fused levels of a 721 x 1440 frame per round, and the
+                #  residual pass of at most 65535 records a launch)
+                r["blocks_kept"], r["blocks"], r["frames_named"] = round(float(keep.sum()) / named, 1), nb, named
+                r["rounds"] = -(-len(table) // n)
+                r["launches"] = 5 * r["rounds"] + -(-len(table) // 65535)
+            elif isinstance(win, str):
+                r["blocks_kept"], r["blocks"] = win, 298
+            elif win is None:
                 r["blocks_kept"], r["blocks"] = 298, 298
             else:
                 blocks = np.zeros((512, 6), np.int32)
@@ -140,6 +207,7 @@ def main():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--lib", help=argparse.SUPPRESS)
     ap.add_argument("--full-only", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--no-boxes", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args)
@@ -149,17 +217,20 @@ def main():
 
     for rnd in range(args.rounds):
         if args.parent_lib:
-            p = run_child(["--lib", os.path.abspath(args.parent_lib), "--full-only"], args.frames, args.reps)["full"]
-            print(f"round {rnd} [parent] full decode: resident {med(p['resident_ms']):8.2f} ms (min {min(p['resident_ms']):.2f}), t1_decode {p['t1_decode_ms']:.2f} ms, "
-                  f"host array {med(p['host_ms']):8.2f} ms (min {min(p['host_ms']):.2f})", flush=True)
+            pr = run_child(["--lib", os.path.abspath(args.parent_lib), "--no-boxes"], args.frames, args.reps)
+            for name, _ in CASES:
+                p = pr[name]
+                print(f"round {rnd} [parent]     {name:24s}: resident {med(p['resident_ms']):8.2f} ms (min {min(p['resident_ms']):.2f}), t1_decode {p['t1_decode_ms']:6.2f} ms, "
+                      f"host array {med(p['host_ms']):8.2f} ms (min {min(p['host_ms']):.2f})", flush=True)
         res = run_child([], args.frames, args.reps)
         full_bytes = res["full"].get("segment_bytes", 0)
-        for name, _ in CASES:
+        for name in [k for k in res if isinstance(res[k], dict)]:
             r = res[name]
             share = f"{100.0 * r['segment_bytes'] / full_bytes:5.1f} %" if full_bytes else "    ?"
-            print(f"round {rnd} [this build] {name:15s}: resident {med(r['resident_ms']):8.2f} ms (min {min(r['resident_ms']):.2f}), t1_decode {r['t1_decode_ms']:6.2f} ms in "
+            more = f"; frames named {r['frames_named']}, rounds {r['rounds']}, launches {r['launches']} (derived)" if "rounds" in r else ""
+            print(f"round {rnd} [this build] {name:24s}: resident {med(r['resident_ms']):8.2f} ms (min {min(r['resident_ms']):.2f}), t1_decode {r['t1_decode_ms']:6.2f} ms in "
                   f"{r['t1_decode_spans']} spans, host array {med(r['host_ms']):8.2f} ms (min {min(r['host_ms']):.2f}); code-blocks kept {r['blocks_kept']}/{r['blocks']}, "
-                  f"segment bytes {r.get('segment_bytes', 0)} ({share})", flush=True)
+                  f"segment bytes {r.get('segment_bytes', 0)} ({share}){more}", flush=True)
 
 
 if __name__ == "__main__":
