@@ -898,7 +898,7 @@ bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf)
 // tile-parts of one tiled codestream (reference :121-125) - and its residual layer one frame of `rctx` (== ctx for
 // one-frame chunks).
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, const DecodeWindow *win, const DecodeBoxes *boxes)
+                 SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, const DecodeRegion &region)
 {
     struct Release { SliceGate *g; ~Release() { if (g) g->release(); } } release_on_exit{next};
     ebcc_hip_ctx *const rc = rctx ? rctx : ctx;
@@ -906,51 +906,39 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     hipStream_t s = ctx->stream;
     const size_t nt = n * tiles, n_pix = ctx->n_pix * tiles;         // frames of ctx; pixels of a chunk
     const J2kGeom &g = jb.geom;
-    // window decode: the cone of the window and, per code-block of a frame, whether it holds it
-    J2kWindow cone;
+    // The plan of the region, made (or refused) before anything is written: what the kernels put out (`dev`: the window's cone,
+    // or the table of the boxes with the spans of their cones) and `keep`, whether a code-block holds any of it - one row for
+    // every frame (keep_row 0: a window) or a row per frame (a box list: the union over the frame's boxes); empty: all do.
+    J2kRegion dev;
     std::vector<uint8_t> keep;
-    if (win) {
-        if (tiles != 1 || g.period != 1) { set_error("window decode: chunks of several frames are not supported"); return 1; }
-        if (!j2k_window_supported(g)) { set_error("window decode: frames of %d x %d are not supported (fewer than 3 columns)", g.H, g.W); return 1; }
-        if (!j2k_window_plan(g, win->row0, win->col0, win->rows, win->cols, cone)) {
-            set_error("window decode: the window is empty or not inside the %d x %d frame", g.H, g.W);
-            return 1;
-        }
-        std::vector<J2kBlock> blocks;
-        make_j2k_geom(g.H, g.W, blocks);
-        keep.resize(blocks.size());
-        int rect[4];
-        for (size_t b = 0; b < blocks.size(); b++) keep[b] = j2k_window_keeps(g, blocks[b], cone, rect) ? 1 : 0;
-    }
-    // box list: per frame, the union of the code-blocks its boxes hold; the entry table with what the caller says of a box
-    // (launch_j2k_box_levels adds slot and ranges)
-    J2kBoxList list{};
-    const size_t keep_row = boxes ? (size_t) g.nblocks : 0;            // (keep: one row per frame; a window: one row for all)
-    if (boxes) {
-        if (win || tiles != 1 || g.period != 1) { set_error("box decode: chunks of several frames are not supported"); return 1; }
-        std::vector<ebcc_hip_box> local(boxes->boxes, boxes->boxes + boxes->n);
-        for (ebcc_hip_box &b : local) b.frame -= boxes->frame0;
-        keep.resize(n * keep_row);
-        if (!j2k_boxes_check("box decode", g, n, local.data(), local.size(), boxes->rows, boxes->cols, keep.data())) return 1;
-        if (boxes->n > ctx->boxes_cap) {                               // grow (rare: sized by the longest list seen)
-            void *h_old = ctx->h_boxes, *d_old = ctx->d_boxes;
-            ctx->h_boxes = nullptr; ctx->d_boxes = nullptr; ctx->boxes_cap = 0;
-            if (h_old) hipHostFree(h_old);
-            if (d_old) hipFree(d_old);
-            const size_t cap = boxes->n + boxes->n / 2 + 64;
-            void *h_new = nullptr, *d_new = nullptr;
-            EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap * sizeof(J2kBoxEntry)));
-            const hipError_t e = device_malloc(&d_new, cap * sizeof(J2kBoxEntry));
-            if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
-            ctx->h_boxes = h_new; ctx->d_boxes = d_new; ctx->boxes_cap = cap;
-        }
-        list = J2kBoxList{static_cast<J2kBoxEntry *>(ctx->h_boxes), static_cast<J2kBoxEntry *>(ctx->d_boxes), boxes->n, (int) boxes->rows, (int) boxes->cols, d_out};
-        for (size_t e = 0; e < local.size(); e++) {
-            J2kBoxEntry &b = list.h_table[e];
-            b.frame = (int) local[e].frame; b.out = (int) e; b.row0 = (int) local[e].row0; b.col0 = (int) local[e].col0;
+    size_t keep_row = 0;
+    if (region.kind != DecodeRegion::Frames) {
+        const bool window = region.kind == DecodeRegion::Window;
+        if (tiles != 1 || g.period != 1) { set_error("%s decode: chunks of several frames are not supported", window ? "window" : "box"); return 1; }
+        dev.kind = window ? J2kRegion::Window : J2kRegion::Boxes;
+        dev.out = d_out;
+        if (window) {
+            if (!j2k_window_supported(g)) { set_error("window decode: frames of %d x %d are not supported (fewer than 3 columns)", g.H, g.W); return 1; }
+            if (!j2k_window_plan(g, region.row0, region.col0, region.rows, region.cols, dev.cone)) {
+                set_error("window decode: the window is empty or not inside the %d x %d frame", g.H, g.W);
+                return 1;
+            }
+            std::vector<J2kBlock> blocks;
+            make_j2k_geom(g.H, g.W, blocks);
+            keep.resize(blocks.size());
+            int rect[4];
+            for (size_t b = 0; b < blocks.size(); b++) keep[b] = j2k_window_keeps(g, blocks[b], dev.cone, rect) ? 1 : 0;
+        } else {
+            std::vector<ebcc_hip_box> local(region.boxes, region.boxes + region.n);
+            for (ebcc_hip_box &b : local) b.frame -= region.frame0;
+            keep_row = (size_t) g.nblocks;
+            keep.resize(n * keep_row);
+            boxes_reserve(ctx, region.n, sizeof(J2kBoxEntry));
+            dev.list = J2kBoxList{static_cast<J2kBoxEntry *>(ctx->h_boxes), static_cast<J2kBoxEntry *>(ctx->d_boxes), region.n, (int) region.rows, (int) region.cols};
+            if (!j2k_boxes_check("box decode", g, n, local.data(), local.size(), region.rows, region.cols, keep.data(), dev.list.h_table, j2k_first_fused(jb))) return 1;
         }
     }
-    const size_t out_pix = win ? win->pixels() : boxes ? boxes->pixels() : n_pix;   // samples a chunk (a box) puts out
+    const size_t out_pix = region.pixels(n_pix), n_out = region.outputs(n);     // samples of an output item; items
     int *const table = ctx->h_table;                                  // (pinned)
     const size_t table_ints = nt * (size_t) g.stride * 4;
     memset(table, 0, table_ints * sizeof(int));
@@ -1079,36 +1067,28 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     // the decoded field is written where the caller wants it ([n][tiles][tile pixels] == [n][chunk pixels]; the engine's own
     // field buffer and a 1 GB device-to-device copy per 256 frames only for an output that is not aligned the way the
     // engine's buffers are)
-    // (a window always goes straight to the caller's compact array: its kernels store single samples where pairs are not aligned)
-    const bool direct = win || boxes || ((uintptr_t) d_out & 255u) == 0;
+    const bool direct = region.direct(d_out);
     J2kBuffers view = jb;
-    if (direct && !win && !boxes) view.DEC = d_out;
-    launch_j2k_decode(view, (int) nt, s, table, win ? &cone : nullptr, win ? d_out : nullptr, boxes ? &list : nullptr);
+    if (direct && dev.kind == J2kRegion::Frames) view.DEC = d_out;
+    launch_j2k_decode(view, (int) nt, s, table, dev);
     if (next) { next->release(); release_on_exit.g = nullptr; }     // host parsing done, kernels queued
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
-        // last row pass: field += residual (of a window: its rows alone)
-        if (boxes) launch_synthesis_tail_add_boxes(d_out, rc->rb, list.table, list.n, rc->d_active, s, list.rows, list.cols);
-        else if (win) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, cone.row0, cone.col0, cone.rows, cone.cols);
+        // last row pass: field += residual (of a window or a box: its rows alone)
+        if (dev.kind == J2kRegion::Boxes) launch_synthesis_tail_add_boxes(d_out, rc->rb, dev.list.table, dev.list.n, rc->d_active, s, dev.list.rows, dev.list.cols);
+        else if (dev.kind == J2kRegion::Window) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, dev.cone.row0, dev.cone.col0, dev.cone.rows, dev.cone.cols);
         else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s, 0, 0, rc->rb.g.size_y, rc->rb.g.size_x);
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // constant chunks: fill on the host side of the copy (rare path)
-    // (a box list: one host image per constant frame, kept until the one wait below, whatever the number of its boxes)
+    // constant chunks: fill on the host side of the copy (rare path) - one host image per constant frame, whatever the number
+    // of its items (which are in the order of their frames), kept until the one wait below
     std::vector<std::vector<float>> fills;
-    for (size_t e = 0, last = (size_t) -1; boxes && e < list.n; e++) {
-        const size_t f = (size_t) list.h_table[e].frame;
+    for (size_t e = 0, last = (size_t) -1; e < n_out; e++) {
+        const size_t f = dev.kind == J2kRegion::Boxes ? (size_t) dev.list.h_table[e].frame : e;
         if (!rc->h_fs[f].const_field) continue;
-        if (f != last) { fills.emplace_back(out_pix, rc->h_fs[f].minv); last = f; }      // (the boxes are in the order of their frames)
+        if (f != last) { fills.emplace_back(out_pix, rc->h_fs[f].minv); last = f; }
         EBCC_HIP_CHECK(hipMemcpyAsync(d_out + e * out_pix, fills.back().data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
     }
-    if (!fills.empty()) wait_stream(s);
-    for (size_t c = 0; c < n && !boxes; c++)
-        if (rc->h_fs[c].const_field) {
-            std::vector<float> v(out_pix, rc->h_fs[c].minv);
-            EBCC_HIP_CHECK(hipMemcpyAsync(d_out + c * out_pix, v.data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
-            wait_stream(s);
-        }
     wait_stream(s);
     pt.mark("decode: kernels");
     return 0;

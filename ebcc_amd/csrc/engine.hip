@@ -155,6 +155,21 @@ void stage_download(ebcc_hip_ctx *ctx, const uint8_t *src, size_t stride, const 
 
 void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m) { stage_layout(ctx, len, off, m); }
 
+void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes)
+{
+    if (n <= ctx->boxes_cap) return;
+    void *h_old = ctx->h_boxes, *d_old = ctx->d_boxes;
+    ctx->h_boxes = nullptr; ctx->d_boxes = nullptr; ctx->boxes_cap = 0;
+    if (h_old) hipHostFree(h_old);
+    if (d_old) hipFree(d_old);
+    const size_t cap = n + n / 2 + 64;
+    void *h_new = nullptr, *d_new = nullptr;
+    EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap * bytes));
+    const hipError_t e = device_malloc(&d_new, cap * bytes);
+    if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
+    ctx->h_boxes = h_new; ctx->d_boxes = d_new; ctx->boxes_cap = cap;
+}
+
 void stage_send(ebcc_hip_ctx *ctx, size_t m, hipStream_t s)
 {
     size_t total = 0;

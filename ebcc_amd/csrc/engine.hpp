@@ -70,6 +70,8 @@ void stage_download(ebcc_hip_ctx *ctx, const uint8_t *src, size_t stride, const 
 void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m);
 void stage_send(ebcc_hip_ctx *ctx, size_t m, hipStream_t s);
 void stage_scatter(ebcc_hip_ctx *ctx, uint8_t *dst, size_t stride, size_t first, size_t count, hipStream_t s);
+// room for n records of `bytes` each in ctx->h_boxes / d_boxes (grown rarely: sized by the longest box list seen)
+void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes);
 
 // cut slots for `capacity` simultaneous probes (residual.hpp); false: not available (unsupported grid or no memory)
 bool ensure_cut_slots(ebcc_hip_ctx *ctx, int capacity);

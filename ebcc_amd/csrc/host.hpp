@@ -279,31 +279,43 @@ struct ParsedFrame {
     const uint8_t *z = nullptr, *tail = nullptr;
 };
 bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf);
-// ebcc_decode for a batch of `n` chunk streams of `tiles` frames each, as encode_batch codes them -> device buffer
-// d_out [n][tiles * H * W].  Returns 0 or 1 (error).  `win` (one-frame chunks only): the window [row0, row0 + rows) x
-// [col0, col0 + cols) of every frame alone, d_out [n][rows][cols], from the code-blocks its dependency cone holds (J2kWindow).
-struct DecodeWindow {
-    size_t row0, col0, rows, cols;
-    size_t pixels() const { return rows * cols; }
-};
-// `boxes` (one-frame chunks only, instead of `win`): a box list - boxes of rows x cols in non-decreasing order of their frames,
-// which count from the batch's stream `frame0`; every stream of the batch is named by a box; d_out [n][rows][cols], box e
-// at index e.  part(lo, cnt): the boxes of the streams lo .. lo + cnt - 1 of the batch, as the list of that part.
-struct DecodeBoxes {
-    const ebcc_hip_box *boxes;
-    size_t n, rows, cols, frame0;
-    size_t pixels() const { return rows * cols; }
-    DecodeBoxes part(size_t lo, size_t cnt, size_t *first = nullptr) const
+// What a decode call puts out - one value through every layer from the entry point to decode_batch.  An output item is
+//   Frames   a frame, whole: [n][frame pixels] (chunks of several frames: [n][tiles * H * W])
+//   Window   the window [row0, row0 + rows) x [col0, col0 + cols) of a frame, [n][rows][cols], from the code-blocks its dependency
+//            cone holds (J2kWindow); one-frame chunks only
+//   Boxes    a box of a list of `n` boxes of rows x cols in non-decreasing order of their frames, which count from the stream
+//            `frame0` of the batch; every stream of the batch is named by a box; [n][rows][cols]; one-frame chunks only
+struct DecodeRegion {
+    enum Kind { Frames, Window, Boxes } kind = Frames;
+    size_t row0 = 0, col0 = 0, rows = 0, cols = 0;
+    const ebcc_hip_box *boxes = nullptr;
+    size_t n = 0, frame0 = 0;
+    static DecodeRegion window(size_t row0, size_t col0, size_t rows, size_t cols) { return DecodeRegion{Window, row0, col0, rows, cols, nullptr, 0, 0}; }
+    static DecodeRegion box_list(const ebcc_hip_box *boxes, size_t n, size_t rows, size_t cols) { return DecodeRegion{Boxes, 0, 0, rows, cols, boxes, n, 0}; }
+    size_t pixels(size_t frame_pixels) const { return kind == Frames ? frame_pixels : rows * cols; }      // samples of an item
+    size_t outputs(size_t cnt) const { return kind == Boxes ? n : cnt; }                                  // items, over cnt streams
+    // a window and boxes always go straight to the caller's compact array (single stores where pairs are not aligned); whole
+    // frames only to one that is aligned the way the engine's buffers are
+    bool direct(const void *d_out) const { return kind != Frames || ((uintptr_t) d_out & 255u) == 0; }
+    // the region of the streams lo .. lo + cnt - 1 and its first item: the region itself from item lo, or those streams' boxes -
+    // a contiguous part of the list, which is sorted by frame - with their frames counted from lo
+    DecodeRegion part(size_t lo, size_t cnt, size_t *first) const
     {
-        auto before = [](const ebcc_hip_box &x, size_t frame) { return x.frame < frame; };     // (the list is sorted by frame)
-        const size_t a = (size_t) (std::lower_bound(boxes, boxes + n, frame0 + lo, before) - boxes);
-        const size_t b = (size_t) (std::lower_bound(boxes + a, boxes + n, frame0 + lo + cnt, before) - boxes);
-        if (first) *first = a;
-        return DecodeBoxes{boxes + a, b - a, rows, cols, frame0 + lo};
+        DecodeRegion p = *this;
+        *first = lo;
+        if (kind != Boxes) return p;
+        auto before = [](const ebcc_hip_box &x, size_t frame) { return x.frame < frame; };
+        p.boxes = std::lower_bound(boxes, boxes + n, frame0 + lo, before);
+        p.n = (size_t) (std::lower_bound(p.boxes, boxes + n, frame0 + lo + cnt, before) - p.boxes);
+        p.frame0 = frame0 + lo;
+        *first = (size_t) (p.boxes - boxes);
+        return p;
     }
 };
+// ebcc_decode for a batch of `n` chunk streams of `tiles` frames each, as encode_batch codes them -> the region's items in the
+// device buffer d_out.  Returns 0 or 1 (error); a region that is refused is refused before anything is written.
 int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out, SliceGate *next = nullptr,
-                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr);
+                 size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, const DecodeRegion &region = DecodeRegion{});
 // chunks of several frames (one tiled codestream per chunk): frame heights such a chunk can have, and heights for which
 // every tile has the geometry of a tile at the origin
 bool tile_height_supported(size_t h);

@@ -380,19 +380,14 @@ int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,
 // the decode counterpart (decode overlaps its two layers on the engine's two streams, decode_batch; a second slice hides
 // the host side - parsing, zstd, uploads - of one half behind the kernels of the other when there are hardware queues
 // for four streams)
-// (`win`: the frames' window alone, d_out [n_frames][rows][cols]; `boxes`: the boxes of a box list, d_out [boxes][rows][cols] -
-//  they are in the order of their frames, so a slice's boxes are a contiguous part of the list and of the output)
-int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeWindow *win = nullptr,
-                      const DecodeBoxes *boxes = nullptr)
+// (`region`: d_out holds the output items of these streams; a slice's items are a contiguous part of them, DecodeRegion::part)
+int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeRegion &region = DecodeRegion{})
 {
-    const size_t n_pix = win ? win->pixels() : ctx->n_pix;
+    const size_t n_pix = region.pixels(ctx->n_pix);
     return run_slices(ctx, n_frames, [&](ebcc_hip_ctx *c, size_t lo, size_t cnt, SliceGate *next, unsigned) {
-        if (boxes) {
-            size_t first = 0;
-            const DecodeBoxes part = boxes->part(lo, cnt, &first);
-            return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + first * boxes->pixels(), next, 1, nullptr, nullptr, &part);
-        }
-        return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + lo * n_pix, next, 1, nullptr, win);
+        size_t first = 0;
+        const DecodeRegion part = region.part(lo, cnt, &first);
+        return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + first * n_pix, next, 1, nullptr, part);
     }, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);
 }
 
@@ -537,29 +532,27 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 // The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
 // the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
 // Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
-// `win` (one-frame chunks): the frames' window alone - `out` is [n][rows][cols], and only that crosses to the host.
+// `region`: `out` holds its output items, and only they cross to the host; a batch's items are a contiguous part of them, and
+// the device image holds the most items any batch has.
 int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
-                   float *out, Prefault *prefault, const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr)
+                   float *out, Prefault *prefault, const DecodeRegion &region = DecodeRegion{})
 {
-    const size_t n_pix = win ? win->pixels() : boxes ? boxes->pixels() : ctx->n_pix * tiles;
-    // (`boxes`, one-frame chunks: `out` is [boxes][rows][cols]; a batch's boxes are a contiguous part of it, and the device image
-    //  holds the most boxes any batch has)
-    size_t most = cap;
-    for (size_t lo = 0; boxes && lo < n; lo += cap) most = std::max(most, boxes->part(lo, std::min(cap, n - lo)).n);
+    const size_t n_pix = region.pixels(ctx->n_pix * tiles);
+    size_t most = cap, at = 0;
+    for (size_t lo = 0; lo < n; lo += cap) { const size_t k = std::min(cap, n - lo); most = std::max(most, region.part(lo, k, &at).outputs(k)); }
     auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
         PhaseTimer pt;
-        size_t first = lo, count = k;
-        DecodeBoxes part{};
-        if (boxes) { part = boxes->part(lo, k, &first); count = part.n; }
+        size_t first = 0;
+        const DecodeRegion part = region.part(lo, k, &first);
         float *d = io_buffer(set, most * n_pix * sizeof(float));
         pt.mark("host decode: device image");
-        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, win)
-                                : run_decode_slices(set, streams + lo, sizes + lo, k, d, win, boxes ? &part : nullptr);
+        const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, part)
+                                : run_decode_slices(set, streams + lo, sizes + lo, k, d, part);
         if (r) return r;
         pt.mark("host decode: decode");
         if (prefault) prefault->join();
         pt.mark("host decode: output pages");
-        copy_pageable(set, out + first * n_pix, d, count * n_pix * sizeof(float), true);
+        copy_pageable(set, out + first * n_pix, d, part.outputs(k) * n_pix * sizeof(float), true);
         pt.mark("host decode: download");
         return 0;
     };
@@ -639,58 +632,64 @@ int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, s
         return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * ctx->n_pix; });
     });
 }
-int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n, float *d_out,
-                    const DecodeWindow *win = nullptr, const DecodeBoxes *boxes = nullptr)
-{
-    if (!ctx || !streams || !sizes || !d_out || n < 1) { set_error("%s: bad arguments", who); return 1; }
-    const size_t out_pix = win ? win->pixels() : ctx->n_pix;
-    return on_codec(ctx->device, 1, [&] {
-        return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
-            if (boxes) {
-                size_t first = 0;
-                const DecodeBoxes part = boxes->part(lo, k, &first);
-                return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + first * boxes->pixels(), nullptr, &part);
-            }
-            return run_decode_slices(set, streams + lo, sizes + lo, k, d_out + lo * out_pix, win);
-        });
-    });
-}
-// the window of a window-decode entry point, checked against the context's frames before anything runs (nothing is written
-// for a window that is refused)
-bool window_of(const char *who, const ebcc_hip_ctx *ctx, size_t row0, size_t col0, size_t rows, size_t cols, DecodeWindow &w)
-{
-    if (!ctx) { set_error("%s: bad arguments", who); return false; }
-    const size_t H = (size_t) ctx->height, W = (size_t) ctx->width;
-    if (rows < 1 || cols < 1 || row0 >= H || col0 >= W || rows > H - row0 || cols > W - col0) {
-        set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is empty or not inside the %zu x %zu frame", who, row0, rows, col0, cols, H, W);
-        return false;
-    }
-    w = DecodeWindow{row0, col0, rows, cols};
-    return true;
-}
-
-// The box list of a box-list entry point, checked against the context's frames before anything runs (nothing is written for
-// a list that is refused), and the call it stands for: the streams of the frames the boxes name, in their order, with the
-// boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
+// The box list of a box-list entry point, as the call it stands for: the streams of the frames the boxes name, in their order,
+// with the boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
 struct BoxCall {
     std::vector<const uint8_t *> streams;
     std::vector<size_t> sizes;
     std::vector<ebcc_hip_box> boxes;
-    DecodeBoxes list{};
 };
-bool boxes_of(const char *who, const ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
-              size_t n_boxes, size_t rows, size_t cols, const void *out, BoxCall &call)
+
+// The decode entry points: `region` as the caller states it, and the checks in their order - bad batch (`one_batch`, the _frames
+// forms: at most the context's capacity of frames), bad arguments, a window or a list that does not fit the context's frames
+// (nothing is written for one that is refused) - then run(region, streams, sizes, n) in the device prologue.
+template <class Run>
+int decode_call(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const void *out,
+                DecodeRegion region, bool one_batch, Run &&run)
 {
-    if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return false; }
-    if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return false; }
-    if (!j2k_boxes_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, boxes, n_boxes, rows, cols)) return false;
-    call.boxes.assign(boxes, boxes + n_boxes);
-    for (size_t e = 0; e < n_boxes; e++) {
-        if (e == 0 || boxes[e].frame != boxes[e - 1].frame) { call.streams.push_back(streams[boxes[e].frame]); call.sizes.push_back(sizes[boxes[e].frame]); }
-        call.boxes[e].frame = call.streams.size() - 1;
+    if (one_batch && (!ctx || n_frames < 1 || n_frames > ctx->max_frames)) { set_error("%s: bad batch", who); return 1; }
+    if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return 1; }
+    BoxCall call;
+    if (region.kind == DecodeRegion::Window) {
+        const size_t H = (size_t) ctx->height, W = (size_t) ctx->width, row0 = region.row0, col0 = region.col0, rows = region.rows, cols = region.cols;
+        if (rows < 1 || cols < 1 || row0 >= H || col0 >= W || rows > H - row0 || cols > W - col0) {
+            set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is empty or not inside the %zu x %zu frame", who, row0, rows, col0, cols, H, W);
+            return 1;
+        }
+    } else if (region.kind == DecodeRegion::Boxes) {
+        if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return 1; }
+        if (!j2k_boxes_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.boxes, region.n, region.rows, region.cols)) return 1;
+        call.boxes.assign(region.boxes, region.boxes + region.n);
+        for (size_t e = 0; e < region.n; e++) {
+            const size_t f = region.boxes[e].frame;
+            if (e == 0 || f != region.boxes[e - 1].frame) { call.streams.push_back(streams[f]); call.sizes.push_back(sizes[f]); }
+            call.boxes[e].frame = call.streams.size() - 1;
+        }
+        region.boxes = call.boxes.data();
+        streams = call.streams.data(); sizes = call.sizes.data(); n_frames = call.streams.size();
     }
-    call.list = DecodeBoxes{call.boxes.data(), n_boxes, rows, cols, 0};
-    return true;
+    return on_codec(ctx->device, 1, [&] { return run(region, streams, sizes, n_frames); });
+}
+// device output: batches of the context's capacity on the two sets side by side, each as its slices
+int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out,
+                    const DecodeRegion &asked, bool one_batch)
+{
+    return decode_call(who, ctx, streams, sizes, n_frames, d_out, asked, one_batch, [&](const DecodeRegion &region, const uint8_t *const *st, const size_t *sz, size_t n) {
+        const size_t out_pix = region.pixels(ctx->n_pix);
+        return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            size_t first = 0;
+            const DecodeRegion part = region.part(lo, k, &first);
+            return run_decode_slices(set, st + lo, sz + lo, k, d_out + first * out_pix, part);
+        });
+    });
+}
+// host output: the output's pages are mapped while the GPU decodes
+int decode_host(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_out, const DecodeRegion &asked)
+{
+    return decode_call(who, ctx, streams, sizes, n_frames, h_out, asked, false, [&](const DecodeRegion &region, const uint8_t *const *st, const size_t *sz, size_t n) {
+        Prefault prefault(h_out, region.outputs(n) * region.pixels(ctx->n_pix) * sizeof(float));
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, st, sz, n, h_out, &prefault, region);
+    });
 }
 
 }  // namespace
@@ -817,11 +816,7 @@ int ebcc_hip_encode_host_frames(ebcc_hip_ctx *ctx, const float *h_frames, size_t
 }
 int ebcc_hip_decode_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_frames_out)
 {
-    if (!ctx || !streams || !sizes || !h_frames_out || n_frames < 1) { set_error("ebcc_hip_decode_host_frames: bad arguments"); return 1; }
-    return on_codec(ctx->device, 1, [&] {
-        Prefault prefault(h_frames_out, n_frames * ctx->n_pix * sizeof(float));
-        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_frames_out, &prefault);
-    });
+    return decode_host("ebcc_hip_decode_host_frames", ctx, streams, sizes, n_frames, h_frames_out, DecodeRegion{});
 }
 
 // Window decode: the box [row0, row0 + rows) x [col0, col0 + cols) of every frame, bit for bit the crop of what the entry
@@ -829,28 +824,17 @@ int ebcc_hip_decode_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams
 int ebcc_hip_decode_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
                                   size_t rows, size_t cols, float *d_out)
 {
-    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames_window: bad batch"); return 1; }
-    DecodeWindow w;
-    if (!window_of("ebcc_hip_decode_frames_window", ctx, row0, col0, rows, cols, w)) return 1;
-    return decode_resident("ebcc_hip_decode_frames_window", ctx, streams, sizes, n_frames, d_out, &w);
+    return decode_resident("ebcc_hip_decode_frames_window", ctx, streams, sizes, n_frames, d_out, DecodeRegion::window(row0, col0, rows, cols), true);
 }
 int ebcc_hip_decode_shard_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
                                  size_t rows, size_t cols, float *d_out)
 {
-    DecodeWindow w;
-    if (!window_of("ebcc_hip_decode_shard_window", ctx, row0, col0, rows, cols, w)) return 1;
-    return decode_resident("ebcc_hip_decode_shard_window", ctx, streams, sizes, n_frames, d_out, &w);
+    return decode_resident("ebcc_hip_decode_shard_window", ctx, streams, sizes, n_frames, d_out, DecodeRegion::window(row0, col0, rows, cols), false);
 }
 int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
                                        size_t rows, size_t cols, float *h_out)
 {
-    if (!ctx || !streams || !sizes || !h_out || n_frames < 1) { set_error("ebcc_hip_decode_host_frames_window: bad arguments"); return 1; }
-    DecodeWindow w;
-    if (!window_of("ebcc_hip_decode_host_frames_window", ctx, row0, col0, rows, cols, w)) return 1;
-    return on_codec(ctx->device, 1, [&] {
-        Prefault prefault(h_out, n_frames * w.pixels() * sizeof(float));
-        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n_frames, h_out, &prefault, &w);
-    });
+    return decode_host("ebcc_hip_decode_host_frames_window", ctx, streams, sizes, n_frames, h_out, DecodeRegion::window(row0, col0, rows, cols));
 }
 
 // Box-list decode: boxes of rows x cols, each from the frame it names, bit for bit the crops of what the entry points without
@@ -859,31 +843,21 @@ int ebcc_hip_decode_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *stream
                                  size_t n_boxes, size_t rows, size_t cols, float *d_out)
 {
     EBCC_API_TRY
-    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames_boxes: bad batch"); return 1; }
-    BoxCall call;
-    if (!boxes_of("ebcc_hip_decode_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, call)) return 1;
-    return decode_resident("ebcc_hip_decode_frames_boxes", ctx, call.streams.data(), call.sizes.data(), call.streams.size(), d_out, nullptr, &call.list);
+    return decode_resident("ebcc_hip_decode_frames_boxes", ctx, streams, sizes, n_frames, d_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols), true);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_decode_shard_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
                                 size_t n_boxes, size_t rows, size_t cols, float *d_out)
 {
     EBCC_API_TRY
-    BoxCall call;
-    if (!boxes_of("ebcc_hip_decode_shard_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, call)) return 1;
-    return decode_resident("ebcc_hip_decode_shard_boxes", ctx, call.streams.data(), call.sizes.data(), call.streams.size(), d_out, nullptr, &call.list);
+    return decode_resident("ebcc_hip_decode_shard_boxes", ctx, streams, sizes, n_frames, d_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols), false);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
                                       size_t n_boxes, size_t rows, size_t cols, float *h_out)
 {
     EBCC_API_TRY
-    BoxCall call;
-    if (!boxes_of("ebcc_hip_decode_host_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, h_out, call)) return 1;
-    return on_codec(ctx->device, 1, [&] {
-        Prefault prefault(h_out, n_boxes * call.list.pixels() * sizeof(float));
-        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, call.streams.data(), call.sizes.data(), call.streams.size(), h_out, &prefault, nullptr, &call.list);
-    });
+    return decode_host("ebcc_hip_decode_host_frames_boxes", ctx, streams, sizes, n_frames, h_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols));
     EBCC_API_CATCH(1)
 }
 
@@ -938,8 +912,7 @@ int ebcc_hip_encode_frames(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_fr
 int ebcc_hip_decode_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                            float *d_frames_out)
 {
-    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_decode_frames: bad batch"); return 1; }
-    return decode_resident("ebcc_hip_decode_frames", ctx, streams, sizes, n_frames, d_frames_out);
+    return decode_resident("ebcc_hip_decode_frames", ctx, streams, sizes, n_frames, d_frames_out, DecodeRegion{}, true);
 }
 
 // Any number of frames resident on the device, coded in batches of the context's capacity on two alternating engine sets
@@ -956,7 +929,7 @@ int ebcc_hip_encode_shard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_fra
 int ebcc_hip_decode_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                           float *d_frames_out)
 {
-    return decode_resident("ebcc_hip_decode_shard", ctx, streams, sizes, n_frames, d_frames_out);
+    return decode_resident("ebcc_hip_decode_shard", ctx, streams, sizes, n_frames, d_frames_out, DecodeRegion{}, false);
 }
 
 size_t ebcc_encode(float *data, codec_config_t *config, uint8_t **out_buffer)

@@ -405,7 +405,7 @@ bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, i
 }
 
 bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
-                     uint8_t *keep)
+                     uint8_t *keep, J2kBoxEntry *table, int first_fused)
 {
     const size_t H = (size_t) g.H, W = (size_t) g.W;
     if (!boxes || n_boxes < 1 || rows < 1 || cols < 1) { set_error("%s: an empty box list or empty boxes", who); return false; }
@@ -426,9 +426,15 @@ bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const e
     memset(keep, 0, n_frames * blk.size());
     for (size_t e = 0; e < n_boxes; e++) {
         const ebcc_hip_box &b = boxes[e];
-        if (e && b.frame == boxes[e - 1].frame && b.row0 == boxes[e - 1].row0 && b.col0 == boxes[e - 1].col0) continue;   // (a repeat)
+        const bool repeat = e && b.frame == boxes[e - 1].frame && b.row0 == boxes[e - 1].row0 && b.col0 == boxes[e - 1].col0;
+        if (table) { table[e] = repeat ? table[e - 1] : J2kBoxEntry{(int) b.frame, 0, 0, (int) b.row0, (int) b.col0}; table[e].out = (int) e; }
+        if (repeat) continue;
         J2kWindow w;
         if (!j2k_window_plan(g, b.row0, b.col0, rows, cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
+        for (int r = first_fused; table && r < kJ2kRes; r++) {
+            const J2kStripRange sp = j2k_cone_span(w, r);
+            table[e].strip0[r] = sp.strip0; table[e].strips[r] = sp.strips; table[e].pos0[r] = sp.pos0; table[e].pos1[r] = sp.pos1;
+        }
         uint8_t *row = keep + b.frame * blk.size();
         int rect[4];
         for (size_t i = 0; i < blk.size(); i++)

@@ -199,27 +199,49 @@ bool j2k_window_plan(const J2kGeom &g, size_t row0, size_t col0, size_t rows, si
 bool j2k_window_supported(const J2kGeom &g);    // frames a window decode takes (j2k_analysis.hip)
 // the code-block's rectangle {x0, x1, y0, y1} in its sub-band's coordinates; true if it meets the band's needed rectangle
 bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, int rect[4]);
+// The fused inverse levels (j2k_analysis.hip: j2k_strip_pass) run in strips of kL5Pairs sample pairs of the width, over a range: the
+// strips strip0 .. strip0 + strips - 1 and the vertical positions [pos0, pos1) in `pieces` pieces (pos1 is cut to the level's
+// positions).  j2k_cone_span: the range that holds a cone's samples of resolution r, in one piece (the pieces are the launch's).
+constexpr int kL5Pairs = 60;
+struct J2kStripRange { int strip0, strips, pos0, pos1, pieces; };
+inline J2kStripRange j2k_cone_span(const J2kWindow &w, int r)
+{
+    const int strip0 = (w.rx0[r] / 2) / kL5Pairs;
+    return J2kStripRange{strip0, ((w.rx1[r] - 1) / 2) / kL5Pairs - strip0 + 1, w.ry0[r] / 2, (w.ry1[r] - 1) / 2 + 1, 1};
+}
+// the levels j2k_first_fused(jb) .. kJ2kRes - 1 take the fused pass (sizes grow with r); kJ2kRes: none does
+int j2k_first_fused(const J2kBuffers &jb);
 // Box-list decode: boxes of one size, each cut from the frame it names (j2k_analysis.hip: launch_j2k_box_levels).  A record of
 // the device table is one box of the current round: the frame its code-blocks were decoded for, the slot of jb.B2 that holds
-// its intermediate low-pass bands, its index in the caller's [n_boxes][rows][cols] array, its origin, and for every level the
-// strips and vertical positions its dependency cone holds (J2kStripRange without the piece count, which is the launch's).
+// its intermediate low-pass bands, its index in the caller's [n_boxes][rows][cols] array, its origin, and for every fused level
+// the span of its dependency cone (j2k_cone_span; zero for the levels below the first fused one).
 struct J2kBoxEntry {
     int frame, slot, out, row0, col0;
     int strip0[kJ2kRes], strips[kJ2kRes], pos0[kJ2kRes], pos1[kJ2kRes];
     int pad[3];
 };
-// the boxes of a batch (host): entry[e] with frame, out, row0, col0 set, in any order of frames; `table` / `h_table`: device
-// and pinned room for `n` records
+// the boxes of a batch: `h_table` / `table`: pinned and device room for `n` records, the pinned ones filled by j2k_boxes_check
+// but for the slot, which is the launch's
 struct J2kBoxList {
     J2kBoxEntry *h_table, *table;
     size_t n;
     int rows, cols;
-    float *out;
+};
+// What a decode launch puts out (launch_j2k_decode), as decode_batch plans it once per batch: whole frames to jb.DEC; the
+// window `cone` of every frame to out [n_frames][rows][cols]; or the boxes of `list`, each from the frame it names, to
+// out [n][rows][cols].
+struct J2kRegion {
+    enum Kind { Frames, Window, Boxes } kind = Frames;
+    J2kWindow cone{};
+    J2kBoxList list{};
+    float *out = nullptr;
 };
 // the box list of a box-list entry point against frames of geometry g (include/ebcc_hip.h); false: refused, message set.
-// keep (may be null): [n_frames][g.nblocks], row f the OR of j2k_window_keeps over the boxes of frame f
+// keep (may be null): [n_frames][g.nblocks], row f the OR of j2k_window_keeps over the boxes of frame f.  table (with keep, may
+// be null): record e is box e - frame, out = e, origin, and the spans of its cone for the levels first_fused and above - so a
+// box's cone is planned once.
 bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
-                     uint8_t *keep = nullptr);
+                     uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, int first_fused = kJ2kRes);
 int j2k_selfcheck_div65535();   // mismatches of the division-free s / 65535.0f of the fused inverse level (0 expected)
 
 // ---- launchers (asynchronous on s) ---------------------------------------------------------------
@@ -251,14 +273,11 @@ void launch_j2k_probe_decode(const float *data, const J2kBuffers &jb, int n_fram
 // true decode of codestreams whose packet headers were parsed on the host into jb.dec_table
 // (fs[f].minv/maxv must hold the header's values); result in jb.DEC.  host_table: the host's copy of jb.dec_table, from
 // which the launch sizes its waves (null: the fixed tiers tuned for 256 frames)
-// `win`: only the window of the field, to win_out [n_frames][rows][cols] (jb.dec_table with the entries outside the window's
-// cone zeroed; host_table must be given; j2k_window_supported geometries); jb.DEC is not written
-// `boxes` (instead of `win`): the boxes of a box list, each from the frame it names, to boxes->out [n][rows][cols]; the table
-// entries outside the union of the cones of a frame's boxes have been zeroed
-void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kWindow *win = nullptr,
-                       float *win_out = nullptr, const J2kBoxList *boxes = nullptr);
+// `region` other than whole frames (host_table must be given; j2k_window_supported geometries): jb.DEC is not written, and the
+// entries of jb.dec_table outside the window's cone (the cones of a frame's boxes) have been zeroed
+void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kRegion &region = J2kRegion{});
 // the inverse levels of a box list over the tier-1 decoder's output jb.V (j2k_analysis.hip)
-void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &boxes, hipStream_t s);
+void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &boxes, float *out, hipStream_t s);
 void plan_decode_lanes(const int *host_table, int total, int out[4]);   // (what launch_j2k_decode chooses; ebcc_hip_plan_decode_lanes)
 
 }  // namespace ebcc

@@ -628,14 +628,12 @@ __global__ __launch_bounds__(kFinT) void k_j2k_cols_fin(const float *__restrict_
 // through v_mov_dpp wave shifts, (4) s / 65535.0f is fmaf(s, K_hi, s * K_lo) - equal to the correctly rounded quotient for
 // every integer s in [0, 65535] (div65535_exact; checked exhaustively by ebcc_hip_selfcheck and tests/test_boundary.py),
 // (5) frame samples and field leave / arrive as 8-byte pairs.
-constexpr int kL5Pairs = 60;
 constexpr int kL5MaxWaves = 16;       // strips (waves) of one workgroup
 struct J2kLevelIO {
     const float *ll; int ll_pitch; size_t ll_frame;      // low-pass input (null: from V, level 1)
     float *out; int out_pitch; size_t out_frame;         // J2kSinkNextLevel only
     int r;
 };
-struct J2kStripRange { int strip0, strips, pos0, pos1, pieces; };    // (pos1 is cut to the level's positions)
 constexpr int kToLevelEnd = 0x7fffffff;                  // pos1 of a range that runs to the level's last position
 struct J2kWinOut { float *out; int row0, col0, rows, cols; };
 // what a sink is told about its lane: the pair i (columns 2i, 2i + 1) of frame `frame`, the level's extent, and the
@@ -1877,6 +1875,36 @@ void launch_j2k_analysis(const float *data, const J2kBuffers &jb, int n_frames, 
     EBCC_HIP_LAUNCH_CHECK();
 }
 
+// The fused inverse levels of a geometry: from the first level that is large enough up to the top (cas == 0 single-tile frames;
+// the lower ones alternate between two buffers, the top one leaves a statistics partial per strip and piece).
+int j2k_first_fused(const J2kBuffers &jb)
+{
+    const J2kGeom &g = jb.geom;
+    auto fusable = [&](int r) {
+        return g.period == 1 && g.ry0[r] % 2 == 0 && g.rw[r - 1] >= 2 && g.rh[r - 1] >= 1 &&
+               (r == kJ2kRes - 1 ? ceil_div(g.rw[r - 1], kL5Pairs) <= kPartials : jb.B2 != nullptr);
+    };
+    int first_fused = kJ2kRes;
+    for (int r = kJ2kRes - 1; r >= 1 && fusable(r); r--) first_fused = r;
+    return first_fused;
+}
+
+// The launch of one fused level over `strips` strips and `span` vertical positions of each of `tiles` (frame or box) tiles: the
+// pieces the positions are cut into, and the grid - tile blockIdx.y = piece * tiles + tile.
+struct J2kLevelGrid { int pieces; dim3 grid, block; };
+static J2kLevelGrid j2k_level_grid(int strips, int span, int tiles, bool top, int piece_cap)
+{
+    // (the top level in more, shorter pieces: a piece is what an infeasible probe can skip)
+    int pieces = std::max(1, std::min({top ? 8 : 4, piece_cap, span / 16}));
+    while (pieces > 1 && (long long) tiles * pieces > 65535) pieces--;   // (grid y)
+    // neighbouring strips of a tile as the waves of one workgroup, four at a time (measured per 128-frame probe round,
+    // tools/gpu/kstat.sh: 1 wave 231 us, 4 waves 220, 6 waves 258, all 12 strips 264 - a large workgroup needs all
+    // its wave slots free on one CU at once)
+    const int wave_cap = 4;
+    const int wg = std::min(strips, wave_cap);
+    return J2kLevelGrid{pieces, dim3((unsigned) ceil_div(strips, wg), (unsigned) (tiles * pieces)), dim3(64 * wg)};
+}
+
 // dequantisation + inverse transform of the tier-1 decoder's output V through the tile buffers B to the decoded
 // field jb.DEC, with the error statistics against `data` (if given) left as partial sums per frame; used by both
 // decode flavours (j2k_rate.hip).  Returns the number of partials per frame.
@@ -1893,12 +1921,7 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     // below it and tiles at odd offsets use the separate LDS-staged row / column passes in place.
     const J2kGeom &g = jb.geom;
     const size_t n_pix = (size_t) g.W * g.H;
-    auto fusable = [&](int r) {
-        return V && g.period == 1 && g.ry0[r] % 2 == 0 && g.rw[r - 1] >= 2 && g.rh[r - 1] >= 1 &&
-               (r == kJ2kRes - 1 ? ceil_div(g.rw[r - 1], kL5Pairs) <= kPartials : jb.B2 != nullptr);
-    };
-    int first_fused = kJ2kRes;                                          // levels first_fused .. top are fused (sizes grow with r)
-    for (int r = kJ2kRes - 1; r >= 1 && fusable(r); r--) first_fused = r;
+    const int first_fused = V ? j2k_first_fused(jb) : kJ2kRes;          // levels first_fused .. top are fused
     if (win && first_fused == kJ2kRes) throw std::runtime_error("window decode: this geometry has no fused top level");
     const float *ll = nullptr;                                          // low-pass input of the next fused level (null: from V)
     float *spare = jb.B2;
@@ -1907,32 +1930,22 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
             const bool top = r == kJ2kRes - 1;
             // the part of the level to run: all of it, or the strips and vertical positions that hold the window's cone
             J2kStripRange range{0, ceil_div(g.rw[r - 1], kL5Pairs), 0, g.rh[r - 1], 1};
-            if (win) {
-                range.strip0 = (win->rx0[r] / 2) / kL5Pairs; range.strips = ((win->rx1[r] - 1) / 2) / kL5Pairs - range.strip0 + 1;
-                range.pos0 = win->ry0[r] / 2; range.pos1 = (win->ry1[r] - 1) / 2 + 1;
-            }
-            const int piece_cap = win ? kPartials : kPartials / range.strips;   // (whole frame: a statistics partial per strip and piece)
-            // (the top level in more, shorter pieces: a piece is what an infeasible probe can skip)
-            range.pieces = std::max(1, std::min({top ? 8 : 4, piece_cap, (range.pos1 - range.pos0) / 16}));
-            while (range.pieces > 1 && (long long) n_frames * range.pieces > 65535) range.pieces--;   // (grid y)
-            // neighbouring strips of a tile as the waves of one workgroup, four at a time (measured per 128-frame probe round,
-            // tools/gpu/kstat.sh: 1 wave 231 us, 4 waves 220, 6 waves 258, all 12 strips 264 - a large workgroup needs all
-            // its wave slots free on one CU at once)
-            const int wave_cap = 4;
-            const int wg = std::min(range.strips, wave_cap);
-            const dim3 grid((unsigned) ceil_div(range.strips, wg), (unsigned) (n_frames * range.pieces)), block(64 * wg);
+            if (win) range = j2k_cone_span(*win, r);
+            // (whole frame: a statistics partial per strip and piece)
+            const J2kLevelGrid lg = j2k_level_grid(range.strips, range.pos1 - range.pos0, n_frames, top, win ? kPartials : kPartials / range.strips);
+            range.pieces = lg.pieces;
             if (r > 1 && !ll) ll = B;                                   // (the separate passes below left their result in B)
             J2kLevelIO io{ll, g.W, n_pix, nullptr, g.W, n_pix, r};
             if (!top) {
                 io.out = ll == spare ? B : spare;                         // never the buffer the level reads from
-                hipLaunchKernelGGL(k_j2k_level5_fin<false>, grid, block, 0, s, io, V, jb.d_geom, fs, active, J2kFinish{}, range, n_frames);
+                hipLaunchKernelGGL(k_j2k_level5_fin<false>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, active, J2kFinish{}, range, n_frames);
                 ll = io.out;
             } else if (win) {
-                hipLaunchKernelGGL(k_j2k_level_win, grid, block, 0, s, io, V, jb.d_geom, fs, J2kWinOut{win_out, win->row0, win->col0, win->rows, win->cols},
+                hipLaunchKernelGGL(k_j2k_level_win, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, J2kWinOut{win_out, win->row0, win->col0, win->rows, win->cols},
                                    range, n_frames);
             } else {
                 partials = range.strips * range.pieces;
-                hipLaunchKernelGGL(k_j2k_level5_fin<true>, grid, block, 0, s, io, V, jb.d_geom, fs, active, fin, range, n_frames);
+                hipLaunchKernelGGL(k_j2k_level5_fin<true>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, active, fin, range, n_frames);
             }
             continue;
         }
@@ -1950,19 +1963,14 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
 // even pitch at frame coordinates; together under half a frame), so two boxes of one frame never share a band.  More boxes
 // than slots run as rounds of jb.max_frames entries: five launches a round, on one stream, so a slot is reused only after the
 // round before has read it - what an earlier entry left outside the new cone is read and dropped like any position outside
-// a cone.  The records of all rounds are made here and sent as one copy.
-void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &bl, hipStream_t s)
+// a cone.  The records of all rounds (j2k_boxes_check) get their slots here and are sent as one copy.
+void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &bl, float *out, hipStream_t s)
 {
     const J2kGeom &g = jb.geom;
     const size_t n_pix = (size_t) g.W * g.H;
     const int32_t *V = jb.V;
     const FrameState *fs = jb.fs;
-    auto fusable = [&](int r) {
-        return g.period == 1 && g.ry0[r] % 2 == 0 && g.rw[r - 1] >= 2 && g.rh[r - 1] >= 1 &&
-               (r == kJ2kRes - 1 ? ceil_div(g.rw[r - 1], kL5Pairs) <= kPartials : jb.B2 != nullptr);
-    };
-    int first_fused = kJ2kRes;
-    for (int r = kJ2kRes - 1; r >= 1 && fusable(r); r--) first_fused = r;
+    const int first_fused = j2k_first_fused(jb);
     if (first_fused == kJ2kRes) throw std::runtime_error("box decode: this geometry has no fused top level");
     for (int r = 1; r < first_fused; r++) {
         dwt_rows<false>(jb.B, V, jb, r, n_frames, fs, nullptr, s);
@@ -1977,19 +1985,7 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
     }
     if (used > n_pix) throw std::runtime_error("box decode: the level bands of a box do not fit its slot");
     const size_t cap = (size_t) jb.max_frames;
-    for (size_t e = 0; e < bl.n; e++) {
-        J2kBoxEntry &b = bl.h_table[e];
-        J2kWindow w;
-        if (!j2k_window_plan(g, (size_t) b.row0, (size_t) b.col0, (size_t) bl.rows, (size_t) bl.cols, w)) throw std::runtime_error("box decode: a box is not inside the frame");
-        b.slot = (int) (e % cap);
-        for (int r = 0; r < kJ2kRes; r++) {
-            b.strip0[r] = b.strips[r] = b.pos0[r] = b.pos1[r] = 0;
-            if (r < first_fused) continue;
-            b.strip0[r] = (w.rx0[r] / 2) / kL5Pairs; b.strips[r] = ((w.rx1[r] - 1) / 2) / kL5Pairs - b.strip0[r] + 1;
-            b.pos0[r] = w.ry0[r] / 2; b.pos1[r] = (w.ry1[r] - 1) / 2 + 1;
-        }
-        b.pad[0] = b.pad[1] = b.pad[2] = 0;
-    }
+    for (size_t e = 0; e < bl.n; e++) bl.h_table[e].slot = (int) (e % cap);
     EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * sizeof(J2kBoxEntry), hipMemcpyHostToDevice, s));
     for (size_t lo = 0; lo < bl.n; lo += cap) {
         const int n = (int) std::min(cap, bl.n - lo);
@@ -2000,15 +1996,12 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
                 const J2kBoxEntry &b = bl.h_table[lo + e];
                 strips = std::max(strips, b.strips[r]); span = std::max(span, b.pos1[r] - b.pos0[r]);
             }
-            int pieces = std::max(1, std::min({top ? 8 : 4, kPartials, span / 16}));
-            while (pieces > 1 && (long long) n * pieces > 65535) pieces--;   // (grid y)
-            const int wg = std::min(strips, 4);                              // (wave_cap of j2k_inverse_dwt)
-            const dim3 grid((unsigned) ceil_div(strips, wg), (unsigned) (n * pieces)), block(64 * wg);
+            const J2kLevelGrid lg = j2k_level_grid(strips, span, n, top, kPartials);
             const bool from_frames = r == first_fused;                       // (its low-pass input: V, or the band in jb.B)
             J2kLevelIO io{from_frames ? (r > 1 ? jb.B : nullptr) : jb.B2 + off[r - 1], from_frames ? g.W : pitch[r - 1], n_pix,
                           top ? nullptr : jb.B2 + off[r], top ? g.W : pitch[r], n_pix, r};
-            if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, grid, block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, pieces, from_frames ? 1 : 0, bl.out, bl.rows, bl.cols);
-            else hipLaunchKernelGGL(k_j2k_level_box<false>, grid, block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, pieces, from_frames ? 1 : 0, bl.out, bl.rows, bl.cols);
+            if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
+            else hipLaunchKernelGGL(k_j2k_level_box<false>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
         }
     }
     EBCC_HIP_LAUNCH_CHECK();

@@ -1734,8 +1734,7 @@ void plan_decode_lanes(const int *host_table, int total, int out[4])
     out[3] = t.lanes[3];
 }
 
-void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table, const J2kWindow *win, float *win_out,
-                       const J2kBoxList *boxes)
+void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table, const J2kRegion &region)
 {
     const size_t n_pix = (size_t) jb.geom.W * jb.geom.H;
     const int total = n_frames * jb.geom.stride;
@@ -1745,7 +1744,7 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
     // from those entries alone: a small window has few, short chains and lands on the one-lane shape by the same model.
     int live = total;
     std::vector<int> live_table;
-    const bool part = win || boxes;
+    const bool part = region.kind != J2kRegion::Frames;
     if (part && host_table) {
         for (int i = 0; i < total; i++) {
             const int *e = host_table + (size_t) i * 4;
@@ -1822,8 +1821,8 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
                            jb.stream_cap, jb.dec_table, jb.dec_order, jb.V, jb.d_geom, jb.d_blocks, jb.fs, live, tiers);
     }
     timing_end("t1_decode", s);
-    if (boxes) launch_j2k_box_levels(jb, n_frames, *boxes, s);
-    else decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, win, win_out);
+    if (region.kind == J2kRegion::Boxes) launch_j2k_box_levels(jb, n_frames, region.list, region.out, s);
+    else decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, part ? &region.cone : nullptr, region.out);
     EBCC_HIP_LAUNCH_CHECK();
 }
 

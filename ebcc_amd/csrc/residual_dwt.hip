@@ -234,21 +234,18 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
 }
 
 // The decoder's last synthesis pass: out += r (ebcc_codec.c:1307) for the box [row0, row0 + rows) x [col0, col0 + cols) of the
-// image - all of it, or the window of a window decode - with `out` the compact [frame][rows][cols] array.  Only the box's rows
-// are synthesised, each of them whole (a row is one lifting chain; its samples outside the box are its halo), so a sample
-// has the same bits whatever the box.
-__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__restrict__ src, int stride, size_t frame_stride, int n,
-                                                               const int *active, const FrameState *fs, float *out, int row0, int col0,
-                                                               int rows, int cols)
+// grid of `frame`, added to the compact box out[out_index] of [rows][cols].  Only the box's rows are synthesised, each of them
+// whole (a row is one lifting chain; its samples outside the box are its halo), so a sample has the same bits whatever the box.
+__device__ __forceinline__ void rows_inv_add_body(const float *__restrict__ src, int stride, size_t frame_stride, int n, const int *active,
+                                                  const FrameState *fs, float *out, int frame, int out_index, int row0, int col0, int rows, int cols)
 {
     extern __shared__ float sm[];
-    const int frame = blockIdx.y;
     if (active && !active[frame]) return;
     const int half = n >> 1;
     float *E = sm, *O = sm + half;
     src += (size_t) frame * frame_stride;
     const int tid = threadIdx.x;
-    float *o = out + (size_t) frame * ((size_t) rows * (size_t) cols);
+    float *o = out + (size_t) out_index * ((size_t) rows * (size_t) cols);
     const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
     for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
         const float *s = src + (size_t) (row0 + wy) * stride;
@@ -268,39 +265,21 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__res
     }
 }
 
-// k_rows_inv_add for the boxes of a box list: workgroups (x, e) synthesise the rows of box e - rows row0 .. row0 + rows - 1 of
-// the grid of the frame the record names - and add the record's columns to box out[e.out].  The same row, the same chain, the
-// same bits as in the whole frame.
+// the same box of every frame - the whole image, or the window of a window decode: workgroups (x, frame), out [frame][rows][cols]
+__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__restrict__ src, int stride, size_t frame_stride, int n,
+                                                               const int *active, const FrameState *fs, float *out, int row0, int col0,
+                                                               int rows, int cols)
+{
+    rows_inv_add_body(src, stride, frame_stride, n, active, fs, out, blockIdx.y, blockIdx.y, row0, col0, rows, cols);
+}
+
+// the boxes of a box list: workgroups (x, e) take frame and origin from record e and add to box out[e.out]
 __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_box(const float *__restrict__ src, int stride, size_t frame_stride, int n,
                                                                    const int *active, const FrameState *fs, float *out,
                                                                    const J2kBoxEntry *__restrict__ boxes, int rows, int cols)
 {
-    extern __shared__ float sm[];
     const J2kBoxEntry &e = boxes[blockIdx.y];
-    const int frame = e.frame, row0 = e.row0, col0 = e.col0;
-    if (active && !active[frame]) return;
-    const int half = n >> 1;
-    float *E = sm, *O = sm + half;
-    src += (size_t) frame * frame_stride;
-    const int tid = threadIdx.x;
-    float *o = out + (size_t) e.out * ((size_t) rows * (size_t) cols);
-    const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
-    for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
-        const float *s = src + (size_t) (row0 + wy) * stride;
-        for (int k = tid; k < half; k += kRowThreads) {
-            E[k] = s[k];
-            O[k] = s[half + k];
-        }
-        __syncthreads();
-        lift_inverse_tile(E, O, half, 1, RowIdx(), tid, kRowThreads);
-        for (int wx = tid; wx < cols; wx += kRowThreads) {
-            const int xx = col0 + wx;
-            const float r = residual_value((xx & 1) ? O[xx >> 1] : E[xx >> 1], dc, rmin, rng);
-            const size_t i = (size_t) wy * (size_t) cols + (size_t) wx;
-            o[i] = o[i] + r;
-        }
-        __syncthreads();
-    }
+    rows_inv_add_body(src, stride, frame_stride, n, active, fs, out, e.frame, e.out, e.row0, e.col0, rows, cols);
 }
 
 __global__ __launch_bounds__(kRowThreads) void k_rows_inv(const float *__restrict__ src, float *__restrict__ dst,

@@ -40,6 +40,37 @@ def frame_config(height, width, base_cr, residual_opt=("none", None)):
     return c
 
 
+def _stream_arrays(streams, named=None):
+    """(the streams as bytes - the caller keeps them alive for the call -, their ctypes pointer array, their size array);
+    `named`: only the streams at these indices are read, the others (None allowed) become a null pointer of size 0"""
+    n = len(streams)
+    kept = [None if named is not None and i not in named else (s if isinstance(s, bytes) else bytes(s)) for i, s in enumerate(streams)]
+    ptrs = (ctypes.c_void_p * n)(*[None if s is None else ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in kept])
+    sizes = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in kept])
+    return kept, ptrs, sizes
+
+
+def _box_array(boxes):
+    """`boxes` as an int64 array (k, 3) of (frame, row0, col0)"""
+    b = np.asarray(boxes)
+    if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
+        raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
+    return b.astype(np.int64)
+
+
+def _read_chunks(dset, frames):
+    """The raw chunks of the frames `frames` (counted in C order over the leading axes) of a one-frame-per-chunk dataset"""
+    lead = dset.shape[:-2]
+    raw = []
+    for f in frames:
+        idx = np.unravel_index(int(f), lead) if lead else ()
+        mask, chunk = dset.id.read_direct_chunk(tuple(int(v) for v in idx) + (0, 0))
+        if mask:
+            raise ValueError(f"chunk {idx} was stored with filters disabled (mask {mask})")
+        raw.append(chunk)
+    return raw
+
+
 class BatchCodec:
     """Device engine for stacks of (H, W) float32 frames held in host memory."""
 
@@ -74,7 +105,10 @@ class BatchCodec:
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
         self.ctx = lib.ebcc_hip_create(device, self.max_frames, self.h, self.w)
         if not self.ctx:
-            raise RuntimeError("EBCC MI355X engine: " + (lib.ebcc_hip_last_error() or b"?").decode())
+            self._fail("EBCC MI355X engine")
+
+    def _fail(self, name):
+        raise RuntimeError(name + ": " + (self.lib.ebcc_hip_last_error() or b"?").decode())
 
     def close(self):
         if self.ctx:
@@ -97,7 +131,7 @@ class BatchCodec:
         outs = (ctypes.c_void_p * n)()
         sizes = (ctypes.c_size_t * n)()
         if self.lib.ebcc_hip_encode_host_frames(self.ctx, frames.ctypes.data, n, ctypes.byref(cfg), outs, sizes):
-            raise RuntimeError("ebcc_hip_encode_host_frames: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
+            self._fail("ebcc_hip_encode_host_frames")
         res = []
         for i in range(n):
             res.append(ctypes.string_at(outs[i], sizes[i]))
@@ -112,10 +146,7 @@ class BatchCodec:
         downloaded."""
         n = len(streams)
         assert n >= 1
-        streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
-        # (pointers into the bytes objects themselves: they stay alive in `streams` for the duration of the call)
-        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
-        sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        streams, ptrs, sizes = _stream_arrays(streams)
         if window is not None:
             row0, col0, rows, cols = (int(v) for v in window)
             if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > self.h or col0 + cols > self.w:
@@ -124,14 +155,14 @@ class BatchCodec:
                 out = np.empty((n, rows, cols), np.float32)
             assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == n * rows * cols
             if self.lib.ebcc_hip_decode_host_frames_window(self.ctx, ptrs, sizes, n, row0, col0, rows, cols, out.ctypes.data):
-                raise RuntimeError("ebcc_hip_decode_host_frames_window: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
+                self._fail("ebcc_hip_decode_host_frames_window")
             return out
         if out is None:
             out = np.empty((n, self.h, self.w), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == n * self.h * self.w
         t0 = time.perf_counter()
         if self.lib.ebcc_hip_decode_host_frames(self.ctx, ptrs, sizes, n, out.ctypes.data):
-            raise RuntimeError("ebcc_hip_decode_host_frames: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
+            self._fail("ebcc_hip_decode_host_frames")
         if os.environ.get("EBCC_H5_TIMING"):
             print(f"h5_batch.decode: {n} frames decoded and downloaded in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
         return out
@@ -145,10 +176,7 @@ class BatchCodec:
         RuntimeError for what the call itself reports, such as a malformed stream."""
         n = len(streams)
         rows, cols = int(rows), int(cols)
-        b = np.asarray(boxes)
-        if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
-            raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
-        b = b.astype(np.int64)
+        b = _box_array(boxes)
         if rows < 1 or cols < 1 or rows > self.h or cols > self.w:
             raise ValueError(f"boxes of {rows} x {cols} are empty or not inside the {self.h} x {self.w} frame")
         if b.min() < 0 or (b[:, 0] >= n).any():
@@ -158,16 +186,13 @@ class BatchCodec:
         if (np.diff(b[:, 0]) < 0).any():
             raise ValueError("boxes must be in non-decreasing order of their frames")
         k = len(b)
-        named = set(int(f) for f in np.unique(b[:, 0]))
-        streams = [None if i not in named else (s if isinstance(s, bytes) else bytes(s)) for i, s in enumerate(streams)]
-        ptrs = (ctypes.c_void_p * n)(*[None if s is None else ctypes.cast(ctypes.c_char_p(s), ctypes.c_void_p).value for s in streams])
-        sizes = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in streams])
+        streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.unique(b[:, 0])))
         table = np.ascontiguousarray(b, np.uint64)                       # == ebcc_hip_box[k]
         if out is None:
             out = np.empty((k, rows, cols), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == k * rows * cols
         if self.lib.ebcc_hip_decode_host_frames_boxes(self.ctx, ptrs, sizes, n, table.ctypes.data, k, rows, cols, out.ctypes.data):
-            raise RuntimeError("ebcc_hip_decode_host_frames_boxes: " + (self.lib.ebcc_hip_last_error() or b"?").decode())
+            self._fail("ebcc_hip_decode_host_frames_boxes")
         return out
 
 
@@ -263,14 +288,7 @@ def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
 
     def fetch(lo, box):
         try:
-            raw = []
-            for i in range(lo, min(n, lo + step)):
-                idx = np.unravel_index(i, lead) if lead else ()
-                mask, chunk = dset.id.read_direct_chunk(tuple(int(v) for v in idx) + (0, 0))
-                if mask:
-                    raise ValueError(f"chunk {idx} was stored with filters disabled (mask {mask})")
-                raw.append(chunk)
-            box.append(raw)
+            box.append(_read_chunks(dset, range(lo, min(n, lo + step))))
         except BaseException as e:                                  # (handed to the caller's thread)
             box.append(e)
 
@@ -303,10 +321,7 @@ def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):
     h, w = dset.shape[-2:]
     lead = dset.shape[:-2]
     n = int(np.prod(lead)) if lead else 1
-    b = np.asarray(boxes)
-    if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
-        raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
-    b = b.astype(np.int64)
+    b = _box_array(boxes)
     if b[:, 0].min() < 0 or b[:, 0].max() >= n:
         raise ValueError(f"a box names a frame outside the {n} frames of the dataset")
     order = np.argsort(b[:, 0], kind="stable")
@@ -317,13 +332,7 @@ def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):
     step = _SUPER * codec.max_frames
     for lo in range(0, len(frames), step):
         part = frames[lo:lo + step]
-        raw = []
-        for f in part:
-            idx = np.unravel_index(int(f), lead) if lead else ()
-            mask, chunk = dset.id.read_direct_chunk(tuple(int(v) for v in idx) + (0, 0))
-            if mask:
-                raise ValueError(f"chunk {idx} was stored with filters disabled (mask {mask})")
-            raw.append(chunk)
+        raw = _read_chunks(dset, part)
         e0, e1 = np.searchsorted(b[:, 0], part[0], "left"), np.searchsorted(b[:, 0], part[-1], "right")
         local = b[e0:e1].copy()
         local[:, 0] = np.searchsorted(part, local[:, 0])
