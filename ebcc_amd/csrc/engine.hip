@@ -157,15 +157,15 @@ void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m) 
 
 void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes)
 {
-    if (n <= ctx->boxes_cap) return;
+    if (n * bytes <= ctx->boxes_cap) return;
     void *h_old = ctx->h_boxes, *d_old = ctx->d_boxes;
     ctx->h_boxes = nullptr; ctx->d_boxes = nullptr; ctx->boxes_cap = 0;
     if (h_old) hipHostFree(h_old);
     if (d_old) hipFree(d_old);
-    const size_t cap = n + n / 2 + 64;
+    const size_t cap = (n + n / 2 + 64) * bytes;
     void *h_new = nullptr, *d_new = nullptr;
-    EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap * bytes));
-    const hipError_t e = device_malloc(&d_new, cap * bytes);
+    EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap));
+    const hipError_t e = device_malloc(&d_new, cap);
     if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
     ctx->h_boxes = h_new; ctx->d_boxes = d_new; ctx->boxes_cap = cap;
 }

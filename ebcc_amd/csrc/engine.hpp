@@ -47,7 +47,7 @@ struct ebcc_hip_ctx {
     size_t io_cap = 0;                      // bytes
     uint8_t *h_bounce = nullptr;            // 2 x kBounceBytes pinned: pageable host arrays cross PCIe through it (host_codec.hip)
     unsigned long long *h_pack = nullptr, *d_pack = nullptr;   // [2 pieces per frame][offset, length]
-    void *h_boxes = nullptr, *d_boxes = nullptr;               // [boxes_cap] J2kBoxEntry (j2k.hpp): the entry table of a box-list decode, pinned and on the device (made on first use)
+    void *h_boxes = nullptr, *d_boxes = nullptr;               // boxes_cap bytes: the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use)
     size_t boxes_cap = 0;
     ebcc::CutSlots cut{};                   // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
     bool cut_failed = false;                // (no memory for it: the search probes one cut per round)
@@ -70,7 +70,7 @@ void stage_download(ebcc_hip_ctx *ctx, const uint8_t *src, size_t stride, const 
 void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m);
 void stage_send(ebcc_hip_ctx *ctx, size_t m, hipStream_t s);
 void stage_scatter(ebcc_hip_ctx *ctx, uint8_t *dst, size_t stride, size_t first, size_t count, hipStream_t s);
-// room for n records of `bytes` each in ctx->h_boxes / d_boxes (grown rarely: sized by the longest box list seen)
+// room for n records of `bytes` each in ctx->h_boxes / d_boxes (grown rarely: sized by the largest table seen)
 void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes);
 
 // cut slots for `capacity` simultaneous probes (residual.hpp); false: not available (unsupported grid or no memory)

@@ -3,6 +3,7 @@
 // container (/root/reference/src/ebcc_codec.c:920-1090, :1322-1449), and the batch entry points of include/ebcc_hip.h.
 // The frame codec itself is batch_codec.hip, the HDF5 plugin h5z_filter.hip, the host services host_pool.hip (host.hpp).
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
+#include <climits>
 #include "host.hpp"
 
 using namespace ebcc;
@@ -383,11 +384,10 @@ int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,
 // (`region`: d_out holds the output items of these streams; a slice's items are a contiguous part of them, DecodeRegion::part)
 int run_decode_slices(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *d_out, const DecodeRegion &region = DecodeRegion{})
 {
-    const size_t n_pix = region.pixels(ctx->n_pix);
     return run_slices(ctx, n_frames, [&](ebcc_hip_ctx *c, size_t lo, size_t cnt, SliceGate *next, unsigned) {
         size_t first = 0;
         const DecodeRegion part = region.part(lo, cnt, &first);
-        return decode_batch(c, streams + lo, sizes + lo, cnt, d_out + first * n_pix, next, 1, nullptr, part);
+        return decode_batch(c, streams + lo, sizes + lo, cnt, region.at(d_out, first, ctx->n_pix), next, 1, nullptr, part);
     }, "EBCC_HIP_DECODE_SLICES", kDefaultDecodeSlices);
 }
 
@@ -533,7 +533,23 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 // the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
 // Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
 // `region`: `out` holds its output items, and only they cross to the host; a batch's items are a contiguous part of them, and
-// the device image holds the most items any batch has.
+// the device image holds the most items any batch has.  Placed boxes: a batch's boxes lie compact in the device image, one
+// behind the other at pitch `cols` (PlacedStage), cross as one download into a host image of the same layout, and are put into
+// their rectangles of `out` row by row - nothing else of `out` is touched.
+struct PlacedStage {
+    std::vector<ebcc_hip_placed_box> boxes;
+    size_t floats = 0;
+    PlacedStage(const ebcc_hip_placed_box *list, size_t n) : boxes(list, list + n)
+    {
+        for (ebcc_hip_placed_box &b : boxes) { b.out_offset = floats; b.out_pitch = b.cols; floats += b.rows * b.cols; }
+    }
+    void place(const ebcc_hip_placed_box *list, const float *image, float *out) const
+    {
+        for (size_t e = 0; e < boxes.size(); e++)
+            for (size_t y = 0; y < list[e].rows; y++)
+                memcpy(out + list[e].out_offset + y * list[e].out_pitch, image + boxes[e].out_offset + y * boxes[e].cols, list[e].cols * sizeof(float));
+    }
+};
 int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const uint8_t *const *streams, const size_t *sizes, size_t n,
                    float *out, Prefault *prefault, const DecodeRegion &region = DecodeRegion{})
 {
@@ -544,6 +560,21 @@ int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap
         PhaseTimer pt;
         size_t first = 0;
         const DecodeRegion part = region.part(lo, k, &first);
+        if (part.kind == DecodeRegion::Placed) {
+            if (part.n == 0) return 0;
+            const PlacedStage stage(part.placed, part.n);
+            DecodeRegion staged = part;
+            staged.placed = stage.boxes.data(); staged.out_floats = stage.floats;
+            float *d = io_buffer(set, stage.floats * sizeof(float));
+            const int r = run_decode_slices(set, streams + lo, sizes + lo, k, d, staged);
+            if (r) return r;
+            pt.mark("host decode: decode");
+            std::vector<float> image(stage.floats);
+            copy_pageable(set, image.data(), d, stage.floats * sizeof(float), true);
+            stage.place(part.placed, image.data(), out);
+            pt.mark("host decode: download");
+            return 0;
+        }
         float *d = io_buffer(set, most * n_pix * sizeof(float));
         pt.mark("host decode: device image");
         const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, part)
@@ -638,24 +669,33 @@ struct BoxCall {
     std::vector<const uint8_t *> streams;
     std::vector<size_t> sizes;
     std::vector<ebcc_hip_box> boxes;
+    std::vector<ebcc_hip_placed_box> placed;
 };
 
 // The decode entry points: `region` as the caller states it, and the checks in their order - bad batch (`one_batch`, the _frames
 // forms: at most the context's capacity of frames), bad arguments, a window or a list that does not fit the context's frames
 // (nothing is written for one that is refused) - then run(region, streams, sizes, n) in the device prologue.
-template <class Run>
-int decode_call(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const void *out,
-                DecodeRegion region, bool one_batch, Run &&run)
+// (decode_region: the checks of the region alone, which also turn a list into its BoxCall - for a caller that holds the device)
+int decode_region(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *&streams, const size_t *&sizes, size_t &n_frames, DecodeRegion &region,
+                  BoxCall &call)
 {
-    if (one_batch && (!ctx || n_frames < 1 || n_frames > ctx->max_frames)) { set_error("%s: bad batch", who); return 1; }
-    if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return 1; }
-    BoxCall call;
     if (region.kind == DecodeRegion::Window) {
         const size_t H = (size_t) ctx->height, W = (size_t) ctx->width, row0 = region.row0, col0 = region.col0, rows = region.rows, cols = region.cols;
         if (rows < 1 || cols < 1 || row0 >= H || col0 >= W || rows > H - row0 || cols > W - col0) {
             set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is empty or not inside the %zu x %zu frame", who, row0, rows, col0, cols, H, W);
             return 1;
         }
+    } else if (region.kind == DecodeRegion::Placed) {
+        if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return 1; }
+        if (!j2k_placed_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.placed, region.n, region.out_floats)) return 1;
+        call.placed.assign(region.placed, region.placed + region.n);
+        for (size_t e = 0; e < region.n; e++) {
+            const size_t f = region.placed[e].frame;
+            if (e == 0 || f != region.placed[e - 1].frame) { call.streams.push_back(streams[f]); call.sizes.push_back(sizes[f]); }
+            call.placed[e].frame = call.streams.size() - 1;
+        }
+        region.placed = call.placed.data();
+        streams = call.streams.data(); sizes = call.sizes.data(); n_frames = call.streams.size();
     } else if (region.kind == DecodeRegion::Boxes) {
         if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return 1; }
         if (!j2k_boxes_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.boxes, region.n, region.rows, region.cols)) return 1;
@@ -668,6 +708,16 @@ int decode_call(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *stream
         region.boxes = call.boxes.data();
         streams = call.streams.data(); sizes = call.sizes.data(); n_frames = call.streams.size();
     }
+    return 0;
+}
+template <class Run>
+int decode_call(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const void *out,
+                DecodeRegion region, bool one_batch, Run &&run)
+{
+    if (one_batch && (!ctx || n_frames < 1 || n_frames > ctx->max_frames)) { set_error("%s: bad batch", who); return 1; }
+    if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return 1; }
+    BoxCall call;
+    if (decode_region(who, ctx, streams, sizes, n_frames, region, call)) return 1;
     return on_codec(ctx->device, 1, [&] { return run(region, streams, sizes, n_frames); });
 }
 // device output: batches of the context's capacity on the two sets side by side, each as its slices
@@ -675,11 +725,10 @@ int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *st
                     const DecodeRegion &asked, bool one_batch)
 {
     return decode_call(who, ctx, streams, sizes, n_frames, d_out, asked, one_batch, [&](const DecodeRegion &region, const uint8_t *const *st, const size_t *sz, size_t n) {
-        const size_t out_pix = region.pixels(ctx->n_pix);
         return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
             size_t first = 0;
             const DecodeRegion part = region.part(lo, k, &first);
-            return run_decode_slices(set, st + lo, sz + lo, k, d_out + first * out_pix, part);
+            return run_decode_slices(set, st + lo, sz + lo, k, region.at(d_out, first, ctx->n_pix), part);
         });
     });
 }
@@ -687,9 +736,86 @@ int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *st
 int decode_host(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_out, const DecodeRegion &asked)
 {
     return decode_call(who, ctx, streams, sizes, n_frames, h_out, asked, false, [&](const DecodeRegion &region, const uint8_t *const *st, const size_t *sz, size_t n) {
-        Prefault prefault(h_out, region.outputs(n) * region.pixels(ctx->n_pix) * sizeof(float));
+        // (placed boxes: the output is not the call's to clear - no page of it is touched ahead of the boxes)
+        Prefault prefault(h_out, region.kind == DecodeRegion::Placed ? 0 : region.outputs(n) * region.pixels(ctx->n_pix) * sizeof(float));
         return decode_to_host(ctx, nullptr, 1, ctx->max_frames, st, sz, n, h_out, &prefault, region);
     });
+}
+
+// ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
+size_t cdiv(size_t a, size_t b) { return a / b + (a % b != 0); }
+// The container as ebcc_decode_chunking checks it: the header, then the chain of `u64 nbytes | stream` entries - of a chunk only
+// the length field is read.  parse: "" or what is wrong with it (the reference's messages).
+struct Container {
+    size_t dims[3], cd[3], cnt[3], csize = 0, nchunks = 0, total = 0;
+    std::vector<const uint8_t *> ptrs;
+    std::vector<size_t> lens;
+    std::string parse(const uint8_t *data, size_t data_size)
+    {
+        char text[160];
+        if (!data || data_size < sizeof(ChunkHeader) || memcmp(data, EBCC_CHUNKING_HEADER_MAGIC, 4) != 0) return "not an EBCK chunk container";
+        ChunkHeader hd;
+        memcpy(&hd, data, sizeof hd);
+        if (hd.version != EBCC_CHUNKING_HEADER_VERSION) { snprintf(text, sizeof text, "Unsupported EBCC chunking header version: %u", hd.version); return text; }
+        if (hd.ndims != NDIMS) { snprintf(text, sizeof text, "Unsupported EBCC chunking dimensionality: %u", hd.ndims); return text; }
+        for (int i = 0; i < 3; i++) { dims[i] = hd.dims[i]; cd[i] = hd.chunk_dims[i]; }
+        if (!dims_are_valid(cd)) return "Invalid chunked EBCC data: bad chunk dimensions";
+        for (int i = 0; i < 3; i++) {
+            if (!dims[i] || !cd[i]) return "Invalid chunked EBCC data: dims and chunk_dims must be non-zero";
+            cnt[i] = cdiv(dims[i], cd[i]);
+        }
+        csize = cd[0] * cd[1] * cd[2]; nchunks = cnt[0] * cnt[1] * cnt[2]; total = dims[0] * dims[1] * dims[2];
+        if (hd.chunk_size != csize || hd.num_chunks != nchunks) return "Invalid chunked EBCC data: inconsistent chunk metadata";
+        if (cd[0] != 1 && !tile_height_supported(cd[1])) {
+            snprintf(text, sizeof text, "chunks holding %lu frames of %lu rows are not supported", cd[0], cd[1]);
+            return text;
+        }
+        ptrs.resize(nchunks); lens.resize(nchunks);
+        const uint8_t *p = data + sizeof hd, *end = data + data_size;
+        for (size_t c = 0; c < nchunks; c++) {
+            uint64_t nb;
+            if ((size_t) (end - p) < 8) return "Invalid chunked EBCC data: missing chunk size";
+            memcpy(&nb, p, 8); p += 8;
+            if (nb > (size_t) (end - p)) return "Invalid chunked EBCC data: truncated chunk payload";
+            ptrs[c] = p; lens[c] = nb; p += nb;
+        }
+        if (p != end) return "Invalid chunked EBCC data: trailing payload bytes";
+        return "";
+    }
+};
+
+// A slab of a container of one-frame chunks as the placed boxes of the chunks it meets (ebcc_hip_slab_plan), against a compact
+// [nt][rows][cols] output; false: refused, message set.  (H, W: the geometry of the engine that is to decode it, 0: any)
+bool slab_boxes(const char *who, Container &box, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, size_t H, size_t W,
+                std::vector<ebcc_hip_placed_box> &boxes)
+{
+    const std::string bad = box.parse(data, size);
+    if (!bad.empty()) { set_error("%s: %s", who, bad.c_str()); return false; }
+    if (box.cd[0] != 1) { set_error("%s: chunks of several frames (%zu) are not supported", who, box.cd[0]); return false; }
+    if (H && (box.cd[1] != H || box.cd[2] != W)) {
+        set_error("%s: the context's frames are %zu x %zu, the container's chunks %zu x %zu", who, H, W, box.cd[1], box.cd[2]);
+        return false;
+    }
+    const long n = slab ? ebcc_hip_slab_plan(box.dims, box.cd, slab, nullptr, 0) : -1;
+    if (n < 0) {
+        if (slab) set_error("%s: the slab [%zu, +%zu) x [%zu, +%zu) x [%zu, +%zu) is empty or not inside the (%zu, %zu, %zu) array", who, slab->t0, slab->nt,
+                            slab->row0, slab->rows, slab->col0, slab->cols, box.dims[0], box.dims[1], box.dims[2]);
+        else set_error("%s: bad arguments", who);
+        return false;
+    }
+    boxes.resize((size_t) n);
+    ebcc_hip_slab_plan(box.dims, box.cd, slab, boxes.data(), boxes.size());
+    return true;
+}
+int container_slab(const char *who, ebcc_hip_ctx *ctx, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, float *out, bool host)
+{
+    if (!ctx || !out) { set_error("%s: bad arguments", who); return 1; }
+    Container box;
+    std::vector<ebcc_hip_placed_box> boxes;
+    if (!slab_boxes(who, box, data, size, slab, (size_t) ctx->height, (size_t) ctx->width, boxes)) return 1;
+    const DecodeRegion region = DecodeRegion::placed_list(boxes.data(), boxes.size(), slab->nt * slab->rows * slab->cols);
+    return host ? decode_host(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region)
+                : decode_resident(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region, false);
 }
 
 }  // namespace
@@ -861,6 +987,88 @@ int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *s
     EBCC_API_CATCH(1)
 }
 
+// Placed boxes: boxes of their own sizes, each to its own rectangle of the output (include/ebcc_hip.h).
+int ebcc_hip_decode_frames_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_placed_box *boxes,
+                                  size_t n_boxes, float *d_out, size_t out_floats)
+{
+    EBCC_API_TRY
+    return decode_resident("ebcc_hip_decode_frames_placed", ctx, streams, sizes, n_frames, d_out, DecodeRegion::placed_list(boxes, n_boxes, out_floats), true);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_decode_shard_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_placed_box *boxes,
+                                 size_t n_boxes, float *d_out, size_t out_floats)
+{
+    EBCC_API_TRY
+    return decode_resident("ebcc_hip_decode_shard_placed", ctx, streams, sizes, n_frames, d_out, DecodeRegion::placed_list(boxes, n_boxes, out_floats), false);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_decode_host_frames_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_placed_box *boxes,
+                                       size_t n_boxes, float *h_out, size_t out_floats)
+{
+    EBCC_API_TRY
+    return decode_host("ebcc_hip_decode_host_frames_placed", ctx, streams, sizes, n_frames, h_out, DecodeRegion::placed_list(boxes, n_boxes, out_floats));
+    EBCC_API_CATCH(1)
+}
+
+// A slab of an array in chunks as placed boxes (include/ebcc_hip.h; host only, no device work).
+long ebcc_hip_slab_plan(const size_t dims[3], const size_t chunk_dims[3], const ebcc_hip_slab *slab, ebcc_hip_placed_box *boxes, size_t max_boxes)
+{
+    EBCC_API_TRY
+    if (!dims || !chunk_dims || !slab) { set_error("ebcc_hip_slab_plan: bad arguments"); return -1; }
+    const size_t *cd = chunk_dims;
+    if (!dims[0] || !dims[1] || !dims[2]) { set_error("ebcc_hip_slab_plan: zero dims"); return -1; }
+    if (cd[0] != 1) { set_error("ebcc_hip_slab_plan: chunks of %zu frames (one-frame chunks only)", cd[0]); return -1; }
+    if (!dims_are_valid(cd)) { set_error("ebcc_hip_slab_plan: chunks of %zu x %zu are not between %d and %d", cd[1], cd[2], EBCC_MIN_INTERNAL_IMAGE_DIM, EBCC_MAX_INTERNAL_IMAGE_DIM); return -1; }
+    const size_t org[3] = {slab->t0, slab->row0, slab->col0}, ext[3] = {slab->nt, slab->rows, slab->cols};
+    for (int i = 0; i < 3; i++)
+        if (ext[i] < 1 || org[i] >= dims[i] || ext[i] > dims[i] - org[i]) {       // (no sums: they may overflow)
+            set_error("ebcc_hip_slab_plan: the slab is empty or not inside the (%zu, %zu, %zu) array", dims[0], dims[1], dims[2]);
+            return -1;
+        }
+    const size_t cnt1 = cdiv(dims[1], cd[1]), cnt2 = cdiv(dims[2], cd[2]);
+    const size_t cy0 = org[1] / cd[1], cy1 = (org[1] + ext[1] - 1) / cd[1], cx0 = org[2] / cd[2], cx1 = (org[2] + ext[2] - 1) / cd[2];
+    const size_t count = ext[0] * (cy1 - cy0 + 1) * (cx1 - cx0 + 1);
+    if (count > (size_t) LONG_MAX) { set_error("ebcc_hip_slab_plan: too many chunks"); return -1; }
+    if (!boxes) return (long) count;
+    if (max_boxes < count) { set_error("ebcc_hip_slab_plan: room for %zu of %zu boxes", max_boxes, count); return -1; }
+    ebcc_hip_placed_box *b = boxes;
+    for (size_t t = org[0]; t < org[0] + ext[0]; t++)
+        for (size_t cy = cy0; cy <= cy1; cy++)
+            for (size_t cx = cx0; cx <= cx1; cx++, b++) {
+                // the slab cut with the chunk (the slab lies inside the array: so does the cut, in the chunk's real part)
+                const size_t r0 = std::max(org[1], cy * cd[1]), r1 = std::min(org[1] + ext[1], (cy + 1) * cd[1]);
+                const size_t c0 = std::max(org[2], cx * cd[2]), c1 = std::min(org[2] + ext[2], (cx + 1) * cd[2]);
+                *b = ebcc_hip_placed_box{(t * cnt1 + cy) * cnt2 + cx, r0 - cy * cd[1], c0 - cx * cd[2], r1 - r0, c1 - c0,
+                                         ((t - org[0]) * ext[1] + (r0 - org[1])) * ext[2] + (c0 - org[2]), ext[2]};
+            }
+    return (long) count;
+    EBCC_API_CATCH(-1)
+}
+
+int ebcc_hip_container_info(const uint8_t *data, size_t size, size_t dims[3], size_t chunk_dims[3])
+{
+    EBCC_API_TRY
+    Container box;
+    const std::string bad = box.parse(data, size);
+    if (!bad.empty()) { set_error("ebcc_hip_container_info: %s", bad.c_str()); return 1; }
+    for (int i = 0; i < 3; i++) { if (dims) dims[i] = box.dims[i]; if (chunk_dims) chunk_dims[i] = box.cd[i]; }
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
+int ebcc_hip_decode_container_slab(ebcc_hip_ctx *ctx, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, float *d_out)
+{
+    EBCC_API_TRY
+    return container_slab("ebcc_hip_decode_container_slab", ctx, data, size, slab, d_out, false);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_decode_container_slab_host(ebcc_hip_ctx *ctx, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, float *h_out)
+{
+    EBCC_API_TRY
+    return container_slab("ebcc_hip_decode_container_slab_host", ctx, data, size, slab, h_out, true);
+    EBCC_API_CATCH(1)
+}
+
 // The engines the reference-compatible entry points keep between calls (one per device and frame geometry, with their slice
 // engines and second set: tens of GB of device memory for 256 frames of 721 x 1440) are destroyed; the next call makes them
 // again.  Contexts made with ebcc_hip_create are the caller's and are not touched.
@@ -1003,8 +1211,6 @@ size_t ebcc_decode(uint8_t *data, size_t data_size, float **out_buffer)
 }
 
 // ---- EBCK chunk container (:920-1052) -------------------------------------------------------------
-static size_t cdiv(size_t a, size_t b) { return a / b + (a % b != 0); }
-
 size_t ebcc_encode_chunking(float *data, codec_config_t *config, uint8_t **out_buffer)
 {
     log_set_level_from_env();
@@ -1109,34 +1315,13 @@ size_t ebcc_decode_chunking(uint8_t *data, size_t data_size, float **out_buffer)
     // :1322-1449
     log_set_level_from_env();
     if (data_size < sizeof(ChunkHeader) || memcmp(data, EBCC_CHUNKING_HEADER_MAGIC, 4) != 0) return ebcc_decode(data, data_size, out_buffer);
-    ChunkHeader hd;
-    memcpy(&hd, data, sizeof hd);
-    if (hd.version != EBCC_CHUNKING_HEADER_VERSION) { log_fatal("Unsupported EBCC chunking header version: %u", hd.version); return 0; }
-    if (hd.ndims != NDIMS) { log_fatal("Unsupported EBCC chunking dimensionality: %u", hd.ndims); return 0; }
-    size_t dims[3], cd[3], cnt[3];
-    for (int i = 0; i < 3; i++) { dims[i] = hd.dims[i]; cd[i] = hd.chunk_dims[i]; }
-    if (!dims_are_valid(cd)) { log_fatal("Invalid chunked EBCC data: bad chunk dimensions"); return 0; }
-    for (int i = 0; i < 3; i++) {
-        if (!dims[i] || !cd[i]) { log_fatal("Invalid chunked EBCC data: dims and chunk_dims must be non-zero"); return 0; }
-        cnt[i] = cdiv(dims[i], cd[i]);
-    }
-    const size_t csize = cd[0] * cd[1] * cd[2], nchunks = cnt[0] * cnt[1] * cnt[2], total = dims[0] * dims[1] * dims[2];
-    if (hd.chunk_size != csize || hd.num_chunks != nchunks) { log_fatal("Invalid chunked EBCC data: inconsistent chunk metadata"); return 0; }
-    if (cd[0] != 1 && !tile_height_supported(cd[1])) {
-        log_fatal("chunks holding %lu frames of %lu rows are not supported", cd[0], cd[1]);
-        return 0;
-    }
-    std::vector<const uint8_t *> ptrs(nchunks);
-    std::vector<size_t> lens(nchunks);
-    const uint8_t *p = data + sizeof hd, *end = data + data_size;
-    for (size_t c = 0; c < nchunks; c++) {
-        uint64_t nb;
-        if ((size_t) (end - p) < 8) { log_fatal("Invalid chunked EBCC data: missing chunk size"); return 0; }
-        memcpy(&nb, p, 8); p += 8;
-        if (nb > (size_t) (end - p)) { log_fatal("Invalid chunked EBCC data: truncated chunk payload"); return 0; }
-        ptrs[c] = p; lens[c] = nb; p += nb;
-    }
-    if (p != end) { log_fatal("Invalid chunked EBCC data: trailing payload bytes"); return 0; }
+    Container held;
+    const std::string bad = held.parse(data, data_size);
+    if (!bad.empty()) { log_fatal("%s", bad.c_str()); return 0; }
+    const size_t *const dims = held.dims, *const cd = held.cd, *const cnt = held.cnt;
+    const size_t csize = held.csize, nchunks = held.nchunks, total = held.total;
+    const std::vector<const uint8_t *> &ptrs = held.ptrs;
+    const std::vector<size_t> &lens = held.lens;
     const int H = (int) cd[1], W = (int) cd[2];
     ChunkBox box;
     for (int i = 0; i < 3; i++) { box.dims[i] = dims[i]; box.cd[i] = cd[i]; box.cnt[i] = cnt[i]; }
@@ -1163,6 +1348,38 @@ size_t ebcc_decode_chunking(uint8_t *data, size_t data_size, float **out_buffer)
         for (size_t cl = 0; cl < nchunks; cl++) box.scatter(chunks.data() + cl * csize, cl, o);          // :353-370
     *out_buffer = o;
     return total;
+}
+
+// The slab of a container on the cached engines of one device (include/ebcc_hip.h): the chunks it meets through decode_to_host
+// as placed boxes of a compact [nt][rows][cols] array.
+size_t ebcc_decode_chunking_slab(uint8_t *data, size_t data_size, const ebcc_hip_slab *slab, float **out_buffer)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_decode_chunking_slab";
+    log_set_level_from_env();
+    Container held;
+    std::vector<ebcc_hip_placed_box> boxes;
+    if (!out_buffer) { set_error("%s: bad arguments", who); return 0; }
+    if (!slab_boxes(who, held, data, data_size, slab, 0, 0, boxes)) { log_fatal("%s", ebcc_hip_last_error()); return 0; }
+    const size_t floats = slab->nt * slab->rows * slab->cols;
+    float *o = (float *) malloc(floats * sizeof(float));
+    if (!o) { log_fatal("Failed to allocate chunked EBCC decode output"); return 0; }
+    const int H = (int) held.cd[1], W = (int) held.cd[2], device = resolve_device();
+    const int rcode = on_codec(device, 1, [&] {
+        ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
+        if (!chunk_engines(device, H, W, std::min(boxes.size(), batch_capacity(held.csize)), 1, &ctx, &rc)) return 1;
+        DecodeRegion region = DecodeRegion::placed_list(boxes.data(), boxes.size(), floats);
+        const uint8_t *const *streams = held.ptrs.data();
+        const size_t *sizes = held.lens.data();
+        size_t n = held.nchunks;
+        BoxCall call;
+        if (decode_region(who, ctx, streams, sizes, n, region, call)) return 1;
+        return decode_to_host(ctx, nullptr, 1, ctx->max_frames, streams, sizes, n, o, nullptr, region);
+    });
+    if (rcode) { free(o); return 0; }
+    *out_buffer = o;
+    return floats;
+    EBCC_API_CATCH(0)
 }
 
 }  // extern "C"

@@ -404,6 +404,38 @@ bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, i
     return n[0] < n[1] && n[2] < n[3] && rect[0] < n[1] && n[0] < rect[1] && rect[2] < n[3] && n[2] < rect[3];
 }
 
+namespace {
+// a box of a checked list, of either kind
+struct BoxView { size_t frame, row0, col0, rows, cols; };
+// keep and table of a checked list whose box e is at(e) (j2k.hpp: j2k_boxes_check)
+template <class At>
+bool boxes_plan(const char *who, const J2kGeom &g, size_t n_frames, size_t n_boxes, At at, uint8_t *keep, J2kBoxEntry *table, int first_fused)
+{
+    std::vector<J2kBlock> blk;
+    make_j2k_geom(g.H, g.W, blk);
+    memset(keep, 0, n_frames * blk.size());
+    BoxView prev{};
+    for (size_t e = 0; e < n_boxes; e++) {
+        const BoxView b = at(e);
+        const bool repeat = e && b.frame == prev.frame && b.row0 == prev.row0 && b.col0 == prev.col0 && b.rows == prev.rows && b.cols == prev.cols;
+        prev = b;
+        if (table) { table[e] = repeat ? table[e - 1] : J2kBoxEntry{(int) b.frame, 0, 0, (int) b.row0, (int) b.col0}; table[e].out = (int) e; }
+        if (repeat) continue;
+        J2kWindow w;
+        if (!j2k_window_plan(g, b.row0, b.col0, b.rows, b.cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
+        for (int r = first_fused; table && r < kJ2kRes; r++) {
+            const J2kStripRange sp = j2k_cone_span(w, r);
+            table[e].strip0[r] = sp.strip0; table[e].strips[r] = sp.strips; table[e].pos0[r] = sp.pos0; table[e].pos1[r] = sp.pos1;
+        }
+        uint8_t *row = keep + b.frame * blk.size();
+        int rect[4];
+        for (size_t i = 0; i < blk.size(); i++)
+            if (!row[i] && j2k_window_keeps(g, blk[i], w, rect)) row[i] = 1;
+    }
+    return true;
+}
+}  // namespace
+
 bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
                      uint8_t *keep, J2kBoxEntry *table, int first_fused)
 {
@@ -421,26 +453,41 @@ bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const e
         }
     }
     if (!keep) return true;
-    std::vector<J2kBlock> blk;
-    make_j2k_geom(g.H, g.W, blk);
-    memset(keep, 0, n_frames * blk.size());
+    return boxes_plan(who, g, n_frames, n_boxes, [&](size_t e) { return BoxView{boxes[e].frame, boxes[e].row0, boxes[e].col0, rows, cols}; }, keep, table, first_fused);
+}
+
+bool j2k_placed_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
+                      uint8_t *keep, J2kBoxEntry *table, J2kPlacement *place, int first_fused, int *max_rows, int *max_cols)
+{
+    const size_t H = (size_t) g.H, W = (size_t) g.W;
+    if (!boxes || n_boxes < 1) { set_error("%s: an empty box list", who); return false; }
+    if (!j2k_window_supported(g)) { set_error("%s: frames of %d x %d are not supported (fewer than 3 columns)", who, g.H, g.W); return false; }
+    size_t most_rows = 0, most_cols = 0;
     for (size_t e = 0; e < n_boxes; e++) {
-        const ebcc_hip_box &b = boxes[e];
-        const bool repeat = e && b.frame == boxes[e - 1].frame && b.row0 == boxes[e - 1].row0 && b.col0 == boxes[e - 1].col0;
-        if (table) { table[e] = repeat ? table[e - 1] : J2kBoxEntry{(int) b.frame, 0, 0, (int) b.row0, (int) b.col0}; table[e].out = (int) e; }
-        if (repeat) continue;
-        J2kWindow w;
-        if (!j2k_window_plan(g, b.row0, b.col0, rows, cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
-        for (int r = first_fused; table && r < kJ2kRes; r++) {
-            const J2kStripRange sp = j2k_cone_span(w, r);
-            table[e].strip0[r] = sp.strip0; table[e].strips[r] = sp.strips; table[e].pos0[r] = sp.pos0; table[e].pos1[r] = sp.pos1;
+        const ebcc_hip_placed_box &b = boxes[e];
+        if (b.frame >= n_frames) { set_error("%s: box %zu names frame %zu of %zu", who, e, b.frame, n_frames); return false; }
+        if (e && b.frame < boxes[e - 1].frame) { set_error("%s: box %zu: the boxes are not in the order of their frames", who, e); return false; }
+        if (b.rows < 1 || b.cols < 1 || b.rows > H || b.cols > W || b.row0 > H - b.rows || b.col0 > W - b.cols) {   // (no sums: they may overflow)
+            set_error("%s: box %zu, [%zu, +%zu) x [%zu, +%zu), is empty or not inside the %zu x %zu frame", who, e, b.row0, b.rows, b.col0, b.cols, H, W);
+            return false;
         }
-        uint8_t *row = keep + b.frame * blk.size();
-        int rect[4];
-        for (size_t i = 0; i < blk.size(); i++)
-            if (!row[i] && j2k_window_keeps(g, blk[i], w, rect)) row[i] = 1;
+        if (b.out_pitch < b.cols) { set_error("%s: box %zu: a pitch of %zu for rows of %zu samples", who, e, b.out_pitch, b.cols); return false; }
+        // the last sample, out_offset + (rows - 1) * out_pitch + cols - 1, is inside the output (rows and cols are at most 2047)
+        const size_t room = out_floats > b.out_offset ? out_floats - b.out_offset : 0;
+        if (room < b.cols || (b.rows > 1 && (room - b.cols) / (b.rows - 1) < b.out_pitch)) {
+            set_error("%s: box %zu, %zu x %zu at offset %zu with pitch %zu, does not end inside the %zu floats of the output", who, e, b.rows, b.cols,
+                      b.out_offset, b.out_pitch, out_floats);
+            return false;
+        }
+        most_rows = std::max(most_rows, b.rows); most_cols = std::max(most_cols, b.cols);
     }
-    return true;
+    if (max_rows) *max_rows = (int) most_rows;
+    if (max_cols) *max_cols = (int) most_cols;
+    if (!keep) return true;
+    if (place)
+        for (size_t e = 0; e < n_boxes; e++) place[e] = J2kPlacement{(int) boxes[e].rows, (int) boxes[e].cols, boxes[e].out_offset, boxes[e].out_pitch};
+    return boxes_plan(who, g, n_frames, n_boxes, [&](size_t e) { return BoxView{boxes[e].frame, boxes[e].row0, boxes[e].col0, boxes[e].rows, boxes[e].cols}; },
+                      keep, table, first_fused);
 }
 
 }  // namespace ebcc

@@ -220,18 +220,28 @@ struct J2kBoxEntry {
     int strip0[kJ2kRes], strips[kJ2kRes], pos0[kJ2kRes], pos1[kJ2kRes];
     int pad[3];
 };
+// A placed box (include/ebcc_hip.h: ebcc_hip_placed_box): record e of a second table beside the entries - the box's own extent
+// and where it lies in the caller's array, sample (y, x) at out[at + y * pitch + x].  `J2kBoxEntry::out` is not used then.
+struct J2kPlacement {
+    int rows, cols;
+    unsigned long long at, pitch;
+};
 // the boxes of a batch: `h_table` / `table`: pinned and device room for `n` records, the pinned ones filled by j2k_boxes_check
-// but for the slot, which is the launch's
+// but for the slot, which is the launch's.  Boxes of one size rows x cols at index `out` of [n][rows][cols]; or placed boxes
+// (`h_place` / `place` set, behind the entries in the same pinned / device allocation: one copy sends both; filled by
+// j2k_placed_check), of at most rows x cols.
 struct J2kBoxList {
     J2kBoxEntry *h_table, *table;
     size_t n;
     int rows, cols;
+    J2kPlacement *h_place = nullptr, *place = nullptr;
 };
 // What a decode launch puts out (launch_j2k_decode), as decode_batch plans it once per batch: whole frames to jb.DEC; the
 // window `cone` of every frame to out [n_frames][rows][cols]; or the boxes of `list`, each from the frame it names, to
-// out [n][rows][cols].
+// out [n][rows][cols]; or the placed boxes of `list` (its second table set), each to its own rectangle of out.
 struct J2kRegion {
-    enum Kind { Frames, Window, Boxes } kind = Frames;
+    enum Kind { Frames, Window, Boxes, Placed } kind = Frames;
+    bool lists() const { return kind == Boxes || kind == Placed; }
     J2kWindow cone{};
     J2kBoxList list{};
     float *out = nullptr;
@@ -242,6 +252,11 @@ struct J2kRegion {
 // box's cone is planned once.
 bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
                      uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, int first_fused = kJ2kRes);
+// the same for the placed boxes of the _placed entry points, each of its own size, against an output of out_floats floats;
+// place (with table): record e is box e's extent and placement.  max_rows / max_cols (may be null): the largest extents.
+bool j2k_placed_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
+                      uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, J2kPlacement *place = nullptr, int first_fused = kJ2kRes,
+                      int *max_rows = nullptr, int *max_cols = nullptr);
 int j2k_selfcheck_div65535();   // mismatches of the division-free s / 65535.0f of the fused inverse level (0 expected)
 
 // ---- launchers (asynchronous on s) ---------------------------------------------------------------
@@ -278,6 +293,8 @@ void launch_j2k_probe_decode(const float *data, const J2kBuffers &jb, int n_fram
 void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kRegion &region = J2kRegion{});
 // the inverse levels of a box list over the tier-1 decoder's output jb.V (j2k_analysis.hip)
 void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &boxes, float *out, hipStream_t s);
+// after it, for placed boxes: those of constant frames (jb.fs) filled with the frame's value, at their pitch
+void launch_j2k_fill_placed(const J2kBuffers &jb, const J2kBoxList &boxes, float *out, hipStream_t s);
 void plan_decode_lanes(const int *host_table, int total, int out[4]);   // (what launch_j2k_decode chooses; ebcc_hip_plan_decode_lanes)
 
 }  // namespace ebcc

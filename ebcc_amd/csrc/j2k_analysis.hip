@@ -826,6 +826,31 @@ struct J2kSinkBoxTop : J2kSinkWindowTop {
         return !empty;
     }
 };
+// the top level of one placed box (J2kPlacement): the box's own origin and extent (win.out is the box's first sample), rows
+// `pitch` floats apart; the 8-byte form is decided per box from that address, the pitch's parity, col0 and cols
+struct J2kSinkPlacedTop : J2kSinkWindowTop {
+    size_t pitch;
+    __device__ bool begin(const J2kStripLane &l, bool empty)
+    {
+        d = win.out;
+        mn = fs[l.frame].minv; rng = fs[l.frame].maxv - fs[l.frame].minv;
+        wx = 2 * l.i - win.col0;
+        pair_io = (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (l.nh & 1) == 0 && (pitch & 1) == 0 && ((size_t) d & 7) == 0;
+        return !empty;
+    }
+    __device__ void put(bool emit, int y, float ev, float od, float, float, bool has_odd_col)
+    {
+        const float de = fin_map_fast(ev, rng, mn), dq = fin_map_fast(od, rng, mn);
+        const int wy = y - win.row0;
+        if (!emit || wy < 0 || wy >= win.rows) return;
+        float *q = d + (size_t) wy * pitch;
+        if (pair_io) { if (wx >= 0 && wx < win.cols) *reinterpret_cast<f32x2 *>(q + wx) = f32x2{de, dq}; }
+        else {
+            if (wx >= 0 && wx < win.cols) q[wx] = de;
+            if (has_odd_col && wx + 1 >= 0 && wx + 1 < win.cols) q[wx + 1] = dq;
+        }
+    }
+};
 
 // (io, range and sink by value: the compiler optimises this function on its own before it inlines it, and behind a reference
 //  they are memory that the pass's stores may alias - the whole-frame top level then takes 7 VGPRs more)
@@ -957,6 +982,35 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_box(J2kLevelIO i
         J2kSinkNextLevel sink{io};
         j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
     }
+}
+// The top level of the placed boxes of one round: k_j2k_level_box<true> with the box's extent and placement from record e of
+// the second table (the levels below are k_j2k_level_box<false> over the entries, as for boxes of one size).
+__global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_placed(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
+                                                                        const FrameState *fs, const J2kBoxEntry *__restrict__ entries,
+                                                                        const J2kPlacement *__restrict__ places, int n_entries, int pieces,
+                                                                        int ll_by_frame, float *out)
+{
+    const int at = (int) blockIdx.y % n_entries;
+    const J2kBoxEntry &e = entries[at];
+    const J2kPlacement &p = places[at];
+    const int r = kJ2kRes - 1;
+    const J2kStripRange range{e.strip0[r], e.strips[r], e.pos0[r], e.pos1[r], pieces};
+    const J2kStripTile tile{e.frame, (int) blockIdx.y / n_entries, ll_by_frame ? e.frame : e.slot, e.slot};
+    J2kSinkPlacedTop sink{{J2kWinOut{out + p.at, e.row0, e.col0, p.rows, p.cols}, fs}, (size_t) p.pitch};
+    j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
+}
+// placed boxes of constant frames (the strip pass leaves them alone): the rectangle filled with the frame's value;
+// workgroups (row group, entry)
+__global__ __launch_bounds__(256) void k_fill_placed(const FrameState *fs, const J2kBoxEntry *__restrict__ entries,
+                                                      const J2kPlacement *__restrict__ places, float *out)
+{
+    const J2kBoxEntry &e = entries[blockIdx.y];
+    if (!fs[e.frame].const_field) return;
+    const J2kPlacement &p = places[blockIdx.y];
+    const float v = fs[e.frame].minv;
+    float *o = out + p.at;
+    for (int y = (int) blockIdx.x; y < p.rows; y += (int) gridDim.x)
+        for (int x = (int) threadIdx.x; x < p.cols; x += (int) blockDim.x) o[(size_t) y * p.pitch + (size_t) x] = v;
 }
 
 template <typename K>
@@ -1986,7 +2040,8 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
     if (used > n_pix) throw std::runtime_error("box decode: the level bands of a box do not fit its slot");
     const size_t cap = (size_t) jb.max_frames;
     for (size_t e = 0; e < bl.n; e++) bl.h_table[e].slot = (int) (e % cap);
-    EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * sizeof(J2kBoxEntry), hipMemcpyHostToDevice, s));
+    // (placed boxes: the second table lies behind the entries on both sides)
+    EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * (sizeof(J2kBoxEntry) + (bl.place ? sizeof(J2kPlacement) : 0)), hipMemcpyHostToDevice, s));
     for (size_t lo = 0; lo < bl.n; lo += cap) {
         const int n = (int) std::min(cap, bl.n - lo);
         for (int r = first_fused; r < kJ2kRes; r++) {
@@ -2000,9 +2055,20 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
             const bool from_frames = r == first_fused;                       // (its low-pass input: V, or the band in jb.B)
             J2kLevelIO io{from_frames ? (r > 1 ? jb.B : nullptr) : jb.B2 + off[r - 1], from_frames ? g.W : pitch[r - 1], n_pix,
                           top ? nullptr : jb.B2 + off[r], top ? g.W : pitch[r], n_pix, r};
-            if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
+            if (top && bl.place) hipLaunchKernelGGL(k_j2k_level_placed, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, bl.place + lo, n, lg.pieces, from_frames ? 1 : 0, out);
+            else if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
             else hipLaunchKernelGGL(k_j2k_level_box<false>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
         }
+    }
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+// after launch_j2k_box_levels (which sent the tables), for a list of placed boxes that names constant frames: their fill
+void launch_j2k_fill_placed(const J2kBuffers &jb, const J2kBoxList &bl, float *out, hipStream_t s)
+{
+    for (size_t lo = 0; lo < bl.n; lo += 65535) {
+        const unsigned n = (unsigned) std::min<size_t>(65535, bl.n - lo);
+        hipLaunchKernelGGL(k_fill_placed, dim3((unsigned) std::min(std::max(bl.rows, 1), 64), n), dim3(256), 0, s, jb.fs, bl.table + lo, bl.place + lo, out);
     }
     EBCC_HIP_LAUNCH_CHECK();
 }

@@ -139,6 +139,10 @@ void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_fram
 struct J2kBoxEntry;
 void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, size_t n_boxes, const int *d_active,
                                      hipStream_t s, int rows, int cols);
+// and for placed boxes (j2k.hpp: J2kPlacement - extent, first sample and pitch are the second table's); max_rows: the tallest
+struct J2kPlacement;
+void launch_synthesis_tail_add_placed(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, const J2kPlacement *d_places, size_t n_boxes,
+                                      const int *d_active, hipStream_t s, int max_rows);
 
 // plain spiht_decode output image in [0,1] (spiht_re.c:508-516) for the unit entry point
 void launch_emit_image(float *image_out, const ResidualBuffers &rb, int n_frames, hipStream_t s);

@@ -234,10 +234,14 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_use(const float *__res
 }
 
 // The decoder's last synthesis pass: out += r (ebcc_codec.c:1307) for the box [row0, row0 + rows) x [col0, col0 + cols) of the
-// grid of `frame`, added to the compact box out[out_index] of [rows][cols].  Only the box's rows are synthesised, each of them
-// whole (a row is one lifting chain; its samples outside the box are its halo), so a sample has the same bits whatever the box.
+// grid of `frame`, added to the compact box out[out_index] of [rows][cols] - or (PLACED: its own instantiation, the compact
+// form's code stays as it was) to the box whose first sample is `out` and whose rows lie `pitch` floats apart.  Only the box's
+// rows are synthesised, each of them whole (a row is one lifting chain; its samples outside the box are its halo), so a sample
+// has the same bits whatever the box.
+template <bool PLACED = false>
 __device__ __forceinline__ void rows_inv_add_body(const float *__restrict__ src, int stride, size_t frame_stride, int n, const int *active,
-                                                  const FrameState *fs, float *out, int frame, int out_index, int row0, int col0, int rows, int cols)
+                                                  const FrameState *fs, float *out, int frame, int out_index, int row0, int col0, int rows, int cols,
+                                                  size_t pitch = 0)
 {
     extern __shared__ float sm[];
     if (active && !active[frame]) return;
@@ -245,7 +249,7 @@ __device__ __forceinline__ void rows_inv_add_body(const float *__restrict__ src,
     float *E = sm, *O = sm + half;
     src += (size_t) frame * frame_stride;
     const int tid = threadIdx.x;
-    float *o = out + (size_t) out_index * ((size_t) rows * (size_t) cols);
+    float *o = PLACED ? out : out + (size_t) out_index * ((size_t) rows * (size_t) cols);
     const float dc = (float) fs[frame].dec_dc, rmin = fs[frame].rmin, rng = fs[frame].rmax - fs[frame].rmin;
     for (int wy = blockIdx.x; wy < rows; wy += gridDim.x) {
         const float *s = src + (size_t) (row0 + wy) * stride;
@@ -258,7 +262,7 @@ __device__ __forceinline__ void rows_inv_add_body(const float *__restrict__ src,
         for (int wx = tid; wx < cols; wx += kRowThreads) {
             const int xx = col0 + wx;
             const float r = residual_value((xx & 1) ? O[xx >> 1] : E[xx >> 1], dc, rmin, rng);
-            const size_t i = (size_t) wy * (size_t) cols + (size_t) wx;
+            const size_t i = (size_t) wy * (PLACED ? pitch : (size_t) cols) + (size_t) wx;
             o[i] = o[i] + r;
         }
         __syncthreads();
@@ -280,6 +284,17 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_box(const float *_
 {
     const J2kBoxEntry &e = boxes[blockIdx.y];
     rows_inv_add_body(src, stride, frame_stride, n, active, fs, out, e.frame, e.out, e.row0, e.col0, rows, cols);
+}
+
+// placed boxes: extent, first sample and pitch from record e of the second table; the grid's x is sized for the tallest box,
+// and a workgroup beyond a smaller one's rows finds nothing to do
+__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_placed(const float *__restrict__ src, int stride, size_t frame_stride, int n,
+                                                                      const int *active, const FrameState *fs, float *out,
+                                                                      const J2kBoxEntry *__restrict__ boxes, const J2kPlacement *__restrict__ places)
+{
+    const J2kBoxEntry &e = boxes[blockIdx.y];
+    const J2kPlacement &p = places[blockIdx.y];
+    rows_inv_add_body<true>(src, stride, frame_stride, n, active, fs, out + p.at, e.frame, 0, e.row0, e.col0, p.rows, p.cols, (size_t) p.pitch);
 }
 
 __global__ __launch_bounds__(kRowThreads) void k_rows_inv(const float *__restrict__ src, float *__restrict__ dst,
@@ -1355,6 +1370,20 @@ void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, cons
         const unsigned n = (unsigned) std::min<size_t>(65535, n_boxes - lo);
         hipLaunchKernelGGL(k_rows_inv_add_box, dim3(min(rows, 96), n), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
                            d_active, rb.fs, out, d_boxes + lo, rows, cols);
+    }
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+// the same for placed boxes (J2kPlacement), the tallest of `max_rows` rows.  (Overlapping target rectangles are the caller's
+// business: two workgroups may then add to one sample, and which box wins is unspecified.)
+void launch_synthesis_tail_add_placed(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, const J2kPlacement *d_places, size_t n_boxes,
+                                      const int *d_active, hipStream_t s, int max_rows)
+{
+    const Grid &g = rb.g;
+    for (size_t lo = 0; lo < n_boxes; lo += 65535) {
+        const unsigned n = (unsigned) std::min<size_t>(65535, n_boxes - lo);
+        hipLaunchKernelGGL(k_rows_inv_add_placed, dim3(min(max_rows, 96), n), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np,
+                           g.nx, d_active, rb.fs, out, d_boxes + lo, d_places + lo);
     }
     EBCC_HIP_LAUNCH_CHECK();
 }

@@ -100,6 +100,8 @@ class BatchCodec:
         lib.ebcc_hip_decode_host_frames_boxes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
                                                           ctypes.c_void_p]
+        lib.ebcc_hip_decode_host_frames_placed.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -193,6 +195,36 @@ class BatchCodec:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == k * rows * cols
         if self.lib.ebcc_hip_decode_host_frames_boxes(self.ctx, ptrs, sizes, n, table.ctypes.data, k, rows, cols, out.ctypes.data):
             self._fail("ebcc_hip_decode_host_frames_boxes")
+        return out
+
+    def decode_placed(self, streams, boxes, out):
+        """Boxes of their own sizes, each put into its own rectangle of `out`: `boxes` is an int array (k, 7) of (frame, row0,
+        col0, rows, cols, out_offset, out_pitch) in non-decreasing order of frame; sample (y, x) of box e - streams[frame_e]
+        decoded and cropped to [row0, row0 + rows) x [col0, col0 + cols), bit for bit - goes to out.ravel()[out_offset +
+        y * out_pitch + x].  `out` is a C-contiguous float32 array; only the rectangles are written, everything else of it keeps
+        its values (where rectangles overlap the samples are unspecified).  Otherwise as decode_boxes; returns `out`."""
+        n = len(streams)
+        b = np.asarray(boxes)
+        if b.ndim != 2 or b.shape[1] != 7 or b.shape[0] < 1 or b.dtype.kind not in "iu":
+            raise ValueError("boxes must be a non-empty integer array of shape (k, 7): frame, row0, col0, rows, cols, out_offset, out_pitch")
+        b = b.astype(np.int64)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError("out must be a writable C-contiguous float32 array")
+        frame, row0, col0, rows, cols, at, pitch = b.T
+        if b.min() < 0 or (frame >= n).any():
+            raise ValueError(f"a box names a frame outside the {n} streams, or has a negative field")
+        if (rows < 1).any() or (cols < 1).any() or (rows > self.h).any() or (cols > self.w).any() or (row0 > self.h - rows).any() or (col0 > self.w - cols).any():
+            raise ValueError(f"a box is empty or not inside the {self.h} x {self.w} frame")
+        if (pitch < cols).any():
+            raise ValueError("a box's pitch is smaller than its rows")
+        if (at + (rows - 1) * pitch + cols > out.size).any():
+            raise ValueError(f"a box does not end inside the {out.size} floats of out")
+        if (np.diff(frame) < 0).any():
+            raise ValueError("boxes must be in non-decreasing order of their frames")
+        streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.unique(frame)))
+        table = np.ascontiguousarray(b, np.uint64)                       # == ebcc_hip_placed_box[k]
+        if self.lib.ebcc_hip_decode_host_frames_placed(self.ctx, ptrs, sizes, n, table.ctypes.data, len(b), out.ctypes.data, out.size):
+            self._fail("ebcc_hip_decode_host_frames_placed")
         return out
 
 

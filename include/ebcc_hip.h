@@ -217,6 +217,61 @@ int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *s
 int ebcc_hip_boxes_plan(size_t height, size_t width, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes,
                         size_t rows, size_t cols, uint8_t *keep, size_t max_blocks);
 
+/* ---- placed boxes and slabs of a chunk container -----------------------------------------------
+ * A box list whose boxes carry their own extent and their own place in the output: box e is, bit for bit, the crop
+ * [row0, row0 + rows) x [col0, col0 + cols) of what ebcc_hip_decode_frames gives for frame `frame`, and its sample (y, x) goes
+ * to out[out_offset + y * out_pitch + x] (offsets and pitches in floats; `out` at any 4-byte aligned address).  Only the
+ * placed rectangles are written: the gaps between them and everything else of `out` keep their bytes, also when the call
+ * fails, and also in the host form.  Target rectangles that overlap are the caller's business: which box wins there is unspecified
+ * (with a residual layer, both boxes add to the sample that won).
+ * Everything else is the box list's: `boxes` in non-decreasing order of `frame`, repeats allowed, a frame no box names is not
+ * read (its streams[f] may be NULL), n_boxes is not limited by the context's capacity (rounds), constant fields fill their
+ * rectangle, frames without a residual layer, legacy streams and mixed batches work, streams of named frames are refused
+ * exactly as by the full decode.  The batches of the shard and host forms own parts of the list, not of the output; the host
+ * form moves the boxes' samples alone over PCIe (compact on the device, placed row by row on the host).
+ * Refused with return value 1, a message (ebcc_hip_last_error) and nothing written: n_boxes zero, a box with rows or cols zero
+ * or not inside the frame, out_pitch < cols, a box whose last sample lies at or beyond out_floats (the floats `out` holds),
+ * frame >= n_frames, frames out of order.  One-frame chunks only.
+ *
+ * This is what a sub-array ("slab") of an EBCK container (ebcc_encode_chunking / ebcc_encode_chunking_compat,
+ * /root/reference/src/ebcc_codec.c:920-1090: every frame cut into spatial chunks, 1024 x 1024 by default, edge chunks padded
+ * by index clamping) needs: a chunk is a one-frame stream of the chunk geometry, the slab meets a chunk in one window, and
+ * that window lands in its own rectangle of the slab, at the slab's row pitch.  The reference's only read of such a container
+ * is ebcc_decode_chunking (src/ebcc_codec.c:1322-1449), every chunk of every time step. */
+typedef struct { size_t frame, row0, col0, rows, cols, out_offset, out_pitch; } ebcc_hip_placed_box;
+/* at most the context's capacity of frames (n_frames), d_out on the device */
+int ebcc_hip_decode_frames_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                  const ebcc_hip_placed_box *boxes, size_t n_boxes, float *d_out, size_t out_floats);
+/* any number of frames, batches on the two engine sets */
+int ebcc_hip_decode_shard_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                 const ebcc_hip_placed_box *boxes, size_t n_boxes, float *d_out, size_t out_floats);
+/* pageable host output */
+int ebcc_hip_decode_host_frames_placed(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                       const ebcc_hip_placed_box *boxes, size_t n_boxes, float *h_out, size_t out_floats);
+
+/* The slab [t0, t0 + nt) x [row0, row0 + rows) x [col0, col0 + cols) of an array of `dims` stored in chunks of `chunk_dims`. */
+typedef struct { size_t t0, row0, col0, nt, rows, cols; } ebcc_hip_slab;
+/* The placed boxes of a slab (host logic, no device work): one box per chunk the slab meets, in increasing linear chunk index
+ * (C order over (t, chunk row, chunk column), as the container stores the chunks); `frame` is that index, the window is the
+ * slab cut with the chunk's real (unpadded) part, in chunk coordinates, and the placement is that of a compact
+ * [nt][rows][cols] output (pitch `cols`).  boxes may be NULL: the call then only counts.  Returns the number of boxes; -1 with
+ * `boxes` untouched for an empty slab or one not inside dims, zero dims, chunk_dims[0] != 1, chunk dims ebcc_encode_chunking
+ * would refuse, or max_boxes too small. */
+long ebcc_hip_slab_plan(const size_t dims[3], const size_t chunk_dims[3], const ebcc_hip_slab *slab,
+                        ebcc_hip_placed_box *boxes, size_t max_boxes);
+/* dims and chunk_dims of an EBCK container, whose header and chain of `u64 nbytes | stream` entries are checked as
+ * ebcc_decode_chunking checks them.  0 = ok, 1 = not a container or a damaged one (message). */
+int ebcc_hip_container_info(const uint8_t *data, size_t size, size_t dims[3], size_t chunk_dims[3]);
+/* The slab of a container of one-frame chunks, out [nt][rows][cols]: ctx is a context of the chunk geometry, of any
+ * capacity (the chunks the slab meets run as batches on the two engine sets).  Of a chunk the slab does not meet only the
+ * length field is read.  Refused with a message: data that is not an EBCK container (a plain frame stream has the window
+ * decode), chunks of several frames, a context of another geometry, and whatever ebcc_hip_slab_plan refuses. */
+int ebcc_hip_decode_container_slab(ebcc_hip_ctx *ctx, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, float *d_out);
+int ebcc_hip_decode_container_slab_host(ebcc_hip_ctx *ctx, const uint8_t *data, size_t size, const ebcc_hip_slab *slab, float *h_out);
+/* The same on the engines ebcc_decode_chunking keeps between calls (one device): *out_buffer receives a malloc'd array
+ * (free_buffer) as with ebcc_decode_chunking, whatever it held.  Returns the number of floats, 0 on failure (message logged). */
+size_t ebcc_decode_chunking_slab(uint8_t *data, size_t size, const ebcc_hip_slab *slab, float **out_buffer);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
