@@ -8,6 +8,10 @@ instead: only the chunks it meets are read, of those only the code-blocks it dep
 goes straight to its place in the result (include/ebcc_hip.h: placed boxes).  The result is bit for bit
 `decode_chunking(buf)[t, rows, cols]`.
 
+`encode_resident` is the write side for an array that lies on the device: the container `ebcc_encode_chunking` (or, with
+`compat`, `ebcc_encode_chunking_compat`, global range included) gives for the same array on the host, byte for byte, with the
+padded chunks gathered on the device (include/ebcc_hip.h: container encode from the device).
+
 Only numpy and ctypes are needed.
 """
 import ctypes
@@ -32,6 +36,9 @@ def _lib():
     lib.ebcc_decode_chunking.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     lib.ebcc_decode_chunking.restype = ctypes.c_size_t
     lib.free_buffer.argtypes = [ctypes.c_void_p]
+    lib.ebcc_hip_container_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    lib.ebcc_hip_encode_container.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.POINTER(ctypes.c_size_t)]
     return lib
 
 
@@ -113,3 +120,39 @@ def read_slab(buf, t=None, rows=None, cols=None, out=None, codec=None):
         return got.copy()
     out.reshape(nt, nr, nc)[...] = got
     return out.reshape(nt, nr, nc)
+
+
+def plan(cfg, compat=False):
+    """(chunk_dims, n_chunks) `ebcc_encode_chunking` (compat: `ebcc_encode_chunking_compat`) would use for cfg.dims /
+    cfg.chunk_dims - cfg: a h5_batch.CodecConfig; all-zero chunk_dims stand for the entry point's default.  ValueError for
+    what those refuse.  Host logic, no device."""
+    lib = _lib()
+    chunk_dims, n = (ctypes.c_size_t * 3)(), ctypes.c_size_t()
+    if lib.ebcc_hip_container_plan(ctypes.byref(cfg), int(bool(compat)), chunk_dims, ctypes.byref(n)):
+        raise ValueError((lib.ebcc_hip_last_error() or b"?").decode())
+    return tuple(int(v) for v in chunk_dims), int(n.value)
+
+
+def encode_resident(ptr, dims, cfg, codec, compat=False):
+    """The EBCK container of a (nt, H, W) float32 array that lies on the device -> bytes, equal byte for byte to
+    `ebcc_encode_chunking` (compat: `ebcc_encode_chunking_compat`) of the same array on the host.  `ptr`: the array's device
+    address as an int, or an object with `data_ptr()` (a contiguous torch tensor on the codec's device); 4-byte alignment is
+    enough.  `dims`: the array's shape.  `cfg`: a h5_batch.CodecConfig with the codec parameters and chunk_dims (its dims are
+    taken from `dims`).  `codec`: a h5_batch.BatchCodec of the chunk geometry `plan` gives, any capacity.  ValueError for what
+    the call refuses or NaN / Inf in the array, RuntimeError for what the encode reports."""
+    lib = _lib()
+    c = type(cfg).from_buffer_copy(cfg)
+    c.dims[:] = [int(v) for v in dims]
+    address = int(ptr.data_ptr()) if hasattr(ptr, "data_ptr") else int(ptr)
+    chunk_dims, _ = plan(c, compat)
+    if chunk_dims[0] != 1:
+        raise ValueError(f"chunks of {chunk_dims[0]} frames are not supported: one-frame chunks only")
+    if (codec.h, codec.w) != chunk_dims[1:]:
+        raise ValueError(f"the codec's frames are {codec.h} x {codec.w}, the chunks {chunk_dims[1]} x {chunk_dims[2]}")
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    rc = lib.ebcc_hip_encode_container(codec.ctx, address, ctypes.byref(c), int(bool(compat)), ctypes.byref(out), ctypes.byref(n))
+    if rc:
+        raise (ValueError if rc == 2 else RuntimeError)("ebcc_hip_encode_container: " + (lib.ebcc_hip_last_error() or b"?").decode())
+    buf = ctypes.string_at(out.value, n.value)
+    lib.free_buffer(out)
+    return buf

@@ -1,6 +1,7 @@
 // host_codec.hip - the reference's C API (include/ebcc_codec.h) on top of the MI355X engine: engines per device and
 // frame geometry, concurrent slices and alternating engine sets of a batch, host <-> device copies, the EBCK chunk
 // container (/root/reference/src/ebcc_codec.c:920-1090, :1322-1449), and the batch entry points of include/ebcc_hip.h.
+// Two kernels live here, beside the host loops they stand for: the chunk gather and the range of an array on the device.
 // The frame codec itself is batch_codec.hip, the HDF5 plugin h5z_filter.hip, the host services host_pool.hip (host.hpp).
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <climits>
@@ -240,6 +241,8 @@ bool chunk_engines(int device, int H, int W, size_t chunks, size_t tiles, ebcc_h
     return true;
 }
 
+size_t cdiv(size_t a, size_t b) { return a / b + (a % b != 0); }
+
 // Chunk <-> array copies of the chunking entry points (reference :311-370) as row copies: a chunk is a box, its rows
 // are contiguous in the array; rows / frames / columns past the array's edge repeat the last one (index clamping).
 struct ChunkBox {
@@ -275,6 +278,121 @@ struct ChunkBox {
                 memcpy(out + ((org[0] + z) * dims[1] + org[1] + y) * dims[2] + org[2], src + (z * cd[1] + y) * cd[2], w * sizeof(float));
     }
 };
+
+// ChunkBox::gather for an array on the device (one-frame chunks): chunks [first, first + gridDim.y) -> [chunk][ch][cw] at dst.
+// A destination row is one contiguous run, cut into slots of four floats; a thread takes slots i, i + step, .. of its chunk,
+// four of them in flight.  A slot that lies inside the real width of a source row on a 16-byte boundary is one 16-byte load,
+// any other four clamped 4-byte loads (the padding columns repeat the row's last real sample, the padding rows the last row);
+// a slot of a destination row on a 16-byte boundary is one 16-byte store.  Which width is taken changes no value.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct GatherArgs {
+    const float *src;
+    float *dst;
+    size_t H, W, cnt1, cnt2, first;
+    unsigned ch, cw;
+};
+__global__ __launch_bounds__(256) void k_gather_chunks(GatherArgs a)
+{
+    const size_t cl = a.first + blockIdx.y;
+    const size_t r0 = (cl / a.cnt2 % a.cnt1) * a.ch, c0 = (cl % a.cnt2) * a.cw, t = cl / a.cnt2 / a.cnt1;
+    const unsigned w = (unsigned) min((size_t) a.cw, a.W - c0);                     // real columns of this chunk
+    const unsigned spr = (a.cw + 3) / 4, slots = a.ch * spr, step = gridDim.x * 256;
+    const float *plane = a.src + t * a.H * a.W + c0;
+    float *out = a.dst + (size_t) blockIdx.y * a.ch * a.cw;
+    for (unsigned i0 = blockIdx.x * 256 + threadIdx.x; i0 < slots; i0 += 4 * step) {
+        f32x4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned i = i0 + k * step;
+            if (i < slots) {
+                const unsigned y = i / spr, x = 4 * (i - y * spr);
+                const float *row = plane + min(r0 + y, a.H - 1) * a.W;
+                if (x + 4 <= w && ((uintptr_t) row & 15) == 0) v[k] = *reinterpret_cast<const f32x4 *>(row + x);
+                else v[k] = f32x4{row[min(x, w - 1)], row[min(x + 1, w - 1)], row[min(x + 2, w - 1)], row[min(x + 3, w - 1)]};
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned i = i0 + k * step;
+            if (i < slots) {
+                const unsigned y = i / spr, x = 4 * (i - y * spr);
+                float *row = out + (size_t) y * a.cw;
+                if (x + 4 <= a.cw && ((uintptr_t) row & 15) == 0) *reinterpret_cast<f32x4 *>(row + x) = v[k];
+                else {
+                    row[x] = v[k].x;
+                    if (x + 1 < a.cw) row[x + 1] = v[k].y;
+                    if (x + 2 < a.cw) row[x + 2] = v[k].z;
+                    if (x + 3 < a.cw) row[x + 3] = v[k].w;
+                }
+            }
+        }
+    }
+}
+// chunks [first, first + count) of a [..][H][W] array in chunks of ch x cw, enqueued on s (cnt1 x cnt2 chunks a frame)
+void launch_gather_chunks(const float *d_array, size_t H, size_t W, size_t ch, size_t cw, size_t first, size_t count, float *d_out, hipStream_t s)
+{
+    const size_t slots = ch * ((cw + 3) / 4);
+    const unsigned bx = (unsigned) std::min<size_t>(std::max<size_t>(1, slots / (256 * 4)), 64);
+    for (size_t lo = 0; lo < count; lo += 65535) {                  // (gridDim.y)
+        const size_t k = std::min<size_t>(65535, count - lo);
+        const GatherArgs a{d_array, d_out + lo * ch * cw, H, W, cdiv(H, ch), cdiv(W, cw), first + lo, (unsigned) ch, (unsigned) cw};
+        hipLaunchKernelGGL(k_gather_chunks, dim3(bx, (unsigned) k), dim3(256), 0, s, a);
+    }
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+// Global minimum and maximum of n floats as order keys (float_order_key: -0 is +0), and whether a NaN or an Inf is among
+// them: out = {min key, max key, flag}, set to {~0, 0, 0} before the launch.  Any 4-byte alignment: the floats in front of the
+// first 16-byte boundary and behind the last whole 16 bytes go one by one, the rest 16 bytes per lane, two loads in flight
+// (as k_in_minmax, j2k_analysis.hip).  Minimum and maximum do not depend on the order: the result is exact.
+__global__ __launch_bounds__(256) void k_array_range(const float *__restrict__ x, size_t n, unsigned *out)
+{
+    unsigned kmin = ~0u, kmax = 0u;
+    int bad = 0;
+    auto take = [&](float v) {
+        if (isnan(v) || isinf(v)) bad = 1;
+        const unsigned k = float_order_key(v);
+        kmin = min(kmin, k);
+        kmax = max(kmax, k);
+    };
+    const size_t gid = (size_t) blockIdx.x * blockDim.x + threadIdx.x, step = (size_t) gridDim.x * blockDim.x;
+    const size_t lead = (size_t) ((16 - ((uintptr_t) x & 15)) & 15) / 4, head = lead < n ? lead : n, n4 = (n - head) >> 2;
+    if (gid < head) take(x[gid]);
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + head);
+    size_t i = gid;
+    for (; i + step < n4; i += 2 * step) {
+        const f32x4 p = x4[i], q = x4[i + step];
+        take(p.x); take(p.y); take(p.z); take(p.w);
+        take(q.x); take(q.y); take(q.z); take(q.w);
+    }
+    if (i < n4) { const f32x4 p = x4[i]; take(p.x); take(p.y); take(p.z); take(p.w); }
+    if (head + 4 * n4 + gid < n) take(x[head + 4 * n4 + gid]);
+    for (int d = 32; d >= 1; d >>= 1) {
+        kmin = min(kmin, (unsigned) __shfl_xor((int) kmin, d));
+        kmax = max(kmax, (unsigned) __shfl_xor((int) kmax, d));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&out[0], kmin);
+        atomicMax(&out[1], kmax);
+    }
+    if (bad) out[2] = 1;
+}
+float float_of_order_key(uint32_t k) { return u2f((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+// -> 0 and {min, max}, or 2: NaN / Inf among the n floats (mm untouched).  Device current, the context the caller's alone.
+int array_range(ebcc_hip_ctx *ctx, const float *d_data, size_t n, float mm[2])
+{
+    unsigned *d = (unsigned *) ctx->d_counter, *h = (unsigned *) ctx->h_counter;
+    h[0] = ~0u; h[1] = 0; h[2] = 0;
+    EBCC_HIP_CHECK(hipMemcpyAsync(d, h, 3 * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+    const unsigned blocks = (unsigned) std::min<size_t>(std::max<size_t>(1, n / (256 * 8)), 2048);
+    hipLaunchKernelGGL(k_array_range, dim3(blocks), dim3(256), 0, ctx->stream, d_data, n, d);
+    EBCC_HIP_LAUNCH_CHECK();
+    EBCC_HIP_CHECK(hipMemcpyAsync(h, d, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    wait_stream(ctx->stream);
+    if (h[2]) return 2;
+    mm[0] = float_of_order_key(h[0]); mm[1] = float_of_order_key(h[1]);
+    return 0;
+}
 
 // ================================================================================================
 // slices of a batch
@@ -743,7 +861,6 @@ int decode_host(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *stream
 }
 
 // ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
-size_t cdiv(size_t a, size_t b) { return a / b + (a % b != 0); }
 // The container as ebcc_decode_chunking checks it: the header, then the chain of `u64 nbytes | stream` entries - of a chunk only
 // the length field is read.  parse: "" or what is wrong with it (the reference's messages).
 struct Container {
@@ -816,6 +933,119 @@ int container_slab(const char *who, ebcc_hip_ctx *ctx, const uint8_t *data, size
     const DecodeRegion region = DecodeRegion::placed_list(boxes.data(), boxes.size(), slab->nt * slab->rows * slab->cols);
     return host ? decode_host(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region)
                 : decode_resident(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region, false);
+}
+
+// The container of the chunk streams outs[c] / sizes[c] (:975-992, :1028-1046): header, then `u64 nbytes | stream` per chunk.
+// malloc'd, NULL without memory (logged); the streams stay the caller's.
+uint8_t *assemble_container(const size_t dims[3], const size_t cd[3], size_t nchunks, size_t csize, uint8_t *const *outs, const size_t *sizes, size_t *out_len)
+{
+    size_t len = sizeof(ChunkHeader);
+    for (size_t c = 0; c < nchunks; c++) len += 8 + sizes[c];
+    uint8_t *o = (uint8_t *) malloc(len), *p = o;
+    if (!o) { log_fatal("out of memory"); return nullptr; }
+    ChunkHeader hd;
+    memset(&hd, 0, sizeof hd);
+    memcpy(hd.magic, EBCC_CHUNKING_HEADER_MAGIC, 4);
+    hd.version = EBCC_CHUNKING_HEADER_VERSION; hd.ndims = NDIMS;
+    for (int i = 0; i < 3; i++) { hd.dims[i] = dims[i]; hd.chunk_dims[i] = cd[i]; }
+    hd.num_chunks = nchunks; hd.chunk_size = csize;
+    memcpy(p, &hd, sizeof hd); p += sizeof hd;
+    for (size_t c = 0; c < nchunks; c++) {
+        uint64_t nb = sizes[c];
+        memcpy(p, &nb, 8); p += 8;
+        memcpy(p, outs[c], sizes[c]); p += sizes[c];
+    }
+    *out_len = len;
+    return o;
+}
+
+// ---- container encode from the device ---------------------------------------------------------------
+// What ebcc_encode_chunking (compat: ebcc_encode_chunking_compat, :1059-1076) makes of config->dims / chunk_dims: the chunk
+// dims, counts and sizes, or what it refuses - and, which the host scan leaves out, a product of the dims that overflows
+// (:953-964, :1079-1083).  "" or the message.
+struct ContainerPlan {
+    ChunkBox box;
+    size_t csize = 0, nchunks = 0, total = 0, padded = 0;
+    std::string make(const codec_config_t *cfg, bool compat)
+    {
+        char text[200];
+        const size_t *dims = cfg->dims;
+        size_t *cd = box.cd;
+        bool all_zero = true;
+        for (int i = 0; i < 3; i++) { box.dims[i] = dims[i]; cd[i] = cfg->chunk_dims[i]; if (cd[i]) all_zero = false; }
+        if (all_zero) {
+            cd[0] = compat ? 1 : dims[0];
+            for (int i = 1; i < 3; i++) cd[i] = compat && dims[i] > EBCC_MAX_INTERNAL_IMAGE_DIM ? 1024 : dims[i];
+        }
+        if (!dims_are_valid(cd)) {
+            snprintf(text, sizeof text, "Invalid chunking dimensions: product(chunk_dims[0..1]) and chunk_dims[2] must be between %d and %d",
+                     EBCC_MIN_INTERNAL_IMAGE_DIM, EBCC_MAX_INTERNAL_IMAGE_DIM);
+            return text;
+        }
+        for (int i = 0; i < 3; i++) {
+            if (dims[i] == 0 || cd[i] == 0) return "Invalid chunking dimensions: dims and chunk_dims must be non-zero";
+            box.cnt[i] = cdiv(dims[i], cd[i]);
+        }
+        if (cd[0] != 1 && !tile_height_supported(cd[1])) {
+            snprintf(text, sizeof text, "chunks holding %zu frames of %zu rows are not supported; use chunk_dims[0] = 1", cd[0], cd[1]);
+            return text;
+        }
+        auto product = [](const size_t v[3], size_t *out) { return !__builtin_mul_overflow(v[0], v[1], out) && !__builtin_mul_overflow(*out, v[2], out); };
+        size_t bytes;
+        if (!product(cd, &csize) || !product(box.cnt, &nchunks) || !product(dims, &total) || __builtin_mul_overflow(total, sizeof(float), &bytes))
+            return "Invalid chunking dimensions: size overflow";
+        if (__builtin_mul_overflow(csize, nchunks, &padded) || __builtin_mul_overflow(padded, sizeof(float), &bytes))
+            return "Invalid chunking dimensions: padded size overflow";
+        return "";
+    }
+    void warn_padding() const                                   // :965-969
+    {
+        if (padded > total && padded - total > total / 10)
+            log_warn("Chunk padding adds %lu values over %lu real values (%.2f%%)", padded - total, total, ((double) (padded - total) / (double) total) * 100.0);
+    }
+};
+
+// The checks of the two encode entry points, in their order: the plan, one-frame chunks, the context's geometry, the range of
+// chunks (count 0: all of them).  0, or 1 with the message set.
+int array_plan(const char *who, ebcc_hip_ctx *ctx, const codec_config_t *cfg, bool compat, bool defaults, size_t first, size_t count, ContainerPlan &plan)
+{
+    if (!defaults && !cfg->chunk_dims[0] && !cfg->chunk_dims[1] && !cfg->chunk_dims[2]) { set_error("%s: config->chunk_dims must be set", who); return 1; }
+    const std::string bad = plan.make(cfg, compat);
+    if (!bad.empty()) { set_error("%s: %s", who, bad.c_str()); return 1; }
+    const size_t *cd = plan.box.cd;
+    if (cd[0] != 1) { set_error("%s: chunks of %zu frames (one-frame chunks only)", who, cd[0]); return 1; }
+    if (cd[1] != (size_t) ctx->height || cd[2] != (size_t) ctx->width) {
+        set_error("%s: the context's frames are %d x %d, the chunks %zu x %zu", who, ctx->height, ctx->width, cd[1], cd[2]);
+        return 1;
+    }
+    if (first > plan.nchunks || count > plan.nchunks - first) {
+        set_error("%s: chunks [%zu, +%zu) of %zu", who, first, count, plan.nchunks);
+        return 1;
+    }
+    return 0;
+}
+
+// The streams of chunks [first, first + count) of a planned array on the device: batches of the context's capacity on the
+// alternating sets.  A batch's padded chunks are gathered into its engine set's staging buffer, on that set's stream, and the
+// stage waits for them: the slices read them on streams of their own.  Chunks that are whole frames are coded where they lie.
+int encode_array_chunks(const char *who, ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *cfg, const ContainerPlan &plan,
+                        size_t first, size_t count, uint8_t **outs, size_t *sizes)
+{
+    const ChunkBox &box = plan.box;
+    codec_config_t cc = *cfg;
+    for (int i = 0; i < 3; i++) { cc.dims[i] = box.cd[i]; cc.chunk_dims[i] = 0; }
+    const size_t csize = plan.csize, cap = std::min(count, ctx->max_frames);
+    PhaseTimer pt[2];
+    return encode_call(who, ctx, d_array, count, &cc, outs, sizes, [&] {
+        return encode_batches_alternating(ctx, count, &cc, outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
+            if (box.slabs()) return d_array + (first + lo) * csize;
+            float *d = io_buffer(set, cap * csize * sizeof(float));
+            launch_gather_chunks(d_array, box.dims[1], box.dims[2], box.cd[1], box.cd[2], first + lo, cnt, d, set->stream);
+            wait_stream(set->stream);
+            pt[set != ctx].mark("array chunks: gather");
+            return (const float *) d;
+        });
+    });
 }
 
 }  // namespace
@@ -1069,6 +1299,99 @@ int ebcc_hip_decode_container_slab_host(ebcc_hip_ctx *ctx, const uint8_t *data, 
     EBCC_API_CATCH(1)
 }
 
+// ---- container encode from the device (include/ebcc_hip.h) ------------------------------------------
+int ebcc_hip_container_plan(const codec_config_t *config, int compat, size_t chunk_dims[3], size_t *n_chunks)
+{
+    EBCC_API_TRY
+    if (!config) { set_error("ebcc_hip_container_plan: bad arguments"); return 1; }
+    ContainerPlan plan;
+    const std::string bad = plan.make(config, compat != 0);
+    if (!bad.empty()) { set_error("ebcc_hip_container_plan: %s", bad.c_str()); return 1; }
+    for (int i = 0; i < 3; i++) if (chunk_dims) chunk_dims[i] = plan.box.cd[i];
+    if (n_chunks) *n_chunks = plan.nchunks;
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
+int ebcc_hip_array_range(ebcc_hip_ctx *ctx, const float *d_data, size_t n, float minmax[2])
+{
+    if (!ctx || !d_data || !minmax || n < 1) { set_error("ebcc_hip_array_range: bad arguments"); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        const int rc = array_range(ctx, d_data, n, minmax);
+        if (rc == 2) set_error("ebcc_hip_array_range: NaN or Inf found in the data");
+        return rc;
+    });
+}
+
+int ebcc_hip_gather_chunks(ebcc_hip_ctx *ctx, const float *d_array, const size_t dims[3], const size_t chunk_dims[3], size_t first, size_t count,
+                           float *d_out)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_gather_chunks";
+    if (!ctx || !d_array || !dims || !chunk_dims || !d_out || count < 1) { set_error("%s: bad arguments", who); return 1; }
+    codec_config_t cfg{};
+    for (int i = 0; i < 3; i++) { cfg.dims[i] = dims[i]; cfg.chunk_dims[i] = chunk_dims[i]; }
+    ContainerPlan plan;
+    if (!dims[0] || !dims[1] || !dims[2]) { set_error("%s: zero dims", who); return 1; }
+    const std::string bad = plan.make(&cfg, false);
+    if (!bad.empty()) { set_error("%s: %s", who, bad.c_str()); return 1; }
+    if (chunk_dims[0] != 1) { set_error("%s: chunks of %zu frames (one-frame chunks only)", who, chunk_dims[0]); return 1; }
+    if (first > plan.nchunks || count > plan.nchunks - first) { set_error("%s: chunks [%zu, +%zu) of %zu", who, first, count, plan.nchunks); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        launch_gather_chunks(d_array, dims[1], dims[2], chunk_dims[1], chunk_dims[2], first, count, d_out, ctx->stream);
+        wait_stream(ctx->stream);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+
+int ebcc_hip_encode_array_chunks(ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *config, size_t first, size_t count,
+                                 uint8_t **out_streams, size_t *out_sizes)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_encode_array_chunks";
+    if (!ctx || !d_array || !config || !out_streams || !out_sizes || count < 1) { set_error("%s: bad arguments", who); return 1; }
+    log_set_level_from_env();
+    ContainerPlan plan;
+    if (array_plan(who, ctx, config, false, false, first, count, plan)) return 1;
+    plan.warn_padding();
+    return encode_array_chunks(who, ctx, d_array, config, plan, first, count, out_streams, out_sizes);
+    EBCC_API_CATCH(1)
+}
+
+int ebcc_hip_encode_container(ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *config, int compat, uint8_t **out, size_t *out_size)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_encode_container";
+    if (out) *out = nullptr;
+    if (out_size) *out_size = 0;
+    if (!ctx || !d_array || !config || !out || !out_size) { set_error("%s: bad arguments", who); return 1; }
+    log_set_level_from_env();
+    ContainerPlan plan;
+    if (array_plan(who, ctx, config, compat != 0, true, 0, 0, plan)) return 1;
+    codec_config_t c = *config;
+    if (compat && c.residual_compression_type == RELATIVE_ERROR) {                                 // :1078-1087
+        float mm[2];
+        const int rc = on_device(ctx->device, 1, [&] { return array_range(ctx, d_array, plan.total, mm); });
+        if (rc == 2) { log_fatal("NaN or Inf found in data"); set_error("%s: NaN or Inf found in the data", who); }
+        if (rc) return rc;
+        c.error *= mm[1] - mm[0];
+        c.residual_compression_type = MAX_ERROR;
+    }
+    plan.warn_padding();
+    std::vector<uint8_t *> outs(plan.nchunks, nullptr);
+    std::vector<size_t> sizes(plan.nchunks, 0);
+    const int rc = encode_array_chunks(who, ctx, d_array, &c, plan, 0, plan.nchunks, outs.data(), sizes.data());
+    if (rc) return rc;
+    size_t len = 0;
+    uint8_t *o = assemble_container(plan.box.dims, plan.box.cd, plan.nchunks, plan.csize, outs.data(), sizes.data(), &len);
+    for (auto q : outs) free(q);
+    if (!o) { set_error("%s: out of memory", who); return 1; }
+    *out = o; *out_size = len;
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
 // The engines the reference-compatible entry points keep between calls (one per device and frame geometry, with their slice
 // engines and second set: tens of GB of device memory for 256 frames of 721 x 1440) are destroyed; the next call makes them
 // again.  Contexts made with ebcc_hip_create are the caller's and are not touched.
@@ -1263,23 +1586,10 @@ size_t ebcc_encode_chunking(float *data, codec_config_t *config, uint8_t **out_b
         for (auto p : outs) free(p);
         return 0;
     }
-    size_t len = sizeof(ChunkHeader);
-    for (size_t c = 0; c < nchunks; c++) len += 8 + sizes[c];
-    uint8_t *o = (uint8_t *) malloc(len), *p = o;
-    if (!o) { log_fatal("out of memory"); for (auto q : outs) free(q); return 0; }
-    ChunkHeader hd;
-    memset(&hd, 0, sizeof hd);
-    memcpy(hd.magic, EBCC_CHUNKING_HEADER_MAGIC, 4);
-    hd.version = EBCC_CHUNKING_HEADER_VERSION; hd.ndims = NDIMS;
-    for (int i = 0; i < 3; i++) { hd.dims[i] = config->dims[i]; hd.chunk_dims[i] = cd[i]; }
-    hd.num_chunks = nchunks; hd.chunk_size = csize;
-    memcpy(p, &hd, sizeof hd); p += sizeof hd;
-    for (size_t c = 0; c < nchunks; c++) {
-        uint64_t nb = sizes[c];
-        memcpy(p, &nb, 8); p += 8;
-        memcpy(p, outs[c], sizes[c]); p += sizes[c];
-        free(outs[c]);
-    }
+    size_t len = 0;
+    uint8_t *o = assemble_container(config->dims, cd, nchunks, csize, outs.data(), sizes.data(), &len);
+    for (auto q : outs) free(q);
+    if (!o) return 0;
     *out_buffer = o;
     return len;
 }

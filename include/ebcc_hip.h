@@ -272,6 +272,41 @@ int ebcc_hip_decode_container_slab_host(ebcc_hip_ctx *ctx, const uint8_t *data, 
  * (free_buffer) as with ebcc_decode_chunking, whatever it held.  Returns the number of floats, 0 on failure (message logged). */
 size_t ebcc_decode_chunking_slab(uint8_t *data, size_t size, const ebcc_hip_slab *slab, float **out_buffer);
 
+/* ---- container encode from the device --------------------------------------------------------
+ * The write side of the above: a [nt][H][W] array of any size that lies on the device -> the EBCK container
+ * ebcc_encode_chunking / ebcc_encode_chunking_compat (/root/reference/src/ebcc_codec.c:920-1090) give for the same array on
+ * the host, byte for byte.  The padded chunks are gathered on the device, a batch at a time, into the engine set's staging
+ * buffer (edge chunks by index clamping, :339-351); no padded copy of the whole array is made, and chunks that are whole
+ * frames of the array are coded where they lie.  d_array needs 4-byte alignment only and is never written.
+ * Refused with return value 1, a message (ebcc_hip_last_error) and nothing written or allocated for the caller: zero dims,
+ * chunk dims ebcc_encode_chunking refuses, dims whose product overflows size_t, chunk_dims[0] != 1 (one-frame chunks only), a
+ * context whose frames are not the chunks, first + count beyond the chunk count.  One-frame chunks only. */
+
+/* chunk dims and chunk count ebcc_encode_chunking (compat = 0) / ebcc_encode_chunking_compat (compat = 1) would use for
+ * config->dims / config->chunk_dims: host logic, no device.  0 = ok, 1 = whatever those refuse (message). */
+int ebcc_hip_container_plan(const codec_config_t *config, int compat, size_t chunk_dims[3], size_t *n_chunks);
+/* global min / max of n device floats; 0 = ok, 1 = error, 2 = NaN / Inf present (minmax untouched).  Any 4-byte aligned
+ * address; ctx: any context of the device (its stream runs the kernel).  Exact: -0 counts as +0, as < and > see it. */
+int ebcc_hip_array_range(ebcc_hip_ctx *ctx, const float *d_data, size_t n, float minmax[2]);
+/* unit level: the padded chunks [first, first + count) of d_array [dims] as [count][chunk_dims[1]][chunk_dims[2]] at d_out;
+ * chunk_dims[0] must be 1; exactly that many floats are written.  Chunks count in C order over (t, chunk row, chunk column);
+ * sample (y, x) of the chunk at (t, r0, c0) is d_array[t][min(r0 + y, H - 1)][min(c0 + x, W - 1)].  d_array and d_out at any
+ * 4-byte aligned address; ctx: any context of the device. */
+int ebcc_hip_gather_chunks(ebcc_hip_ctx *ctx, const float *d_array, const size_t dims[3], const size_t chunk_dims[3],
+                           size_t first, size_t count, float *d_out);
+/* the streams of chunks [first, first + count) of the container ebcc_encode_chunking would write for d_array under
+ * `config` (dims = the array's, chunk_dims = the chunks'; all zero = refused here).  ctx: a context of the chunk
+ * geometry, any capacity: batches of its capacity, gathered into the engine set's staging buffer, on the two alternating
+ * sets.  Return and ownership as ebcc_hip_encode_shard (0 / 1 / 2 = NaN or Inf; all streams freed on failure). */
+int ebcc_hip_encode_array_chunks(ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *config,
+                                 size_t first, size_t count, uint8_t **out_streams, size_t *out_sizes);
+/* the whole container, malloc'd (free_buffer): byte for byte ebcc_encode_chunking (compat = 0) or
+ * ebcc_encode_chunking_compat (compat = 1: its default chunk dims, and RELATIVE_ERROR restated as
+ * MAX_ERROR with error * (global max - global min), the range taken on the device) of the same array on the host.
+ * 0 / 1 / 2 as above (2: nothing is coded, and the process goes on - the host forms exit); *out NULL on failure. */
+int ebcc_hip_encode_container(ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *config, int compat,
+                              uint8_t **out, size_t *out_size);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
