@@ -915,7 +915,7 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     if (region.kind != DecodeRegion::Frames) {
         const bool window = region.kind == DecodeRegion::Window;
         if (tiles != 1 || g.period != 1) { set_error("%s decode: chunks of several frames are not supported", window ? "window" : "box"); return 1; }
-        dev.kind = window ? J2kRegion::Window : region.kind == DecodeRegion::Placed ? J2kRegion::Placed : J2kRegion::Boxes;
+        dev.kind = window ? J2kRegion::Window : J2kRegion::List;
         dev.out = d_out;
         if (window) {
             if (!j2k_window_supported(g)) { set_error("window decode: frames of %d x %d are not supported (fewer than 3 columns)", g.H, g.W); return 1; }
@@ -928,27 +928,19 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
             keep.resize(blocks.size());
             int rect[4];
             for (size_t b = 0; b < blocks.size(); b++) keep[b] = j2k_window_keeps(g, blocks[b], dev.cone, rect) ? 1 : 0;
-        } else if (region.kind == DecodeRegion::Placed) {
-            std::vector<ebcc_hip_placed_box> local(region.placed, region.placed + region.n);
+        } else {
+            std::vector<ebcc_hip_placed_box> local(region.list, region.list + region.n);
             for (ebcc_hip_placed_box &b : local) b.frame -= region.frame0;
             keep_row = (size_t) g.nblocks;
             keep.resize(n * keep_row);
             boxes_reserve(ctx, region.n, sizeof(J2kBoxEntry) + sizeof(J2kPlacement));
             J2kBoxEntry *const h_table = static_cast<J2kBoxEntry *>(ctx->h_boxes), *const table = static_cast<J2kBoxEntry *>(ctx->d_boxes);
-            dev.list = J2kBoxList{h_table, table, region.n, 0, 0, reinterpret_cast<J2kPlacement *>(h_table + region.n), reinterpret_cast<J2kPlacement *>(table + region.n)};
-            if (!j2k_placed_check("placed decode", g, n, local.data(), local.size(), region.out_floats, keep.data(), h_table, dev.list.h_place, j2k_first_fused(jb),
-                                  &dev.list.rows, &dev.list.cols)) return 1;
-        } else {
-            std::vector<ebcc_hip_box> local(region.boxes, region.boxes + region.n);
-            for (ebcc_hip_box &b : local) b.frame -= region.frame0;
-            keep_row = (size_t) g.nblocks;
-            keep.resize(n * keep_row);
-            boxes_reserve(ctx, region.n, sizeof(J2kBoxEntry));
-            dev.list = J2kBoxList{static_cast<J2kBoxEntry *>(ctx->h_boxes), static_cast<J2kBoxEntry *>(ctx->d_boxes), region.n, (int) region.rows, (int) region.cols};
-            if (!j2k_boxes_check("box decode", g, n, local.data(), local.size(), region.rows, region.cols, keep.data(), dev.list.h_table, j2k_first_fused(jb))) return 1;
+            dev.list = J2kBoxList{h_table, table, reinterpret_cast<J2kPlacement *>(h_table + region.n), reinterpret_cast<J2kPlacement *>(table + region.n), region.n, 0, 0};
+            if (!j2k_list_check("list decode", g, n, local.data(), local.size(), region.out_floats, keep.data(), h_table, dev.list.h_place, j2k_first_fused(jb),
+                                &dev.list.rows, &dev.list.cols)) return 1;
         }
     }
-    const size_t out_pix = region.pixels(n_pix), n_out = region.outputs(n);     // samples of an output item; items
+    const size_t out_pix = region.pixels(n_pix);                      // samples of an output item
     int *const table = ctx->h_table;                                  // (pinned)
     const size_t table_ints = nt * (size_t) g.stride * 4;
     memset(table, 0, table_ints * sizeof(int));
@@ -1085,25 +1077,25 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
     if (any_resid) {
         if (s2 != s) EBCC_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_b, 0));
         // last row pass: field += residual (of a window or a box: its rows alone)
-        if (dev.kind == J2kRegion::Placed) launch_synthesis_tail_add_placed(d_out, rc->rb, dev.list.table, dev.list.place, dev.list.n, rc->d_active, s, dev.list.rows);
-        else if (dev.kind == J2kRegion::Boxes) launch_synthesis_tail_add_boxes(d_out, rc->rb, dev.list.table, dev.list.n, rc->d_active, s, dev.list.rows, dev.list.cols);
+        if (dev.kind == J2kRegion::List) launch_synthesis_tail_add_placed(d_out, rc->rb, dev.list.table, dev.list.place, dev.list.n, rc->d_active, s, dev.list.rows);
         else if (dev.kind == J2kRegion::Window) launch_synthesis_tail_add(d_out, rc->rb, (int) n, rc->d_active, s, dev.cone.row0, dev.cone.col0, dev.cone.rows, dev.cone.cols);
         else launch_synthesis_tail_add(view.DEC, rc->rb, (int) n, rc->d_active, s, 0, 0, rc->rb.g.size_y, rc->rb.g.size_x);
     }
     if (!direct) EBCC_HIP_CHECK(hipMemcpyAsync(d_out, jb.DEC, n * n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // constant chunks: fill on the host side of the copy (rare path) - one host image per constant frame, whatever the number
-    // of its items (which are in the order of their frames), kept until the one wait below
-    // (placed boxes: a pitched fill on the device, from the frame states and the tables that are there already)
+    // constant chunks: fill on the host side of the copy (rare path) - one host image per constant chunk, kept until the one
+    // wait below.  (a list: a pitched fill on the device, from the frame states and the tables that are there already)
     std::vector<std::vector<float>> fills;
-    bool placed_const = false;
-    for (size_t e = 0, last = (size_t) -1; e < n_out; e++) {
-        const size_t f = dev.lists() ? (size_t) dev.list.h_table[e].frame : e;
-        if (!rc->h_fs[f].const_field) continue;
-        if (dev.kind == J2kRegion::Placed) { placed_const = true; break; }
-        if (f != last) { fills.emplace_back(out_pix, rc->h_fs[f].minv); last = f; }
-        EBCC_HIP_CHECK(hipMemcpyAsync(d_out + e * out_pix, fills.back().data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
+    if (dev.kind == J2kRegion::List) {
+        bool any_const = false;
+        for (size_t e = 0; e < dev.list.n && !any_const; e++) any_const = rc->h_fs[dev.list.h_table[e].frame].const_field != 0;
+        if (any_const) launch_j2k_fill_placed(jb, dev.list, d_out, s);
+    } else {
+        for (size_t c = 0; c < n; c++) {
+            if (!rc->h_fs[c].const_field) continue;
+            fills.emplace_back(out_pix, rc->h_fs[c].minv);
+            EBCC_HIP_CHECK(hipMemcpyAsync(d_out + c * out_pix, fills.back().data(), out_pix * sizeof(float), hipMemcpyHostToDevice, s));
+        }
     }
-    if (placed_const) launch_j2k_fill_placed(jb, dev.list, d_out, s);
     wait_stream(s);
     pt.mark("decode: kernels");
     return 0;

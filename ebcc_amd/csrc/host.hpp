@@ -283,44 +283,33 @@ bool parse_frame(const uint8_t *d, size_t len, ParsedFrame &pf);
 //   Frames   a frame, whole: [n][frame pixels] (chunks of several frames: [n][tiles * H * W])
 //   Window   the window [row0, row0 + rows) x [col0, col0 + cols) of a frame, [n][rows][cols], from the code-blocks its dependency
 //            cone holds (J2kWindow); one-frame chunks only
-//   Boxes    a box of a list of `n` boxes of rows x cols in non-decreasing order of their frames, which count from the stream
-//            `frame0` of the batch; every stream of the batch is named by a box; [n][rows][cols]; one-frame chunks only
-//   Placed   a box of a list of `n` placed boxes (ebcc_hip_placed_box: each of its own size, at its own offset and pitch in
-//            an output of `out_floats` floats), otherwise as Boxes.  The items have no common size and a part of the list
-//            still writes to the whole output: at() does not move it.
+//   List     a box of a list of `n` placed boxes (ebcc_hip_placed_box: each of its own size, at its own offset and pitch in an
+//            output of `out_floats` floats) in non-decreasing order of their frames, which count from the stream `frame0` of
+//            the batch; every stream of the batch is named by a box; one-frame chunks only.  The items have no common size
+//            (rows x cols is 0 x 0) and a part of the list still writes to the whole output: its first item is item 0.
 struct DecodeRegion {
-    enum Kind { Frames, Window, Boxes, Placed } kind = Frames;
+    enum Kind { Frames, Window, List } kind = Frames;
     size_t row0 = 0, col0 = 0, rows = 0, cols = 0;
-    const ebcc_hip_box *boxes = nullptr;
-    size_t n = 0, frame0 = 0;
-    const ebcc_hip_placed_box *placed = nullptr;
-    size_t out_floats = 0;
-    static DecodeRegion window(size_t row0, size_t col0, size_t rows, size_t cols) { return DecodeRegion{Window, row0, col0, rows, cols, nullptr, 0, 0}; }
-    static DecodeRegion box_list(const ebcc_hip_box *boxes, size_t n, size_t rows, size_t cols) { return DecodeRegion{Boxes, 0, 0, rows, cols, boxes, n, 0}; }
-    static DecodeRegion placed_list(const ebcc_hip_placed_box *placed, size_t n, size_t out_floats) { return DecodeRegion{Placed, 0, 0, 0, 0, nullptr, n, 0, placed, out_floats}; }
-    bool lists() const { return kind == Boxes || kind == Placed; }
-    size_t pixels(size_t frame_pixels) const { return kind == Frames ? frame_pixels : rows * cols; }      // samples of an item (Placed: none in common, 0)
-    size_t outputs(size_t cnt) const { return lists() ? n : cnt; }                                        // items, over cnt streams
+    const ebcc_hip_placed_box *list = nullptr;
+    size_t n = 0, frame0 = 0, out_floats = 0;
+    static DecodeRegion window(size_t row0, size_t col0, size_t rows, size_t cols) { return DecodeRegion{Window, row0, col0, rows, cols}; }
+    static DecodeRegion placed_list(const ebcc_hip_placed_box *list, size_t n, size_t out_floats) { return DecodeRegion{List, 0, 0, 0, 0, list, n, 0, out_floats}; }
+    size_t pixels(size_t frame_pixels) const { return kind == Frames ? frame_pixels : rows * cols; }      // samples of an item
     // where the items from item `first` on go, in an output that holds them all
-    float *at(float *out, size_t first, size_t frame_pixels) const { return kind == Placed ? out : out + first * pixels(frame_pixels); }
+    float *at(float *out, size_t first, size_t frame_pixels) const { return out + first * pixels(frame_pixels); }
     // a window and boxes always go straight to the caller's array (single stores where pairs are not aligned); whole
     // frames only to one that is aligned the way the engine's buffers are
     bool direct(const void *d_out) const { return kind != Frames || ((uintptr_t) d_out & 255u) == 0; }
-    // the region of the streams lo .. lo + cnt - 1 and its first item: the region itself from item lo, or those streams' boxes -
-    // a contiguous part of the list, which is sorted by frame - with their frames counted from lo
+    // the region of the streams lo .. lo + cnt - 1 and its first item for at(): the region itself from item lo, or those streams'
+    // boxes - a contiguous part of the list, which is sorted by frame - with their frames counted from lo, placed from item 0
     DecodeRegion part(size_t lo, size_t cnt, size_t *first) const
     {
         DecodeRegion p = *this;
-        *first = lo;
-        if (!lists()) return p;
-        auto cut = [&](auto *list) {
-            auto before = [](const auto &x, size_t frame) { return x.frame < frame; };
-            auto *from = std::lower_bound(list, list + n, frame0 + lo, before);
-            p.n = (size_t) (std::lower_bound(from, list + n, frame0 + lo + cnt, before) - from);
-            *first = (size_t) (from - list);
-            return from;
-        };
-        if (kind == Boxes) p.boxes = cut(boxes); else p.placed = cut(placed);
+        *first = kind == List ? 0 : lo;
+        if (kind != List) return p;
+        auto before = [](const ebcc_hip_placed_box &b, size_t frame) { return b.frame < frame; };
+        p.list = std::lower_bound(list, list + n, frame0 + lo, before);
+        p.n = (size_t) (std::lower_bound(p.list, list + n, frame0 + lo + cnt, before) - p.list);
         p.frame0 = frame0 + lo;
         return p;
     }

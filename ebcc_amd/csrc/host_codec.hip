@@ -650,16 +650,21 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
 // The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
 // the slices slowed them down).  `prefault`: host threads are mapping the pages of `out`, joined before the first download.
 // Chunks of several frames are one decode_batch per batch: the slice engines have no tile geometry.
-// `region`: `out` holds its output items, and only they cross to the host; a batch's items are a contiguous part of them, and
-// the device image holds the most items any batch has.  Placed boxes: a batch's boxes lie compact in the device image, one
-// behind the other at pitch `cols` (PlacedStage), cross as one download into a host image of the same layout, and are put into
-// their rectangles of `out` row by row - nothing else of `out` is touched.
-struct PlacedStage {
+// `region`: `out` holds its output items, and only they cross to the host; a window's items of a batch are a contiguous part of
+// them.  A list: a batch's boxes lie compact in the device image, one behind the other at pitch `cols` (ListStage), and cross
+// as one download - straight to their place where they lie in `out` the same way, as the boxes of a compact
+// [n_boxes][rows][cols] array do, else into a host image of the same layout, from which they are put into their rectangles of
+// `out` row by row.  Nothing else of `out` is touched.
+struct ListStage {
     std::vector<ebcc_hip_placed_box> boxes;
     size_t floats = 0;
-    PlacedStage(const ebcc_hip_placed_box *list, size_t n) : boxes(list, list + n)
+    bool in_place = true;                                            // the staged layout is that of `out` from list[0].out_offset on
+    ListStage(const ebcc_hip_placed_box *list, size_t n) : boxes(list, list + n)
     {
-        for (ebcc_hip_placed_box &b : boxes) { b.out_offset = floats; b.out_pitch = b.cols; floats += b.rows * b.cols; }
+        for (ebcc_hip_placed_box &b : boxes) {
+            in_place = in_place && b.out_pitch == b.cols && b.out_offset == list[0].out_offset + floats;
+            b.out_offset = floats; b.out_pitch = b.cols; floats += b.rows * b.cols;
+        }
     }
     void place(const ebcc_hip_placed_box *list, const float *image, float *out) const
     {
@@ -672,28 +677,32 @@ int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap
                    float *out, Prefault *prefault, const DecodeRegion &region = DecodeRegion{})
 {
     const size_t n_pix = region.pixels(ctx->n_pix * tiles);
-    size_t most = cap, at = 0;
-    for (size_t lo = 0; lo < n; lo += cap) { const size_t k = std::min(cap, n - lo); most = std::max(most, region.part(lo, k, &at).outputs(k)); }
     auto one_batch = [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
         PhaseTimer pt;
         size_t first = 0;
         const DecodeRegion part = region.part(lo, k, &first);
-        if (part.kind == DecodeRegion::Placed) {
+        if (part.kind == DecodeRegion::List) {
             if (part.n == 0) return 0;
-            const PlacedStage stage(part.placed, part.n);
+            const ListStage stage(part.list, part.n);
             DecodeRegion staged = part;
-            staged.placed = stage.boxes.data(); staged.out_floats = stage.floats;
+            staged.list = stage.boxes.data(); staged.out_floats = stage.floats;
             float *d = io_buffer(set, stage.floats * sizeof(float));
+            pt.mark("host decode: device image");
             const int r = run_decode_slices(set, streams + lo, sizes + lo, k, d, staged);
             if (r) return r;
             pt.mark("host decode: decode");
-            std::vector<float> image(stage.floats);
-            copy_pageable(set, image.data(), d, stage.floats * sizeof(float), true);
-            stage.place(part.placed, image.data(), out);
+            if (prefault) prefault->join();
+            pt.mark("host decode: output pages");
+            if (stage.in_place) copy_pageable(set, out + part.list[0].out_offset, d, stage.floats * sizeof(float), true);
+            else {
+                std::vector<float> image(stage.floats);
+                copy_pageable(set, image.data(), d, stage.floats * sizeof(float), true);
+                stage.place(part.list, image.data(), out);
+            }
             pt.mark("host decode: download");
             return 0;
         }
-        float *d = io_buffer(set, most * n_pix * sizeof(float));
+        float *d = io_buffer(set, cap * n_pix * sizeof(float));
         pt.mark("host decode: device image");
         const int r = tiles > 1 ? decode_batch(set, streams + lo, sizes + lo, k, d, nullptr, tiles, rc, part)
                                 : run_decode_slices(set, streams + lo, sizes + lo, k, d, part);
@@ -701,7 +710,7 @@ int decode_to_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap
         pt.mark("host decode: decode");
         if (prefault) prefault->join();
         pt.mark("host decode: output pages");
-        copy_pageable(set, out + first * n_pix, d, part.outputs(k) * n_pix * sizeof(float), true);
+        copy_pageable(set, out + first * n_pix, d, k * n_pix * sizeof(float), true);
         pt.mark("host decode: download");
         return 0;
     };
@@ -781,13 +790,12 @@ int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, s
         return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * ctx->n_pix; });
     });
 }
-// The box list of a box-list entry point, as the call it stands for: the streams of the frames the boxes name, in their order,
-// with the boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
+// The list of a list entry point, as the call it stands for: the streams of the frames the boxes name, in their order, with the
+// boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
 struct BoxCall {
     std::vector<const uint8_t *> streams;
     std::vector<size_t> sizes;
-    std::vector<ebcc_hip_box> boxes;
-    std::vector<ebcc_hip_placed_box> placed;
+    std::vector<ebcc_hip_placed_box> list;
 };
 
 // The decode entry points: `region` as the caller states it, and the checks in their order - bad batch (`one_batch`, the _frames
@@ -803,27 +811,16 @@ int decode_region(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *&str
             set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is empty or not inside the %zu x %zu frame", who, row0, rows, col0, cols, H, W);
             return 1;
         }
-    } else if (region.kind == DecodeRegion::Placed) {
+    } else if (region.kind == DecodeRegion::List) {
         if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return 1; }
-        if (!j2k_placed_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.placed, region.n, region.out_floats)) return 1;
-        call.placed.assign(region.placed, region.placed + region.n);
+        if (!j2k_list_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.list, region.n, region.out_floats)) return 1;
+        call.list.assign(region.list, region.list + region.n);
         for (size_t e = 0; e < region.n; e++) {
-            const size_t f = region.placed[e].frame;
-            if (e == 0 || f != region.placed[e - 1].frame) { call.streams.push_back(streams[f]); call.sizes.push_back(sizes[f]); }
-            call.placed[e].frame = call.streams.size() - 1;
+            const size_t f = region.list[e].frame;
+            if (e == 0 || f != region.list[e - 1].frame) { call.streams.push_back(streams[f]); call.sizes.push_back(sizes[f]); }
+            call.list[e].frame = call.streams.size() - 1;
         }
-        region.placed = call.placed.data();
-        streams = call.streams.data(); sizes = call.sizes.data(); n_frames = call.streams.size();
-    } else if (region.kind == DecodeRegion::Boxes) {
-        if (ctx->tile_period != 1) { set_error("%s: chunks of several frames are not supported", who); return 1; }
-        if (!j2k_boxes_check(who, static_cast<const J2kBuffers *>(ctx->j2k)->geom, n_frames, region.boxes, region.n, region.rows, region.cols)) return 1;
-        call.boxes.assign(region.boxes, region.boxes + region.n);
-        for (size_t e = 0; e < region.n; e++) {
-            const size_t f = region.boxes[e].frame;
-            if (e == 0 || f != region.boxes[e - 1].frame) { call.streams.push_back(streams[f]); call.sizes.push_back(sizes[f]); }
-            call.boxes[e].frame = call.streams.size() - 1;
-        }
-        region.boxes = call.boxes.data();
+        region.list = call.list.data();
         streams = call.streams.data(); sizes = call.sizes.data(); n_frames = call.streams.size();
     }
     return 0;
@@ -850,14 +847,29 @@ int decode_resident(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *st
         });
     });
 }
-// host output: the output's pages are mapped while the GPU decodes
-int decode_host(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_out, const DecodeRegion &asked)
+// host output.  own_output: the output array is the call's to fill whole - frames, windows, the compact array of a _boxes entry
+// point - and its pages are mapped while the GPU decodes; else (placed boxes) it is not the call's to clear, and no page of it
+// is touched ahead of the boxes.  The entry point says which: the list does not.
+int decode_host(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, float *h_out, const DecodeRegion &asked,
+                bool own_output = true)
 {
     return decode_call(who, ctx, streams, sizes, n_frames, h_out, asked, false, [&](const DecodeRegion &region, const uint8_t *const *st, const size_t *sz, size_t n) {
-        // (placed boxes: the output is not the call's to clear - no page of it is touched ahead of the boxes)
-        Prefault prefault(h_out, region.kind == DecodeRegion::Placed ? 0 : region.outputs(n) * region.pixels(ctx->n_pix) * sizeof(float));
+        const size_t floats = region.kind == DecodeRegion::List ? region.out_floats : n * region.pixels(ctx->n_pix);
+        Prefault prefault(h_out, own_output ? floats * sizeof(float) : 0);
         return decode_to_host(ctx, nullptr, 1, ctx->max_frames, st, sz, n, h_out, &prefault, region);
     });
+}
+
+// The _boxes entry points: the placed list in which box e lies at index e of a compact [n_boxes][rows][cols] array
+// (j2k_boxes_as_placed), which is the call's to fill whole.
+int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
+                 size_t n_boxes, size_t rows, size_t cols, float *out, bool host, bool one_batch)
+{
+    std::vector<ebcc_hip_placed_box> placed;
+    size_t out_floats = 0;
+    if (!j2k_boxes_as_placed(who, boxes, n_boxes, rows, cols, placed, &out_floats)) return 1;
+    const DecodeRegion region = DecodeRegion::placed_list(placed.data(), placed.size(), out_floats);
+    return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
 // ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
@@ -931,7 +943,7 @@ int container_slab(const char *who, ebcc_hip_ctx *ctx, const uint8_t *data, size
     std::vector<ebcc_hip_placed_box> boxes;
     if (!slab_boxes(who, box, data, size, slab, (size_t) ctx->height, (size_t) ctx->width, boxes)) return 1;
     const DecodeRegion region = DecodeRegion::placed_list(boxes.data(), boxes.size(), slab->nt * slab->rows * slab->cols);
-    return host ? decode_host(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region)
+    return host ? decode_host(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region, false)
                 : decode_resident(who, ctx, box.ptrs.data(), box.lens.data(), box.nchunks, out, region, false);
 }
 
@@ -1194,26 +1206,26 @@ int ebcc_hip_decode_host_frames_window(ebcc_hip_ctx *ctx, const uint8_t *const *
 }
 
 // Box-list decode: boxes of rows x cols, each from the frame it names, bit for bit the crops of what the entry points without
-// boxes give; output [n_boxes][rows][cols].  The named frames are decoded as the batches of a call of their own (BoxCall).
+// boxes give; output [n_boxes][rows][cols] (decode_boxes).
 int ebcc_hip_decode_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
                                  size_t n_boxes, size_t rows, size_t cols, float *d_out)
 {
     EBCC_API_TRY
-    return decode_resident("ebcc_hip_decode_frames_boxes", ctx, streams, sizes, n_frames, d_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols), true);
+    return decode_boxes("ebcc_hip_decode_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, false, true);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_decode_shard_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
                                 size_t n_boxes, size_t rows, size_t cols, float *d_out)
 {
     EBCC_API_TRY
-    return decode_resident("ebcc_hip_decode_shard_boxes", ctx, streams, sizes, n_frames, d_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols), false);
+    return decode_boxes("ebcc_hip_decode_shard_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, d_out, false, false);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_decode_host_frames_boxes(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_box *boxes,
                                       size_t n_boxes, size_t rows, size_t cols, float *h_out)
 {
     EBCC_API_TRY
-    return decode_host("ebcc_hip_decode_host_frames_boxes", ctx, streams, sizes, n_frames, h_out, DecodeRegion::box_list(boxes, n_boxes, rows, cols));
+    return decode_boxes("ebcc_hip_decode_host_frames_boxes", ctx, streams, sizes, n_frames, boxes, n_boxes, rows, cols, h_out, true, false);
     EBCC_API_CATCH(1)
 }
 
@@ -1236,7 +1248,7 @@ int ebcc_hip_decode_host_frames_placed(ebcc_hip_ctx *ctx, const uint8_t *const *
                                        size_t n_boxes, float *h_out, size_t out_floats)
 {
     EBCC_API_TRY
-    return decode_host("ebcc_hip_decode_host_frames_placed", ctx, streams, sizes, n_frames, h_out, DecodeRegion::placed_list(boxes, n_boxes, out_floats));
+    return decode_host("ebcc_hip_decode_host_frames_placed", ctx, streams, sizes, n_frames, h_out, DecodeRegion::placed_list(boxes, n_boxes, out_floats), false);
     EBCC_API_CATCH(1)
 }
 

@@ -404,60 +404,8 @@ bool j2k_window_keeps(const J2kGeom &g, const J2kBlock &b, const J2kWindow &w, i
     return n[0] < n[1] && n[2] < n[3] && rect[0] < n[1] && n[0] < rect[1] && rect[2] < n[3] && n[2] < rect[3];
 }
 
-namespace {
-// a box of a checked list, of either kind
-struct BoxView { size_t frame, row0, col0, rows, cols; };
-// keep and table of a checked list whose box e is at(e) (j2k.hpp: j2k_boxes_check)
-template <class At>
-bool boxes_plan(const char *who, const J2kGeom &g, size_t n_frames, size_t n_boxes, At at, uint8_t *keep, J2kBoxEntry *table, int first_fused)
-{
-    std::vector<J2kBlock> blk;
-    make_j2k_geom(g.H, g.W, blk);
-    memset(keep, 0, n_frames * blk.size());
-    BoxView prev{};
-    for (size_t e = 0; e < n_boxes; e++) {
-        const BoxView b = at(e);
-        const bool repeat = e && b.frame == prev.frame && b.row0 == prev.row0 && b.col0 == prev.col0 && b.rows == prev.rows && b.cols == prev.cols;
-        prev = b;
-        if (table) { table[e] = repeat ? table[e - 1] : J2kBoxEntry{(int) b.frame, 0, 0, (int) b.row0, (int) b.col0}; table[e].out = (int) e; }
-        if (repeat) continue;
-        J2kWindow w;
-        if (!j2k_window_plan(g, b.row0, b.col0, b.rows, b.cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
-        for (int r = first_fused; table && r < kJ2kRes; r++) {
-            const J2kStripRange sp = j2k_cone_span(w, r);
-            table[e].strip0[r] = sp.strip0; table[e].strips[r] = sp.strips; table[e].pos0[r] = sp.pos0; table[e].pos1[r] = sp.pos1;
-        }
-        uint8_t *row = keep + b.frame * blk.size();
-        int rect[4];
-        for (size_t i = 0; i < blk.size(); i++)
-            if (!row[i] && j2k_window_keeps(g, blk[i], w, rect)) row[i] = 1;
-    }
-    return true;
-}
-}  // namespace
-
-bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
-                     uint8_t *keep, J2kBoxEntry *table, int first_fused)
-{
-    const size_t H = (size_t) g.H, W = (size_t) g.W;
-    if (!boxes || n_boxes < 1 || rows < 1 || cols < 1) { set_error("%s: an empty box list or empty boxes", who); return false; }
-    if (!j2k_window_supported(g)) { set_error("%s: frames of %d x %d are not supported (fewer than 3 columns)", who, g.H, g.W); return false; }
-    if (rows > H || cols > W) { set_error("%s: boxes of %zu x %zu are not inside the %zu x %zu frame", who, rows, cols, H, W); return false; }
-    for (size_t e = 0; e < n_boxes; e++) {
-        const ebcc_hip_box &b = boxes[e];
-        if (b.frame >= n_frames) { set_error("%s: box %zu names frame %zu of %zu", who, e, b.frame, n_frames); return false; }
-        if (e && b.frame < boxes[e - 1].frame) { set_error("%s: box %zu: the boxes are not in the order of their frames", who, e); return false; }
-        if (b.row0 > H - rows || b.col0 > W - cols) {                   // (no sums: they may overflow)
-            set_error("%s: box %zu, [%zu, +%zu) x [%zu, +%zu), is not inside the %zu x %zu frame", who, e, b.row0, rows, b.col0, cols, H, W);
-            return false;
-        }
-    }
-    if (!keep) return true;
-    return boxes_plan(who, g, n_frames, n_boxes, [&](size_t e) { return BoxView{boxes[e].frame, boxes[e].row0, boxes[e].col0, rows, cols}; }, keep, table, first_fused);
-}
-
-bool j2k_placed_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
-                      uint8_t *keep, J2kBoxEntry *table, J2kPlacement *place, int first_fused, int *max_rows, int *max_cols)
+bool j2k_list_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
+                    uint8_t *keep, J2kBoxEntry *table, J2kPlacement *place, int first_fused, int *max_rows, int *max_cols)
 {
     const size_t H = (size_t) g.H, W = (size_t) g.W;
     if (!boxes || n_boxes < 1) { set_error("%s: an empty box list", who); return false; }
@@ -484,10 +432,43 @@ bool j2k_placed_check(const char *who, const J2kGeom &g, size_t n_frames, const 
     if (max_rows) *max_rows = (int) most_rows;
     if (max_cols) *max_cols = (int) most_cols;
     if (!keep) return true;
-    if (place)
-        for (size_t e = 0; e < n_boxes; e++) place[e] = J2kPlacement{(int) boxes[e].rows, (int) boxes[e].cols, boxes[e].out_offset, boxes[e].out_pitch};
-    return boxes_plan(who, g, n_frames, n_boxes, [&](size_t e) { return BoxView{boxes[e].frame, boxes[e].row0, boxes[e].col0, boxes[e].rows, boxes[e].cols}; },
-                      keep, table, first_fused);
+    std::vector<J2kBlock> blk;
+    make_j2k_geom(g.H, g.W, blk);
+    memset(keep, 0, n_frames * blk.size());
+    for (size_t e = 0; e < n_boxes; e++) {
+        const ebcc_hip_placed_box &b = boxes[e];
+        if (place) place[e] = J2kPlacement{(int) b.rows, (int) b.cols, b.out_offset, b.out_pitch};
+        const bool repeat = e && b.frame == boxes[e - 1].frame && b.row0 == boxes[e - 1].row0 && b.col0 == boxes[e - 1].col0 &&
+                            b.rows == boxes[e - 1].rows && b.cols == boxes[e - 1].cols;
+        if (table) table[e] = repeat ? table[e - 1] : J2kBoxEntry{(int) b.frame, 0, (int) b.row0, (int) b.col0};
+        if (repeat) continue;
+        J2kWindow w;
+        if (!j2k_window_plan(g, b.row0, b.col0, b.rows, b.cols, w)) { set_error("%s: box %zu is not inside the frame", who, e); return false; }
+        for (int r = first_fused; table && r < kJ2kRes; r++) {
+            const J2kStripRange sp = j2k_cone_span(w, r);
+            table[e].strip0[r] = sp.strip0; table[e].strips[r] = sp.strips; table[e].pos0[r] = sp.pos0; table[e].pos1[r] = sp.pos1;
+        }
+        uint8_t *row = keep + b.frame * blk.size();
+        int rect[4];
+        for (size_t i = 0; i < blk.size(); i++)
+            if (!row[i] && j2k_window_keeps(g, blk[i], w, rect)) row[i] = 1;
+    }
+    return true;
+}
+
+bool j2k_boxes_as_placed(const char *who, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
+                         std::vector<ebcc_hip_placed_box> &placed, size_t *out_floats)
+{
+    size_t box_floats = 0;
+    if (!boxes || n_boxes < 1 || rows < 1 || cols < 1) { set_error("%s: an empty box list or empty boxes", who); return false; }
+    if (rows > 2047 || cols > 2047) { set_error("%s: boxes of %zu x %zu are not inside any frame", who, rows, cols); return false; }
+    if (__builtin_mul_overflow(rows, cols, &box_floats) || __builtin_mul_overflow(box_floats, n_boxes, out_floats)) {
+        set_error("%s: %zu boxes of %zu x %zu: size overflow", who, n_boxes, rows, cols);
+        return false;
+    }
+    placed.resize(n_boxes);
+    for (size_t e = 0; e < n_boxes; e++) placed[e] = ebcc_hip_placed_box{boxes[e].frame, boxes[e].row0, boxes[e].col0, rows, cols, e * box_floats, cols};
+    return true;
 }
 
 }  // namespace ebcc
@@ -507,7 +488,10 @@ __attribute__((visibility("default"))) int ebcc_hip_boxes_plan(size_t height, si
     g.period = 1; g.stride = g.nblocks;
     if (keep && max_blocks < blk.size()) { set_error("ebcc_hip_boxes_plan: keep has room for %zu of %zu code-blocks a frame", max_blocks, blk.size()); return -1; }
     std::vector<uint8_t> flags(keep ? n_frames * blk.size() : 0);      // (keep is not written by a call that refuses)
-    if (!j2k_boxes_check("ebcc_hip_boxes_plan", g, n_frames, boxes, n_boxes, rows, cols, keep ? flags.data() : nullptr)) return -1;
+    std::vector<ebcc_hip_placed_box> placed;
+    size_t out_floats = 0;
+    if (!j2k_boxes_as_placed("ebcc_hip_boxes_plan", boxes, n_boxes, rows, cols, placed, &out_floats)) return -1;
+    if (!j2k_list_check("ebcc_hip_boxes_plan", g, n_frames, placed.data(), placed.size(), out_floats, keep ? flags.data() : nullptr)) return -1;
     if (keep) memcpy(keep, flags.data(), flags.size());
     return g.nblocks;
     EBCC_API_CATCH(-1)

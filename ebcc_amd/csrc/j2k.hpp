@@ -211,52 +211,53 @@ inline J2kStripRange j2k_cone_span(const J2kWindow &w, int r)
 }
 // the levels j2k_first_fused(jb) .. kJ2kRes - 1 take the fused pass (sizes grow with r); kJ2kRes: none does
 int j2k_first_fused(const J2kBuffers &jb);
-// Box-list decode: boxes of one size, each cut from the frame it names (j2k_analysis.hip: launch_j2k_box_levels).  A record of
-// the device table is one box of the current round: the frame its code-blocks were decoded for, the slot of jb.B2 that holds
-// its intermediate low-pass bands, its index in the caller's [n_boxes][rows][cols] array, its origin, and for every fused level
-// the span of its dependency cone (j2k_cone_span; zero for the levels below the first fused one).
+// List decode: placed boxes (include/ebcc_hip.h: ebcc_hip_placed_box), each cut from the frame it names, of its own extent and at
+// its own place in the caller's array (j2k_analysis.hip: launch_j2k_box_levels).  A record of the device table is one box of
+// the current round: the frame its code-blocks were decoded for, the slot of jb.B2 that holds its intermediate low-pass bands,
+// its origin, and for every fused level the span of its dependency cone (j2k_cone_span; zero for the levels below the first
+// fused one).  128 bytes.
 struct J2kBoxEntry {
-    int frame, slot, out, row0, col0;
+    int frame, slot, row0, col0;
     int strip0[kJ2kRes], strips[kJ2kRes], pos0[kJ2kRes], pos1[kJ2kRes];
-    int pad[3];
+    int pad[4];
 };
-// A placed box (include/ebcc_hip.h: ebcc_hip_placed_box): record e of a second table beside the entries - the box's own extent
-// and where it lies in the caller's array, sample (y, x) at out[at + y * pitch + x].  `J2kBoxEntry::out` is not used then.
+// Record e of a second table beside the entries (24 bytes): the box's extent and where it lies in the caller's array, sample
+// (y, x) at out[at + y * pitch + x].
 struct J2kPlacement {
     int rows, cols;
     unsigned long long at, pitch;
 };
-// the boxes of a batch: `h_table` / `table`: pinned and device room for `n` records, the pinned ones filled by j2k_boxes_check
-// but for the slot, which is the launch's.  Boxes of one size rows x cols at index `out` of [n][rows][cols]; or placed boxes
-// (`h_place` / `place` set, behind the entries in the same pinned / device allocation: one copy sends both; filled by
-// j2k_placed_check), of at most rows x cols.
+// the boxes of a batch: `h_table` / `table` and `h_place` / `place`: pinned and device room for `n` records of either table,
+// the placements behind the entries in the same pinned / device allocation (one copy sends both), the pinned ones filled by
+// j2k_list_check but for the slot, which is the launch's.  rows, cols: the largest extents.
 struct J2kBoxList {
     J2kBoxEntry *h_table, *table;
+    J2kPlacement *h_place, *place;
     size_t n;
     int rows, cols;
-    J2kPlacement *h_place = nullptr, *place = nullptr;
 };
 // What a decode launch puts out (launch_j2k_decode), as decode_batch plans it once per batch: whole frames to jb.DEC; the
-// window `cone` of every frame to out [n_frames][rows][cols]; or the boxes of `list`, each from the frame it names, to
-// out [n][rows][cols]; or the placed boxes of `list` (its second table set), each to its own rectangle of out.
+// window `cone` of every frame to out [n_frames][rows][cols]; or the boxes of `list`, each from the frame it names, to its
+// own rectangle of out.
 struct J2kRegion {
-    enum Kind { Frames, Window, Boxes, Placed } kind = Frames;
-    bool lists() const { return kind == Boxes || kind == Placed; }
+    enum Kind { Frames, Window, List } kind = Frames;
     J2kWindow cone{};
     J2kBoxList list{};
     float *out = nullptr;
 };
-// the box list of a box-list entry point against frames of geometry g (include/ebcc_hip.h); false: refused, message set.
-// keep (may be null): [n_frames][g.nblocks], row f the OR of j2k_window_keeps over the boxes of frame f.  table (with keep, may
-// be null): record e is box e - frame, out = e, origin, and the spans of its cone for the levels first_fused and above - so a
-// box's cone is planned once.
-bool j2k_boxes_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
-                     uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, int first_fused = kJ2kRes);
-// the same for the placed boxes of the _placed entry points, each of its own size, against an output of out_floats floats;
-// place (with table): record e is box e's extent and placement.  max_rows / max_cols (may be null): the largest extents.
-bool j2k_placed_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
-                      uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, J2kPlacement *place = nullptr, int first_fused = kJ2kRes,
-                      int *max_rows = nullptr, int *max_cols = nullptr);
+// The list of a list entry point against frames of geometry g and an output of out_floats floats (include/ebcc_hip.h); false:
+// refused, message set, nothing written.  keep (may be null): [n_frames][g.nblocks], row f the OR of j2k_window_keeps over the
+// boxes of frame f.  table and place (with keep, may be null): record e is box e - frame, origin and the spans of its cone for
+// the levels first_fused and above, so a box's cone is planned once; extent and placement.  max_rows / max_cols (may be null):
+// the largest extents.
+bool j2k_list_check(const char *who, const J2kGeom &g, size_t n_frames, const ebcc_hip_placed_box *boxes, size_t n_boxes, size_t out_floats,
+                    uint8_t *keep = nullptr, J2kBoxEntry *table = nullptr, J2kPlacement *place = nullptr, int first_fused = kJ2kRes,
+                    int *max_rows = nullptr, int *max_cols = nullptr);
+// The arguments of a _boxes entry point as the placed list they stand for: box e of rows x cols at index e of a compact
+// [n_boxes][rows][cols] output of *out_floats floats.  false: refused - no list, boxes that are empty or larger than any frame, or a
+// size that overflows - with the message set and before the list is read.
+bool j2k_boxes_as_placed(const char *who, const ebcc_hip_box *boxes, size_t n_boxes, size_t rows, size_t cols,
+                         std::vector<ebcc_hip_placed_box> &placed, size_t *out_floats);
 int j2k_selfcheck_div65535();   // mismatches of the division-free s / 65535.0f of the fused inverse level (0 expected)
 
 // ---- launchers (asynchronous on s) ---------------------------------------------------------------
@@ -291,9 +292,9 @@ void launch_j2k_probe_decode(const float *data, const J2kBuffers &jb, int n_fram
 // `region` other than whole frames (host_table must be given; j2k_window_supported geometries): jb.DEC is not written, and the
 // entries of jb.dec_table outside the window's cone (the cones of a frame's boxes) have been zeroed
 void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const int *host_table = nullptr, const J2kRegion &region = J2kRegion{});
-// the inverse levels of a box list over the tier-1 decoder's output jb.V (j2k_analysis.hip)
+// the inverse levels of a list over the tier-1 decoder's output jb.V (j2k_analysis.hip)
 void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &boxes, float *out, hipStream_t s);
-// after it, for placed boxes: those of constant frames (jb.fs) filled with the frame's value, at their pitch
+// after it: the boxes of constant frames (jb.fs) filled with the frame's value, at their pitch
 void launch_j2k_fill_placed(const J2kBuffers &jb, const J2kBoxList &boxes, float *out, hipStream_t s);
 void plan_decode_lanes(const int *host_table, int total, int out[4]);   // (what launch_j2k_decode chooses; ebcc_hip_plan_decode_lanes)
 

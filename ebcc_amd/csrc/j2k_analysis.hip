@@ -641,7 +641,7 @@ struct J2kWinOut { float *out; int row0, col0, rows, cols; };
 struct J2kStripLane { int frame, slot, lane, i, W, nh, snh, nv; size_t n_pix; int tile; };
 // where a workgroup's tile is: the frame whose coefficients it reads (V, fs, geometry), its vertical piece, and which frame-sized
 // slots of io.ll / io.out hold its low-pass input / its output.  Whole frames and uniform windows: all three are the frame
-// (j2k_tile_of_frame); a box of a box list: the record of its entry (k_j2k_level_box).
+// (j2k_tile_of_frame); a box of a list: the record of its entry (k_j2k_level_box).
 struct J2kStripTile { int frame, piece, ll_at, slot; };
 __device__ __forceinline__ J2kStripTile j2k_tile_of_frame(int n_frames)
 {
@@ -813,19 +813,6 @@ struct J2kSinkWindowTop {
     }
     __device__ void end() {}
 };
-// the top level of one box of a box list: J2kSinkWindowTop with the box's own origin, at index `out_index` of the caller's
-// [n_boxes][rows][cols] array (the 8-byte form is decided per box)
-struct J2kSinkBoxTop : J2kSinkWindowTop {
-    int out_index;
-    __device__ bool begin(const J2kStripLane &l, bool empty)
-    {
-        d = win.out + (size_t) out_index * ((size_t) win.rows * (size_t) win.cols);
-        mn = fs[l.frame].minv; rng = fs[l.frame].maxv - fs[l.frame].minv;
-        wx = 2 * l.i - win.col0;
-        pair_io = (win.col0 & 1) == 0 && (win.cols & 1) == 0 && (l.nh & 1) == 0 && ((size_t) d & 7) == 0;
-        return !empty;
-    }
-};
 // the top level of one placed box (J2kPlacement): the box's own origin and extent (win.out is the box's first sample), rows
 // `pitch` floats apart; the 8-byte form is decided per box from that address, the pitch's parity, col0 and cols
 struct J2kSinkPlacedTop : J2kSinkWindowTop {
@@ -960,31 +947,25 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_win(J2kLevelIO i
     J2kSinkWindowTop sink{win, fs};
     j2k_strip_pass(io, V, geom, fs, nullptr, kJ2kRes - 1, range, j2k_tile_of_frame(n_frames), sink);
 }
-// Level io.r of the boxes of one round of a box list (launch_j2k_box_levels): tile blockIdx.y = piece * n_entries + entry, and
-// the entry's record (uniform loads) says which frame it reads, which strips and positions its cone holds at this level and
-// where its bands live.  The grid is sized for the round's largest strip count and `pieces` is the launch's: an entry with
-// fewer strips leaves at the strip pass's first test, one with fewer positions has empty pieces.  TOP: the field's box to
-// `out`; else the level's samples to the entry's slot of io.out.  ll_by_frame: io.ll is the frames' buffer (the band the
-// separate passes left, shared by every box of the frame), not the entries'.
-template <bool TOP>
+// Level io.r, below the top, of the boxes of one round of a list (launch_j2k_box_levels): tile blockIdx.y = piece * n_entries +
+// entry, and the entry's record (uniform loads) says which frame it reads, which strips and positions its cone holds at this
+// level and where its bands live.  The grid is sized for the round's largest strip count and `pieces` is the launch's: an entry
+// with fewer strips leaves at the strip pass's first test, one with fewer positions has empty pieces.  The level's samples go
+// to the entry's slot of io.out.  ll_by_frame: io.ll is the frames' buffer (the band the separate passes left, shared by every
+// box of the frame), not the entries'.
 __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_box(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
                                                                      const FrameState *fs, const J2kBoxEntry *__restrict__ entries, int n_entries,
-                                                                     int pieces, int ll_by_frame, float *out, int rows, int cols)
+                                                                     int pieces, int ll_by_frame)
 {
     const J2kBoxEntry &e = entries[(int) blockIdx.y % n_entries];
-    const int r = TOP ? kJ2kRes - 1 : io.r;
+    const int r = io.r;
     const J2kStripRange range{e.strip0[r], e.strips[r], e.pos0[r], e.pos1[r], pieces};
     const J2kStripTile tile{e.frame, (int) blockIdx.y / n_entries, ll_by_frame ? e.frame : e.slot, e.slot};
-    if constexpr (TOP) {
-        J2kSinkBoxTop sink{{J2kWinOut{out, e.row0, e.col0, rows, cols}, fs}, e.out};
-        j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
-    } else {
-        J2kSinkNextLevel sink{io};
-        j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
-    }
+    J2kSinkNextLevel sink{io};
+    j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
 }
-// The top level of the placed boxes of one round: k_j2k_level_box<true> with the box's extent and placement from record e of
-// the second table (the levels below are k_j2k_level_box<false> over the entries, as for boxes of one size).
+// The top level of the boxes of one round: the same tiles, with the box's extent and placement from record e of the second
+// table; the field's box goes to its rectangle of `out`.
 __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_placed(J2kLevelIO io, const int32_t *__restrict__ V, const J2kGeom *geom,
                                                                         const FrameState *fs, const J2kBoxEntry *__restrict__ entries,
                                                                         const J2kPlacement *__restrict__ places, int n_entries, int pieces,
@@ -999,7 +980,7 @@ __global__ __launch_bounds__(64 * kL5MaxWaves) void k_j2k_level_placed(J2kLevelI
     J2kSinkPlacedTop sink{{J2kWinOut{out + p.at, e.row0, e.col0, p.rows, p.cols}, fs}, (size_t) p.pitch};
     j2k_strip_pass(io, V, geom, fs, nullptr, r, range, tile, sink);
 }
-// placed boxes of constant frames (the strip pass leaves them alone): the rectangle filled with the frame's value;
+// the boxes of constant frames (the strip pass leaves them alone): the rectangle filled with the frame's value;
 // workgroups (row group, entry)
 __global__ __launch_bounds__(256) void k_fill_placed(const FrameState *fs, const J2kBoxEntry *__restrict__ entries,
                                                       const J2kPlacement *__restrict__ places, float *out)
@@ -2011,13 +1992,13 @@ int j2k_inverse_dwt(float *B, const int32_t *V, const float *data, const J2kBuff
     return partials;
 }
 
-// Box-list decode (J2kBoxList): after the tier-1 decode of the batch, the fused levels of every box.  Levels below the first
+// List decode (J2kBoxList): after the tier-1 decode of the batch, the fused levels of every box.  Levels below the first
 // fused one run whole, once, in jb.B (every box of a frame, in every round, reads that band: nothing here writes jb.B).  An
 // entry keeps the outputs of its fused levels below the top in its slot of jb.B2, each level in a region of its own (rows of
 // even pitch at frame coordinates; together under half a frame), so two boxes of one frame never share a band.  More boxes
 // than slots run as rounds of jb.max_frames entries: five launches a round, on one stream, so a slot is reused only after the
 // round before has read it - what an earlier entry left outside the new cone is read and dropped like any position outside
-// a cone.  The records of all rounds (j2k_boxes_check) get their slots here and are sent as one copy.
+// a cone.  The records of all rounds (j2k_list_check) get their slots here and are sent, both tables, as one copy.
 void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList &bl, float *out, hipStream_t s)
 {
     const J2kGeom &g = jb.geom;
@@ -2040,8 +2021,8 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
     if (used > n_pix) throw std::runtime_error("box decode: the level bands of a box do not fit its slot");
     const size_t cap = (size_t) jb.max_frames;
     for (size_t e = 0; e < bl.n; e++) bl.h_table[e].slot = (int) (e % cap);
-    // (placed boxes: the second table lies behind the entries on both sides)
-    EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * (sizeof(J2kBoxEntry) + (bl.place ? sizeof(J2kPlacement) : 0)), hipMemcpyHostToDevice, s));
+    // (the second table lies behind the entries on both sides)
+    EBCC_HIP_CHECK(hipMemcpyAsync(bl.table, bl.h_table, bl.n * (sizeof(J2kBoxEntry) + sizeof(J2kPlacement)), hipMemcpyHostToDevice, s));
     for (size_t lo = 0; lo < bl.n; lo += cap) {
         const int n = (int) std::min(cap, bl.n - lo);
         for (int r = first_fused; r < kJ2kRes; r++) {
@@ -2055,15 +2036,14 @@ void launch_j2k_box_levels(const J2kBuffers &jb, int n_frames, const J2kBoxList 
             const bool from_frames = r == first_fused;                       // (its low-pass input: V, or the band in jb.B)
             J2kLevelIO io{from_frames ? (r > 1 ? jb.B : nullptr) : jb.B2 + off[r - 1], from_frames ? g.W : pitch[r - 1], n_pix,
                           top ? nullptr : jb.B2 + off[r], top ? g.W : pitch[r], n_pix, r};
-            if (top && bl.place) hipLaunchKernelGGL(k_j2k_level_placed, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, bl.place + lo, n, lg.pieces, from_frames ? 1 : 0, out);
-            else if (top) hipLaunchKernelGGL(k_j2k_level_box<true>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
-            else hipLaunchKernelGGL(k_j2k_level_box<false>, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0, out, bl.rows, bl.cols);
+            if (top) hipLaunchKernelGGL(k_j2k_level_placed, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, bl.place + lo, n, lg.pieces, from_frames ? 1 : 0, out);
+            else hipLaunchKernelGGL(k_j2k_level_box, lg.grid, lg.block, 0, s, io, V, jb.d_geom, fs, bl.table + lo, n, lg.pieces, from_frames ? 1 : 0);
         }
     }
     EBCC_HIP_LAUNCH_CHECK();
 }
 
-// after launch_j2k_box_levels (which sent the tables), for a list of placed boxes that names constant frames: their fill
+// after launch_j2k_box_levels (which sent the tables), for a list that names constant frames: their fill
 void launch_j2k_fill_placed(const J2kBuffers &jb, const J2kBoxList &bl, float *out, hipStream_t s)
 {
     for (size_t lo = 0; lo < bl.n; lo += 65535) {

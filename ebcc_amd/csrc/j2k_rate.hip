@@ -1821,7 +1821,7 @@ void launch_j2k_decode(const J2kBuffers &jb, int n_frames, hipStream_t s, const 
                            jb.stream_cap, jb.dec_table, jb.dec_order, jb.V, jb.d_geom, jb.d_blocks, jb.fs, live, tiers);
     }
     timing_end("t1_decode", s);
-    if (region.lists()) launch_j2k_box_levels(jb, n_frames, region.list, region.out, s);
+    if (region.kind == J2kRegion::List) launch_j2k_box_levels(jb, n_frames, region.list, region.out, s);
     else decode_tail(nullptr, jb, n_frames, nullptr, false, s, 1, part ? &region.cone : nullptr, region.out);
     EBCC_HIP_LAUNCH_CHECK();
 }

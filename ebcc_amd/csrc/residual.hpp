@@ -134,12 +134,9 @@ void launch_synthesis_head(const ResidualBuffers &rb, int n_frames, const int *d
 void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_frames, const int *d_active, hipStream_t s, int row0, int col0,
                                int rows, int cols);
 
-// the same for the boxes of a box list (j2k.hpp: J2kBoxEntry - frame, output index and origin are the record's):
-// out [n_boxes][rows][cols]; boxes of frames without a residual layer are left as they are
+// the same for the boxes of a list (j2k.hpp: frame and origin are J2kBoxEntry's, extent, first sample and pitch J2kPlacement's);
+// max_rows: the tallest; boxes of frames without a residual layer are left as they are
 struct J2kBoxEntry;
-void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, size_t n_boxes, const int *d_active,
-                                     hipStream_t s, int rows, int cols);
-// and for placed boxes (j2k.hpp: J2kPlacement - extent, first sample and pitch are the second table's); max_rows: the tallest
 struct J2kPlacement;
 void launch_synthesis_tail_add_placed(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, const J2kPlacement *d_places, size_t n_boxes,
                                       const int *d_active, hipStream_t s, int max_rows);

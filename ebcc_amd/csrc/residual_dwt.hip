@@ -277,17 +277,8 @@ __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add(const float *__res
     rows_inv_add_body(src, stride, frame_stride, n, active, fs, out, blockIdx.y, blockIdx.y, row0, col0, rows, cols);
 }
 
-// the boxes of a box list: workgroups (x, e) take frame and origin from record e and add to box out[e.out]
-__global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_box(const float *__restrict__ src, int stride, size_t frame_stride, int n,
-                                                                   const int *active, const FrameState *fs, float *out,
-                                                                   const J2kBoxEntry *__restrict__ boxes, int rows, int cols)
-{
-    const J2kBoxEntry &e = boxes[blockIdx.y];
-    rows_inv_add_body(src, stride, frame_stride, n, active, fs, out, e.frame, e.out, e.row0, e.col0, rows, cols);
-}
-
-// placed boxes: extent, first sample and pitch from record e of the second table; the grid's x is sized for the tallest box,
-// and a workgroup beyond a smaller one's rows finds nothing to do
+// the boxes of a list: workgroups (x, e) take frame and origin from record e, extent, first sample and pitch from record e of
+// the second table; the grid's x is sized for the tallest box, and a workgroup beyond a smaller one's rows finds nothing to do
 __global__ __launch_bounds__(kRowThreads) void k_rows_inv_add_placed(const float *__restrict__ src, int stride, size_t frame_stride, int n,
                                                                       const int *active, const FrameState *fs, float *out,
                                                                       const J2kBoxEntry *__restrict__ boxes, const J2kPlacement *__restrict__ places)
@@ -1360,22 +1351,9 @@ void launch_synthesis_tail_add(float *out, const ResidualBuffers &rb, int n_fram
     EBCC_HIP_LAUNCH_CHECK();
 }
 
-// (one workgroup row per box and at most 65535 boxes a launch.  Two records may name the same output samples only if they are
-//  the same box of the same frame - the caller's indices are all different - so no two workgroups add to one sample.)
-void launch_synthesis_tail_add_boxes(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, size_t n_boxes, const int *d_active,
-                                     hipStream_t s, int rows, int cols)
-{
-    const Grid &g = rb.g;
-    for (size_t lo = 0; lo < n_boxes; lo += 65535) {
-        const unsigned n = (unsigned) std::min<size_t>(65535, n_boxes - lo);
-        hipLaunchKernelGGL(k_rows_inv_add_box, dim3(min(rows, 96), n), dim3(kRowThreads), (size_t) g.nx * sizeof(float), s, rb.T, g.nx, rb.np, g.nx,
-                           d_active, rb.fs, out, d_boxes + lo, rows, cols);
-    }
-    EBCC_HIP_LAUNCH_CHECK();
-}
-
-// the same for placed boxes (J2kPlacement), the tallest of `max_rows` rows.  (Overlapping target rectangles are the caller's
-// business: two workgroups may then add to one sample, and which box wins is unspecified.)
+// the same for the boxes of a list (J2kBoxEntry, J2kPlacement), the tallest of `max_rows` rows: one workgroup row per box and at
+// most 65535 boxes a launch.  (Overlapping target rectangles are the caller's business: two workgroups may then add to one
+// sample, and which box wins is unspecified.)
 void launch_synthesis_tail_add_placed(float *out, const ResidualBuffers &rb, const J2kBoxEntry *d_boxes, const J2kPlacement *d_places, size_t n_boxes,
                                       const int *d_active, hipStream_t s, int max_rows)
 {

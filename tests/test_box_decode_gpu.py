@@ -22,6 +22,7 @@ STREAMS = T.STREAMS
 SENTINEL, PAD_FRONT, PAD_BACK = T.SENTINEL, T.PAD_FRONT, T.PAD_BACK
 same_bits, sha = T.same_bits, T.sha
 ENTRIES = ("ebcc_hip_decode_frames_boxes", "ebcc_hip_decode_shard_boxes")
+PLACED = ("ebcc_hip_decode_shard_placed", "ebcc_hip_decode_host_frames_placed")
 
 
 def lib():
@@ -31,6 +32,10 @@ def lib():
     for name in ENTRIES + ("ebcc_hip_decode_host_frames_boxes",):
         fn = getattr(p, name)
         fn.argtypes, fn.restype = sig, ctypes.c_int
+    for name in PLACED:
+        fn = getattr(p, name)
+        fn.argtypes = [ctypes.c_void_p, L.c_void_pp, L.c_size_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
     return p
 
 
@@ -423,3 +428,141 @@ def test_read_boxes_and_points(tmp_path):
     r = subprocess.run([T.CONDA_PY, os.path.join(L.ROOT, "tests", "h5_box_read.py"), str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("OK") == 3, r.stdout
+
+
+# ---- 11. a box list is the placed list of a compact array: shard and host forms of both, three batches ----------------------
+SEVEN_CONST, SEVEN_BASE_ONLY = 4, 1
+FOUR_FORMS = (ENTRIES[1], "ebcc_hip_decode_host_frames_boxes") + PLACED
+GUARD = np.uint32(0xA5A5A5A5)
+_seven = []
+
+
+def seven_of_100x130():
+    """7 frames of 100 x 130 coded by the product - frame 4 a constant field, frame 1 without a residual layer, the others with
+    one: era5_like seeds that keep theirs at base_cr 5, MAX_ERROR 0.01 under a loose base layer - and what
+    ebcc_hip_decode_frames gives for them on a context of capacity 3: (streams, full), made once"""
+    if not _seven:
+        h, w, n = 100, 130, 7
+        frames = np.stack([L.era5_like(h, w, s) for s in (9, 13, 14, 15, 0, 16, 13)])
+        frames[SEVEN_CONST] = np.float32(281.5)
+        before = os.environ.get("EBCC_INIT_BASE_ERROR_QUANTILE")
+        os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"] = "0.1"
+        try:
+            with L.Context(n, h, w) as ctx:
+                streams = ctx.encode_frames(frames, L.make_config((1, h, w), base_cr=5.0, error=0.01, residual_type=L.MAX_ERROR))
+                streams[SEVEN_BASE_ONLY] = ctx.encode_frames(frames[SEVEN_BASE_ONLY:SEVEN_BASE_ONLY + 1],
+                                                             L.make_config((1, h, w), base_cr=10.0, error=0.0, residual_type=L.NONE))[0]
+        finally:
+            if before is None:
+                del os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"]
+            else:
+                os.environ["EBCC_INIT_BASE_ERROR_QUANTILE"] = before
+        for f, st in enumerate(streams):
+            flags, coeffs, zsize = st[5], struct.unpack("<Q", st[16:24])[0], struct.unpack("<Q", st[32:40])[0]
+            assert st[:4] == b"EBCC" and bool(flags & 1) == (f == SEVEN_CONST), f
+            assert (coeffs > 0 and zsize > 0) == (f not in (SEVEN_CONST, SEVEN_BASE_ONLY)), (f, coeffs, zsize)     # a residual layer
+        with L.Context(3, h, w) as ctx:
+            full = np.concatenate([ctx.decode_frames(streams[lo:lo + 3]) for lo in range(0, n, 3)])
+        assert (full[SEVEN_CONST] == np.float32(281.5)).all()
+        full.setflags(write=False)
+        _seven.append((streams, full))
+    return _seven[0]
+
+
+def guarded(ctx, streams, form, boxes, rows, cols, front, n_frames=None):
+    """the box list through a _boxes form, or the equal placed list - box e of rows x cols at offset e * rows * cols, pitch cols -
+    through a _placed form, into k * rows * cols floats that begin `front` floats behind an 8-byte aligned address, between
+    guard words, on the device or (host forms) in host memory -> (return value, the output's words as uint32); asserts that
+    the guards are intact, and after a non-zero return the whole array"""
+    n = len(streams) if n_frames is None else n_frames
+    keep, ptrs, sizes = _args(streams)
+    k, count = len(boxes), len(boxes) * rows * cols
+    words = np.full(front + count + PAD_BACK, GUARD, np.uint32)
+    fn = getattr(lib(), form)
+    if form in PLACED:
+        table = np.array([(f, r0, c0, rows, cols, e * rows * cols, cols) for e, (f, r0, c0) in enumerate(boxes)], np.uint64)   # == ebcc_hip_placed_box[]
+        call = lambda out: fn(ctx.ptr, ptrs, sizes, n, table.ctypes.data, k, out, count)
+    else:
+        table = _table(boxes)
+        call = lambda out: fn(ctx.ptr, ptrs, sizes, n, table.ctypes.data, k, rows, cols, out)
+    if "host" in form:
+        assert words.ctypes.data % 8 == 0
+        rc, back = call(words.ctypes.data + 4 * front), words
+    else:
+        d = L.DeviceArray(words)
+        assert d.ptr % 8 == 0
+        rc = call(d.ptr + 4 * front)
+        back = d.get(np.uint32, words.shape)
+        d.free()
+    assert (back[:front] == GUARD).all() and (back[front + count:] == GUARD).all(), ("written outside the output", form)
+    if rc:
+        assert (back == GUARD).all(), ("written by a call that failed", form)
+    return rc, back[front:front + count].copy()
+
+
+def four_forms(ctx, streams, full, boxes, rows, cols, front, what):
+    """all four forms give the crops, bit for bit -> the output [k][rows][cols]"""
+    want = np.ascontiguousarray(crops(full, boxes, rows, cols)).view(np.uint32).ravel()
+    for form in FOUR_FORMS:
+        rc, got = guarded(ctx, streams, form, boxes, rows, cols, front)
+        assert rc == 0, (what, form, L.product().ebcc_hip_last_error())
+        assert np.array_equal(got, want), (what, form, rows, cols, int((got != want).sum()))
+    return want.view(np.float32).reshape(len(boxes), rows, cols)
+
+
+@pytest.mark.parametrize("rows,cols,front", [(5, 7, 1), (6, 8, 2)], ids=["5x7-unaligned", "6x8-pairs"])
+def test_boxes_equal_their_placed_list(rows, cols, front):
+    """four boxes a frame - a repeat among them, odd and even first columns, the last rows and columns - of every frame, the
+    constant one included: twelve boxes a batch through three slots.  5 x 7: 35 floats a box, so the first samples alternate
+    between 8-byte aligned and not; 6 x 8 in an 8-byte aligned output: the pair stores"""
+    h, w = 100, 130
+    streams, full = seven_of_100x130()
+    boxes = [b for f in range(7) for b in ((f, (7 * f) % (h - rows), (11 * f) % (w - cols)), (f, 40, 60), (f, 40, 60), (f, h - rows, w - cols))]
+    with L.Context(3, h, w) as ctx:
+        four_forms(ctx, streams, full, boxes, rows, cols, front, "equality")
+
+
+def test_constant_frames_across_rounds_and_batches():
+    """the constant frame's boxes in the second round of the second batch (every frame named, four boxes on the frame before
+    it), in the second round of the first batch (frames 2 .. 6 named) and on both sides of a round boundary"""
+    h, w, rows, cols, c = 100, 130, 9, 11, SEVEN_CONST
+    streams, full = seven_of_100x130()
+    spread = lambda f, k: [(f, (13 * f + 29 * j) % (h - rows), (17 * f + 31 * j) % (w - cols)) for j in range(k)]
+    lists = {"second batch, second round": [b for f in range(7) for b in spread(f, 4 if f == c - 1 else 2)],
+             "first batch, second round": [b for f in range(2, 7) for b in spread(f, 2)],
+             "across a round boundary": [b for f in range(7) for b in spread(f, 4 if f == c else 1)]}
+    with L.Context(3, h, w) as ctx:
+        for what, boxes in lists.items():
+            got = four_forms(ctx, streams, full, boxes, rows, cols, 1, what)
+            const = np.array([f == c for f, _, _ in boxes])
+            assert const.sum() >= 2 and (got[const] == np.float32(281.5)).all(), what
+            assert not (got[~const] == np.float32(281.5)).any(), what
+
+
+def test_host_form_writes_nothing_else():
+    h, w = 100, 130
+    streams, full = seven_of_100x130()
+    boxes = [(f, 10 * f, 15 * f) for f in range(7)]
+    with L.Context(3, h, w) as ctx:
+        for form in ("ebcc_hip_decode_host_frames_boxes", PLACED[1]):
+            rc, got = guarded(ctx, streams, form, boxes, 20, 30, 3)                  # (guarded: the guards before and behind)
+            assert rc == 0 and np.array_equal(got, np.ascontiguousarray(crops(full, boxes, 20, 30)).view(np.uint32).ravel()), form
+            rc, _ = guarded(ctx, streams, form, boxes[:6] + [(7, 0, 0)], 20, 30, 3)      # (guarded: the whole array)
+            assert rc == 1 and L.product().ebcc_hip_last_error(), form
+
+
+def test_size_overflow_is_refused_before_the_list_is_read():
+    """n_boxes * rows * cols beyond SIZE_MAX: the list pointer holds one box, and the call must not get as far as the second"""
+    streams, _ = seven_of_100x130()
+    keep, ptrs, sizes = _args(streams)
+    table = np.zeros((1, 3), np.uint64)
+    words = np.full(64, GUARD, np.uint32)
+    with L.Context(3, 100, 130) as ctx:
+        for n_boxes, rows, cols in [(1 << 62, 2, 2), (3, 1 << 32, 1 << 32), (1 << 40, 1 << 12, 1 << 12), ((1 << 64) - 1, (1 << 64) - 1, (1 << 64) - 1)]:
+            for form in ENTRIES[1:] + ("ebcc_hip_decode_host_frames_boxes",):
+                d = L.DeviceArray(words)
+                out = words.ctypes.data if "host" in form else d.ptr
+                assert getattr(lib(), form)(ctx.ptr, ptrs, sizes, 7, table.ctypes.data, n_boxes, rows, cols, out) == 1, (form, n_boxes, rows, cols)
+                assert L.product().ebcc_hip_last_error(), (form, n_boxes, rows, cols)
+                assert (words == GUARD).all() and (d.get(np.uint32, words.shape) == GUARD).all(), form
+                d.free()

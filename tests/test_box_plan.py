@@ -112,3 +112,12 @@ def test_refusals(h, w):
     table = np.zeros((1, 3), np.uint64)
     keep = np.full(4, 0x5A, np.uint8)
     assert _fn()(h, w, 1, table.ctypes.data, 1, 1, 1, keep.ctypes.data, 4) == -1 and (keep == 0x5A).all()
+
+
+def test_size_overflow_is_refused_before_the_list_is_read():
+    """n_boxes * rows * cols beyond SIZE_MAX: the list pointer holds one box, and the call must not get as far as the second"""
+    table = np.zeros((1, 3), np.uint64)
+    keep = np.full(4, 0x5A, np.uint8)
+    for n_boxes, rows, cols in [(1 << 62, 2, 2), (3, 1 << 32, 1 << 32), (1 << 40, 1 << 12, 1 << 12), ((1 << 64) - 1,) * 3]:
+        assert _fn()(100, 130, 4, table.ctypes.data, n_boxes, rows, cols, keep.ctypes.data, 4) == -1, (n_boxes, rows, cols)
+        assert L.product().ebcc_hip_last_error() and (keep == 0x5A).all(), (n_boxes, rows, cols)
