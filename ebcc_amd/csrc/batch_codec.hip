@@ -19,7 +19,9 @@ DevRateSearch rate_search_start(float cr0, double q_init, double q_target)
 }
 
 struct Job {                     // host-side state of one frame being encoded
+    FrameConfig fc;              // its rate, mode and bound
     bool const_field = false;
+    bool search = false;         // it runs the searches and the residual layer: an error-bounded mode, not constant
     float minv = 0, maxv = 0, target = -1, cr = -1;
     double mean_err = 0, q = 0, q_first = 0;
     float rmin = 0, rmax = 0;
@@ -107,13 +109,6 @@ struct Batch {
         push_jf();
         push_active();
         launch_j2k_rate(jb, (int) nt, d_active, s);
-    }
-    // one probe of the base layer for the active chunks: the allocation (+ decode and statistics)
-    void probe(bool decode)
-    {
-        allocate();
-        if (decode) launch_j2k_probe_decode(d_frames, jb, (int) nt, d_active, s);
-        fetch_jf();
     }
     // codestream of the current layer assignment of the active chunks -> jobs[c].tail
     template <class Jobs>
@@ -290,13 +285,17 @@ struct Entropy {
 // One call of encode_batch: the batch, the jobs of its chunks and what every phase reads.  The phases are the steps of
 // the reference's ebcc_encode in its order, each headed by the lines it restates; their host synchronisations, uploads
 // and launches are the slice schedule the codec was measured with.
+// Rate, mode and bound are per chunk (Job::fc: a batch of frame groups mixes them; the environment switches stay
+// process-wide).  A phase runs when a chunk needs it, and a chunk that does not need it is inactive in it the way a constant
+// chunk is (active[f] = 0, rs[k].phase = 6): a chunk in mode NONE takes the first probe's allocation without its decode and
+// hands its codestream over there, one with a stale mode value does so behind the decode (quirk Q2), and everything from
+// search #1 on - the residual range, both searches, the residual layer, the truncation search, the entropy stage and the
+// :838 comparison - sees the searching chunks (Job::search) alone.  With one config for all chunks these are the masks and
+// the launches of the uniform encoder.
 struct BatchEncode {
     struct Gate { SliceGate *g; void release() { if (g) { g->release(); g = nullptr; } } ~Gate() { release(); } } next;   // (error paths too)
     struct NoteOnce { PhaseNote *n; void tell() { if (n) { n->slice_done(); n = nullptr; } } ~NoteOnce() { tell(); } } gpu_phase_over;   // (every path reports once)
     const EncodeEnv env;
-    const codec_config_t *cfg;
-    const int mode;
-    const bool searching;
     const double q_target;
     const bool want_pure;                                           // the pure base-layer fallback runs (:738)
     const size_t n, n_pix;                                          // chunks, pixels of a chunk
@@ -305,18 +304,21 @@ struct BatchEncode {
     const bool overlap2;                                            // search #2 beside the residual layer (queue_search_2)
     std::vector<Job> jobs;
     PhaseTimer pt;
+    bool any_search = false;                                        // a chunk runs the searches (Job::search): the phases behind the first probe run
     bool any_resid = false;                                         // a chunk needs the residual layer
     bool search2_queued = false;                                    // rounds of search #2 are in flight on the second stream
 
-    BatchEncode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_, const codec_config_t *cfg_, SliceGate *next_, size_t tiles,
+    BatchEncode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_, const FrameConfig *fc, SliceGate *next_, size_t tiles,
                 ebcc_hip_ctx *rctx, unsigned slices_, PhaseNote *note)
-        : next{next_}, gpu_phase_over{note}, cfg(cfg_), mode((int) cfg_->residual_compression_type),
-          searching(mode == MAX_ERROR || mode == RELATIVE_ERROR), q_target(1 - env.base_error_quantile),
+        : next{next_}, gpu_phase_over{note}, q_target(1 - env.base_error_quantile),
           want_pure(q_target != 1.0 && !env.no_fallback), n(n_), n_pix(ctx->n_pix * tiles), slices(slices_),
-          b(ctx, d_frames, n_, tiles, rctx), overlap2(want_pure && tiles == 1 && b.rc == ctx), jobs(n_) {}
+          b(ctx, d_frames, n_, tiles, rctx), overlap2(want_pure && tiles == 1 && b.rc == ctx), jobs(n_)
+    { for (size_t f = 0; f < n; f++) jobs[f].fc = fc[f]; }
     // an error return between the two halves of search #2 must not leave its rounds in flight
     ~BatchEncode() { if (search2_queued && b.ctx->stream2) hipStreamSynchronize(b.ctx->stream2); }
 
+    // the mask of a phase: the chunks `in` names, every other chunk inactive in it
+    template <class In> void mask(In in) { for (size_t f = 0; f < n; f++) b.active[f] = in(jobs[f]) ? 1 : 0; }
     // the phases, in the reference's order
     int analyse(); void first_probe(); void search_1(); void queue_search_2(); bool residual_layer(); void truncation_search();
     bool entropy_and_fallback(); int assemble(uint8_t **outs, size_t *sizes);
@@ -345,7 +347,7 @@ void BatchEncode::rate_search(int k, int lane, int part)
     // probes that only steer the search stop counting once they are certainly infeasible (search.hpp); EBCC_HIP_NO_SHORTCUTS=1
     // and TRACE logging (which prints every probe's count) keep every probe exact
     double jobs_qt0 = 0.0;                                               // the error-bounded search's quantile target (0: it never ran)
-    for (size_t f = 0; f < n; f++) if (!jobs[f].const_field) { jobs_qt0 = jobs[f].rs[0].qt; break; }
+    for (size_t f = 0; f < n; f++) if (jobs[f].search) { jobs_qt0 = jobs[f].rs[0].qt; break; }
     const double limit_qt = getenv("EBCC_HIP_NO_SHORTCUTS") || g_log_level <= 0 ? 0.0 : std::min(jobs_qt0, 1.0);
     auto advance = [&]() {
         launch_search_advance(d, jb.jf, d_active, (int) n, (int) b.tiles, k, (double) n_pix, d_counter, s,
@@ -378,7 +380,7 @@ void BatchEncode::rate_search(int k, int lane, int part)
             c.n_probes = (int) std::min<size_t>(j.probes.size(), kMaxProbes);
             std::copy_n(j.probes.begin(), c.n_probes, c.probes);
             c.rs[k] = j.rs[k];
-            if (j.const_field) c.rs[k].phase = 6;
+            if (!j.search) c.rs[k].phase = 6;                                  // (constant, or a mode without searches: never active)
         }
         EBCC_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevChunk) * n, hipMemcpyHostToDevice, s));
         EBCC_HIP_CHECK(hipMemsetAsync(d_counter, 0, sizeof(int) * 4, s));
@@ -422,7 +424,7 @@ void BatchEncode::rate_search(int k, int lane, int part)
     if (getenv("EBCC_HIP_T1_STATS") && slices <= 1) j2k_probe_hist_dump(k == 0 ? "search #1" : "search #2");
     for (size_t f = 0; f < n; f++) {
         Job &j = jobs[f];
-        if (j.const_field) continue;
+        if (!j.search) continue;
         const DevChunk &c = h[f];
         j.rs[k] = c.rs[k];
         if (k == 0) j.q = c.q;
@@ -462,7 +464,7 @@ int BatchEncode::analyse()
         const FrameState &t0 = ctx->h_fs[f * tiles];                   // (all tiles of a chunk carry the chunk's statistics)
         if (t0.has_nonfinite) { log_fatal("NaN or Inf found in data of frame %zu", f); return 2; }
         if (b.jf[f].overflow) { log_fatal("code-block byte slot overflow in frame %zu", f); return 1; }
-        if (searching && !t0.const_field && !std::isfinite(t0.maxv - t0.minv)) {
+        if (jobs[f].fc.searching() && !t0.const_field && !std::isfinite(t0.maxv - t0.minv)) {
             // max - min overflows: the decoded base layer is (s / 65535) * inf + min (:1130), every residual is NaN or
             // infinite, and the reference stops on assert(dc0 >= 0 && dc0 <= MAXELEM) in spiht_encode (spiht_re.c:462)
             log_fatal("range of frame %zu overflows float (max - min = inf)", f);
@@ -472,7 +474,9 @@ int BatchEncode::analyse()
         jobs[f].const_field = t0.const_field != 0;
         jobs[f].minv = t0.minv;
         jobs[f].maxv = t0.maxv;
-        b.jf[f].cr = cfg->base_cr;
+        jobs[f].search = !jobs[f].const_field && jobs[f].fc.searching();
+        any_search |= jobs[f].search;
+        b.jf[f].cr = jobs[f].fc.base_cr;
         b.jf[f].target = 0;
         b.active[f] = jobs[f].const_field ? 0 : 1;
     }
@@ -492,34 +496,44 @@ int BatchEncode::analyse()
 void BatchEncode::first_probe()
 {
     ebcc_hip_ctx *rc = b.rc;
-    const bool need_decode = mode != NONE;
-    if (need_decode)
+    // the chunks whose first encode is decoded: every mode but NONE.  A chunk in mode NONE takes the allocation alone.
+    auto decoded = [](const Job &j) { return !j.const_field && j.fc.mode != NONE; };
+    const bool any_none = std::any_of(jobs.begin(), jobs.end(), [](const Job &j) { return !j.const_field && j.fc.mode == NONE; });
+    const bool need_decode = std::any_of(jobs.begin(), jobs.end(), [](const Job &j) { return j.fc.mode != NONE; });
+    for (size_t f = 0; f < n; f++) {
+        if (jobs[f].fc.mode == NONE) continue;
+        float target = jobs[f].fc.error;                                                      // :723-726
+        if (jobs[f].fc.mode == RELATIVE_ERROR) target *= jobs[f].maxv - jobs[f].minv;
+        jobs[f].target = target;
+        b.jf[f].target = target;
+    }
+    b.allocate();
+    if (need_decode) {
+        // (the allocation's mask is still on its way out of the pinned mirror: it must have left before the mirror changes)
+        if (any_none) { wait_stream(b.s); mask(decoded); b.push_active(); }
+        launch_j2k_probe_decode(b.d_frames, b.jb, (int) b.nt, b.d_active, b.s);
+    }
+    b.fetch_jf();
+    if (need_decode) {
         for (size_t f = 0; f < n; f++) {
-            float target = cfg->error;                                                        // :723-726
-            if (mode == RELATIVE_ERROR) target *= jobs[f].maxv - jobs[f].minv;
-            jobs[f].target = target;
-            b.jf[f].target = target;
-        }
-    b.probe(need_decode);
-    if (mode == NONE) {
-        b.collect_tails(jobs);
-    } else {
-        for (size_t f = 0; f < n; f++) {
-            if (jobs[f].const_field) continue;
+            if (!decoded(jobs[f])) continue;
             jobs[f].mean_err = b.jf[f].err_sum / (double) n_pix;                              // :709
             jobs[f].q = jobs[f].q_first = 1. - ((double) b.jf[f].nbad / (double) n_pix);
-            jobs[f].cr = cfg->base_cr;
+            jobs[f].cr = jobs[f].fc.base_cr;
             jobs[f].probes.push_back(DevProbe{b.jf[f].cr, b.jf[f].stream_bytes, b.jf[f].nbad, b.jf[f].err_sum, 1, 0});
             b.state_cr[f] = b.jf[f].cr;
         }
         // residual range of the first decode: only the header fields survive when no search runs (:716)
         launch_residual_minmax(b.d_frames, b.jb.DEC, (int) n, n_pix, rc->rb.fs, b.rs);
         fetch_frame_states(rc, n);
-        for (size_t f = 0; f < n; f++) { jobs[f].rmin = rc->h_fs[f].rmin; jobs[f].rmax = rc->h_fs[f].rmax; }
-        if (!searching) {                       // stale enum values fall through to a base-only stream (quirk Q2)
-            for (size_t f = 0; f < n; f++) b.active[f] = jobs[f].const_field ? 0 : 1;
-            b.collect_tails(jobs);
-        }
+        for (size_t f = 0; f < n; f++)
+            if (jobs[f].fc.mode != NONE) { jobs[f].rmin = rc->h_fs[f].rmin; jobs[f].rmax = rc->h_fs[f].rmax; }
+    }
+    // the chunks that are done with this encode: mode NONE, and stale enum values, which fall through to a base-only
+    // stream behind their decode (quirk Q2)
+    if (std::any_of(jobs.begin(), jobs.end(), [](const Job &j) { return !j.const_field && !j.search; })) {
+        mask([](const Job &j) { return !j.const_field && !j.search; });
+        b.collect_tails(jobs);
     }
     pt.mark("first probe");
 }
@@ -528,11 +542,11 @@ void BatchEncode::first_probe()
 void BatchEncode::search_1()
 {
     for (size_t f = 0; f < n; f++)
-        if (!jobs[f].const_field) jobs[f].rs[0] = rate_search_start(cfg->base_cr, jobs[f].q, q_target);
+        if (jobs[f].search) jobs[f].rs[0] = rate_search_start(jobs[f].fc.base_cr, jobs[f].q, q_target);
     rate_search(0);
     for (size_t f = 0; f < n; f++) {
-        b.active[f] = jobs[f].const_field ? 0 : 1;
-        if (!jobs[f].const_field) { jobs[f].cr = jobs[f].rs[0].result; jobs[f].len1 = (size_t) jobs[f].rs[0].last.stream_bytes; }
+        b.active[f] = jobs[f].search ? 1 : 0;
+        if (jobs[f].search) { jobs[f].cr = jobs[f].rs[0].result; jobs[f].len1 = (size_t) jobs[f].rs[0].last.stream_bytes; }
     }
     pt.mark("rate search 1");
     // base layer of search #1.  (Sending the codestreams off without waiting for them - written and packed on the second
@@ -546,7 +560,7 @@ void BatchEncode::search_1()
 void BatchEncode::start_search_2()
 {
     for (Job &j : jobs)
-        if (!j.const_field) j.rs[1] = env.no_consistency ? rate_search_start(j.cr, j.q, 1.0) : rate_search_start(cfg->base_cr, j.q_first, 1.0);
+        if (j.search) j.rs[1] = env.no_consistency ? rate_search_start(j.cr, j.q, 1.0) : rate_search_start(j.fc.base_cr, j.q_first, 1.0);
 }
 
 // ---- the pure base-layer search (:819-836) depends on nothing the residual layer produces: for one-frame chunks its rounds
@@ -574,7 +588,7 @@ bool BatchEncode::residual_layer()
     for (size_t f = 0; f < n; f++) {
         Job &j = jobs[f];
         b.active[f] = 0;
-        if (j.const_field) continue;
+        if (!j.search) continue;
         j.rmin = rc->h_fs[f].rmin; j.rmax = rc->h_fs[f].rmax;
         float cur = fmaxf(fabsf(j.rmin), fabsf(j.rmax));                                  // :735
         j.skip = cur <= j.target;                                                         // :737
@@ -684,7 +698,7 @@ void BatchEncode::truncation_search()
         }
     }
     for (Job &j : jobs) {
-        if (j.const_field || j.skip) j.coeffs_size = j.need_pure ? j.coeffs_orig : 0;
+        if (!j.search || j.skip) j.coeffs_size = j.need_pure ? j.coeffs_orig : 0;
         else j.coeffs_size = (size_t) (j.t_best / 8.);                                    // :796
     }
     pt.mark("truncation search");
@@ -767,7 +781,7 @@ bool BatchEncode::entropy_and_fallback()
         for (size_t f = 0; f < n; f++) {
             Job &j = jobs[f];
             b.active[f] = 0;
-            if (j.const_field) continue;
+            if (!j.search) continue;
             const size_t len2 = (size_t) j.rs[1].last.stream_bytes;
             const bool decided = es.floor_decides(f);                                         // (z may not be known - only that it loses)
             if (decided || len2 < j.zbytes.size() + j.len1 || j.need_pure) {                  // :838
@@ -830,13 +844,13 @@ int BatchEncode::assemble(uint8_t **outs, size_t *sizes)
 // ------------------------------------------------------------------------------------------------
 // `n` chunks of `tiles` frames each (tiles == 1: the frame-per-chunk case); `rctx`: residual engine for the stacked
 // chunk image when tiles > 1.
-int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const FrameConfig *fc, uint8_t **outs, size_t *sizes,
                  SliceGate *next, size_t tiles, ebcc_hip_ctx *rctx, unsigned slices, PhaseNote *note)
 {
-    BatchEncode e(ctx, d_frames, n, cfg, next, tiles, rctx, slices, note);
+    BatchEncode e(ctx, d_frames, n, fc, next, tiles, rctx, slices, note);
     if (const int r = e.analyse()) return r;                          // :671-692 (releases `next`)
     e.first_probe();                                                  // :693-716
-    if (e.searching) {
+    if (e.any_search) {
         e.search_1();                                                 // :728
         e.queue_search_2();                                           // (:836, beside what follows)
         if (!e.residual_layer()) return 1;                            // :730-762

@@ -47,7 +47,7 @@ struct ebcc_hip_ctx {
     size_t io_cap = 0;                      // bytes
     uint8_t *h_bounce = nullptr;            // 2 x kBounceBytes pinned: pageable host arrays cross PCIe through it (host_codec.hip)
     unsigned long long *h_pack = nullptr, *d_pack = nullptr;   // [2 pieces per frame][offset, length]
-    void *h_boxes = nullptr, *d_boxes = nullptr;               // boxes_cap bytes: the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use)
+    void *h_boxes = nullptr, *d_boxes = nullptr;               // boxes_cap bytes: the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use); an encode of frame groups keeps the table and the result words of k_group_ranges there (host_codec.hip)
     size_t boxes_cap = 0;
     ebcc::CutSlots cut{};                   // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
     bool cut_failed = false;                // (no memory for it: the search probes one cut per round)

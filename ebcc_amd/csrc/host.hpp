@@ -269,7 +269,18 @@ struct PhaseNote {
 // ---- one device batch (batch_codec.hip)
 // ebcc_encode for a batch of device-resident chunks: `n` chunks of `tiles` frames each (tiles == 1: the frame-per-chunk
 // case); `rctx`: residual engine for the stacked chunk image when tiles > 1.  Returns 0, 1 (error) or 2 (NaN/Inf).
-int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+// What a config says about one chunk: every layer from the entry points down passes one of these per chunk, a part of the
+// array along with the same part of the frames.  An entry point with one config for the whole call fills the array with it;
+// frame groups (ebcc_hip_frame_group) fill it group by group, a group bound already restated as MAX_ERROR.
+struct FrameConfig {
+    float base_cr = 0;
+    int mode = NONE;                                                // residual_compression_type, stale values included (quirk Q2)
+    float error = 0;
+    FrameConfig() = default;
+    explicit FrameConfig(const codec_config_t &c) : base_cr(c.base_cr), mode((int) c.residual_compression_type), error(c.error) {}
+    bool searching() const { return mode == MAX_ERROR || mode == RELATIVE_ERROR; }
+};
+int encode_batch(ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const FrameConfig *fc, uint8_t **outs, size_t *sizes,
                  SliceGate *next = nullptr, size_t tiles = 1, ebcc_hip_ctx *rctx = nullptr, unsigned slices = 1, PhaseNote *note = nullptr);
 // One frame stream, either format: the 48-byte "EBCC" header (:190-202, :1234-1260) or the legacy header-less prefix
 struct ParsedFrame {

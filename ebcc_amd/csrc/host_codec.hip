@@ -394,6 +394,137 @@ int array_range(ebcc_hip_ctx *ctx, const float *d_data, size_t n, float mm[2])
     return 0;
 }
 
+// The same for many arrays in one launch - the variables of a model step, each with a bound relative to its own range:
+// blockIdx.y is the group, its pointer and length one uniform load from `table`, out[3 * group ..] = {min key, max key, flag}
+// set to {~0, 0, 0} before the launch.  A group begins at any 4-byte alignment (head and tail one by one, the body 16 bytes
+// a lane with two loads in flight, as above); the waves reduce by shuffle and add one atomic each per word.  The grid's x
+// extent is that of the longest group: a workgroup that lies beyond a shorter group's body leaves at once (workgroup 0 never
+// does: it holds the lanes of head and tail) - the test is uniform over the workgroup and no barrier follows it.
+struct GroupSpan { const float *x; size_t n; };
+__global__ __launch_bounds__(256) void k_group_ranges(const GroupSpan *__restrict__ table, unsigned *__restrict__ out)
+{
+    const GroupSpan g = table[blockIdx.y];
+    const float *__restrict__ x = g.x;
+    const size_t n = g.n;
+    const size_t lead = (size_t) ((16 - ((uintptr_t) x & 15)) & 15) / 4, head = lead < n ? lead : n, n4 = (n - head) >> 2;
+    if (blockIdx.x != 0 && (size_t) blockIdx.x * blockDim.x >= n4) return;
+    unsigned kmin = ~0u, kmax = 0u;
+    int bad = 0;
+    auto take = [&](float v) {
+        if (isnan(v) || isinf(v)) bad = 1;
+        const unsigned k = float_order_key(v);
+        kmin = min(kmin, k);
+        kmax = max(kmax, k);
+    };
+    const size_t gid = (size_t) blockIdx.x * blockDim.x + threadIdx.x, step = (size_t) gridDim.x * blockDim.x;
+    if (gid < head) take(x[gid]);
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + head);
+    size_t i = gid;
+    for (; i + step < n4; i += 2 * step) {
+        const f32x4 p = x4[i], q = x4[i + step];
+        take(p.x); take(p.y); take(p.z); take(p.w);
+        take(q.x); take(q.y); take(q.z); take(q.w);
+    }
+    if (i < n4) { const f32x4 p = x4[i]; take(p.x); take(p.y); take(p.z); take(p.w); }
+    if (head + 4 * n4 + gid < n) take(x[head + 4 * n4 + gid]);
+    for (int d = 32; d >= 1; d >>= 1) {
+        kmin = min(kmin, (unsigned) __shfl_xor((int) kmin, d));
+        kmax = max(kmax, (unsigned) __shfl_xor((int) kmax, d));
+        bad |= __shfl_xor(bad, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned *o = out + 3 * (size_t) blockIdx.y;
+        atomicMin(&o[0], kmin);
+        atomicMax(&o[1], kmax);
+        if (bad) atomicOr(&o[2], 1u);
+    }
+}
+// keys[3 * g ..] = {min key, max key, non-finite flag} of the device arrays ptrs[g][0 .. lens[g]) (lens > 0, 4-byte aligned):
+// one upload of the table, one launch (per 65535 groups), one download and one wait.  Device current, the context the caller's
+// alone; table and words lie in the context's small pinned / device table (boxes_reserve).
+void group_range_keys(ebcc_hip_ctx *ctx, const float *const *ptrs, const size_t *lens, size_t n, unsigned *keys)
+{
+    constexpr size_t rec = sizeof(GroupSpan) + 3 * sizeof(unsigned);
+    boxes_reserve(ctx, n, rec);
+    GroupSpan *h_t = (GroupSpan *) ctx->h_boxes, *d_t = (GroupSpan *) ctx->d_boxes;
+    unsigned *h_o = (unsigned *) (h_t + n), *d_o = (unsigned *) (d_t + n);
+    size_t longest = 0;
+    for (size_t g = 0; g < n; g++) {
+        h_t[g] = GroupSpan{ptrs[g], lens[g]};
+        h_o[3 * g] = ~0u; h_o[3 * g + 1] = 0; h_o[3 * g + 2] = 0;
+        longest = std::max(longest, lens[g]);
+    }
+    EBCC_HIP_CHECK(hipMemcpyAsync(d_t, h_t, n * rec, hipMemcpyHostToDevice, ctx->stream));
+    const unsigned blocks = (unsigned) std::min<size_t>(std::max<size_t>(1, longest / (256 * 8)), 2048);
+    for (size_t lo = 0; lo < n; lo += 65535) {                      // (gridDim.y)
+        const size_t k = std::min<size_t>(65535, n - lo);
+        hipLaunchKernelGGL(k_group_ranges, dim3(blocks, (unsigned) k), dim3(256), 0, ctx->stream, d_t + lo, d_o + 3 * lo);
+    }
+    EBCC_HIP_LAUNCH_CHECK();
+    EBCC_HIP_CHECK(hipMemcpyAsync(h_o, d_o, n * 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    wait_stream(ctx->stream);
+    memcpy(keys, h_o, n * 3 * sizeof(unsigned));
+}
+// The same for arrays in host memory, on the process-wide pool in pieces of a million floats.
+void host_range_keys(const float *const *ptrs, const size_t *lens, size_t n, unsigned *keys)
+{
+    constexpr size_t kPiece = (size_t) 1 << 20;
+    struct Piece { size_t g, lo, hi; unsigned kmin = ~0u, kmax = 0, bad = 0; };
+    std::vector<Piece> pieces;
+    for (size_t g = 0; g < n; g++)
+        for (size_t lo = 0; lo < lens[g]; lo += kPiece) pieces.push_back(Piece{g, lo, std::min(lens[g], lo + kPiece)});
+    auto batch = HostPool::instance().submit(pieces.size(), entropy_threads(1), [&](size_t i) {
+        Piece &p = pieces[i];
+        const float *x = ptrs[p.g];
+        unsigned kmin = ~0u, kmax = 0, bad = 0;
+        for (size_t k = p.lo; k < p.hi; k++) {
+            bad |= (f2u(x[k]) & 0x7F800000u) == 0x7F800000u;
+            const unsigned key = float_order_key(x[k]);
+            kmin = std::min(kmin, key); kmax = std::max(kmax, key);
+        }
+        p.kmin = kmin; p.kmax = kmax; p.bad = bad;
+    });
+    if (!batch->wait()) throw HipFailure(batch->error.c_str());
+    for (size_t g = 0; g < n; g++) { keys[3 * g] = ~0u; keys[3 * g + 1] = 0; keys[3 * g + 2] = 0; }
+    for (const Piece &p : pieces) {
+        keys[3 * p.g] = std::min(keys[3 * p.g], p.kmin); keys[3 * p.g + 1] = std::max(keys[3 * p.g + 1], p.kmax); keys[3 * p.g + 2] |= p.bad;
+    }
+}
+
+// Where the chunks of an encode call lie: runs of chunks, each contiguous in (device or host) memory - one run for an
+// array, one per frame group unless the groups' arrays happen to follow one another.  The cuts of batches and slices fall
+// where they fall: each(lo, cnt, ...) visits the parts of the runs that make up chunks [lo, lo + cnt).
+struct FrameSource {
+    struct Run { const float *p; size_t first, n; };               // chunks [first, first + n) of the call lie at p
+    std::vector<Run> runs;
+    size_t total = 0;
+    FrameSource() = default;
+    FrameSource(const float *p, size_t n) { runs.push_back(Run{p, 0, n}); total = n; }
+    void add(const float *p, size_t n, size_t chunk_floats)
+    {
+        if (!runs.empty() && (uintptr_t) (runs.back().p + runs.back().n * chunk_floats) == (uintptr_t) p) runs.back().n += n;
+        else runs.push_back(Run{p, total, n});
+        total += n;
+    }
+    // fn(where, chunk of the batch, chunks) for every run that meets chunks [lo, lo + cnt)
+    template <class Fn> void each(size_t lo, size_t cnt, size_t chunk_floats, Fn fn) const
+    {
+        auto it = std::upper_bound(runs.begin(), runs.end(), lo, [](size_t v, const Run &r) { return v < r.first; });
+        for (it = it == runs.begin() ? it : it - 1; it != runs.end() && it->first < lo + cnt; ++it) {
+            const size_t a = std::max(lo, it->first), e = std::min(lo + cnt, it->first + it->n);
+            if (a < e) fn(it->p + (a - it->first) * chunk_floats, a - lo, e - a);
+        }
+    }
+    // chunks [lo, lo + cnt) where they lie, when one run holds them all (else nullptr)
+    const float *in_place(size_t lo, size_t cnt, size_t chunk_floats) const
+    {
+        const float *at = nullptr;
+        size_t parts = 0;
+        each(lo, cnt, chunk_floats, [&](const float *p, size_t, size_t) { at = p; parts++; });
+        return parts == 1 ? at : nullptr;
+    }
+};
+
 // ================================================================================================
 // slices of a batch
 // ================================================================================================
@@ -481,8 +612,8 @@ int run_slices(ebcc_hip_ctx *ctx, size_t n_frames, Fn fn, const char *env_name, 
     return worst;
 }
 
-// n_frames one-frame chunks as concurrent slices
-int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
+// n_frames one-frame chunks as concurrent slices (fc: a config per frame; a slice takes its part of it with its frames)
+int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const FrameConfig *fc, uint8_t **outs, size_t *sizes,
                       GpuPhase *phase = nullptr)
 {
     const size_t n_pix = ctx->n_pix;
@@ -492,7 +623,7 @@ int run_encode_slices(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,
     if (phase) phase->acquire();
     return run_slices(ctx, n_frames, [&](ebcc_hip_ctx *c, size_t lo, size_t cnt, SliceGate *next, unsigned slices) {
         note.expect((int) slices);
-        return encode_batch(c, d_frames + lo * n_pix, cnt, cfg, outs + lo, sizes + lo, next, 1, nullptr, slices, phase ? &note : nullptr);
+        return encode_batch(c, d_frames + lo * n_pix, cnt, fc + lo, outs + lo, sizes + lo, next, 1, nullptr, slices, phase ? &note : nullptr);
     }, "EBCC_HIP_SLICES", default_encode_slices());
 }
 
@@ -556,12 +687,12 @@ struct TwoSets {
 // n_frames one-frame chunks in batches of the context's capacity, alternately on the two sets: one batch at a time is in its
 // GPU phase, the next enters it when every slice of the current one has reached its entropy stage (GpuPhase / PhaseNote).
 // stage(set, first frame, count) -> where the batch's frames are on the device (a host array is uploaded there: that copy
-// runs beside the other batch's kernels too).
+// runs beside the other batch's kernels too).  fc: a config per frame; a batch takes its part of it with its frames.
 template <class Stage>
-int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const codec_config_t *cfg, uint8_t **outs, size_t *sizes, Stage stage)
+int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const FrameConfig *fc, uint8_t **outs, size_t *sizes, Stage stage)
 {
     const size_t cap = ctx->max_frames, batches = (n_frames + cap - 1) / cap;
-    if (batches == 1) return run_encode_slices(ctx, stage(ctx, (size_t) 0, n_frames), n_frames, cfg, outs, sizes);
+    if (batches == 1) return run_encode_slices(ctx, stage(ctx, (size_t) 0, n_frames), n_frames, fc, outs, sizes);
     TwoSets two(ctx);
     GpuPhase phase;
     std::atomic<size_t> next{0};
@@ -590,7 +721,7 @@ int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const codec_c
                 for (size_t r = next++; r < batches; r = next++) redo.push_back(r);
                 return;
             }
-            two.note(t, run_encode_slices(two.set[t], where, cnt, cfg, outs + lo, sizes + lo, &phase));
+            two.note(t, run_encode_slices(two.set[t], where, cnt, fc + lo, outs + lo, sizes + lo, &phase));
         }
     };
     two.both(work);
@@ -620,31 +751,40 @@ int decode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, Each each)
 // ================================================================================================
 // frames in pageable host memory <-> streams
 // ================================================================================================
-// n chunks of `tiles` frames each (tiles > 1: rc is the engine of the stacked chunk image), contiguous in host memory, in
-// batches of `cap` chunks on ctx.  A batch is uploaded in one go: uploads issued from inside the slices slow every slice
+// The chunks of `src` (FrameSource: runs in host memory), `tiles` frames each (tiles > 1: rc is the engine of the stacked chunk
+// image), with a config each, in batches of `cap` chunks on ctx.  A batch is uploaded in one go, run after run: uploads issued from inside the slices slow every slice
 // down (measured in round 1 with pageable copies, 5.6 against 3.7 GB/s, and again in round 2 through the bounce buffers,
 // 7.1 against 6.5).  One-frame chunks in batches that fill the engine run on the alternating sets, anything else batch
 // after batch.  0 ok, 1 error, 2 NaN / Inf in the data.
-int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const float *data, size_t n, const codec_config_t *cfg,
+int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const FrameSource &src, const FrameConfig *fc,
                      uint8_t **outs, size_t *sizes)
 {
-    const size_t n_pix = ctx->n_pix * tiles;
+    const size_t n_pix = ctx->n_pix * tiles, n = src.total;
     PhaseTimer pt[2];                                               // (one per engine set: each has its own thread)
     auto stage = [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
         float *d = io_buffer(set, cap * n_pix * sizeof(float));
-        copy_pageable(set, const_cast<float *>(data + lo * n_pix), d, cnt * n_pix * sizeof(float), false);
+        src.each(lo, cnt, n_pix, [&](const float *h, size_t at, size_t k) {
+            copy_pageable(set, const_cast<float *>(h), d + at * n_pix, k * n_pix * sizeof(float), false);
+        });
         pt[set != ctx].mark("host frames: upload");
         return (const float *) d;
     };
-    if (tiles == 1 && ctx->max_frames == cap) return encode_batches_alternating(ctx, n, cfg, outs, sizes, stage);
+    if (tiles == 1 && ctx->max_frames == cap) return encode_batches_alternating(ctx, n, fc, outs, sizes, stage);
     for (size_t lo = 0; lo < n; lo += cap) {
         const size_t k = std::min(cap, n - lo);
         const float *d = stage(ctx, lo, k);
-        const int r = tiles == 1 ? run_encode_slices(ctx, d, k, cfg, outs + lo, sizes + lo)
-                                 : encode_batch(ctx, d, k, cfg, outs + lo, sizes + lo, nullptr, tiles, rc);
+        const int r = tiles == 1 ? run_encode_slices(ctx, d, k, fc + lo, outs + lo, sizes + lo)
+                                 : encode_batch(ctx, d, k, fc + lo, outs + lo, sizes + lo, nullptr, tiles, rc);
         if (r) return r;
     }
     return 0;
+}
+// (one array, one config)
+int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const float *data, size_t n, const codec_config_t *cfg,
+                     uint8_t **outs, size_t *sizes)
+{
+    const std::vector<FrameConfig> fc(n, FrameConfig(*cfg));
+    return encode_from_host(ctx, rc, tiles, cap, FrameSource(data, n), fc.data(), outs, sizes);
 }
 
 // The decode counterpart: streams of n chunks -> host memory at `out`, one download per batch (copies issued from inside
@@ -767,6 +907,16 @@ int run_on_devices(size_t n_chunks, Fn fn)
 // Encode: the argument checks, out_streams emptied first and, when the call fails, every stream made so far freed again;
 // code() runs in the device prologue and returns the status.
 template <class Code>
+int encode_checked(ebcc_hip_ctx *ctx, size_t n, uint8_t **outs, size_t *sizes, Code &&code)
+{
+    log_set_level_from_env();
+    for (size_t f = 0; f < n; f++) { outs[f] = nullptr; sizes[f] = 0; }
+    const int rc = on_codec(ctx->device, 1, code);
+    if (rc)
+        for (size_t f = 0; f < n; f++) { free(outs[f]); outs[f] = nullptr; sizes[f] = 0; }
+    return rc;
+}
+template <class Code>
 int encode_call(const char *who, ebcc_hip_ctx *ctx, const void *frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes,
                 Code &&code)
 {
@@ -775,21 +925,126 @@ int encode_call(const char *who, ebcc_hip_ctx *ctx, const void *frames, size_t n
         set_error("%s: config dims must be (1, %d, %d)", who, ctx->height, ctx->width);
         return 1;
     }
-    log_set_level_from_env();
-    for (size_t f = 0; f < n; f++) { outs[f] = nullptr; sizes[f] = 0; }
-    const int rc = on_codec(ctx->device, 1, code);
-    if (rc)
-        for (size_t f = 0; f < n; f++) { free(outs[f]); outs[f] = nullptr; sizes[f] = 0; }
-    return rc;
+    return encode_checked(ctx, n, outs, sizes, code);
 }
 
-// device-resident frames: batches of the context's capacity on the alternating sets (one batch: one run_encode_slices)
+// Device-resident frames: batches of the context's capacity on the alternating sets (one batch: one run_encode_slices).  A
+// batch whose frames are adjacent in memory is coded where it lies; otherwise its runs are brought into the engine set's
+// staging buffer, one device-to-device copy per run on that set's stream, and the stage waits for them (the slices read
+// them on streams of their own) - as the container stage does with the chunks it gathers.
+int encode_device_frames(ebcc_hip_ctx *ctx, const FrameSource &src, const FrameConfig *fc, uint8_t **outs, size_t *sizes)
+{
+    const size_t n_pix = ctx->n_pix, cap = std::min(src.total, ctx->max_frames);
+    PhaseTimer pt[2];
+    return encode_batches_alternating(ctx, src.total, fc, outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
+        if (const float *where = src.in_place(lo, cnt, n_pix)) return where;
+        float *d = io_buffer(set, cap * n_pix * sizeof(float));
+        src.each(lo, cnt, n_pix, [&](const float *p, size_t at, size_t k) {
+            EBCC_HIP_CHECK(hipMemcpyAsync(d + at * n_pix, p, k * n_pix * sizeof(float), hipMemcpyDeviceToDevice, set->stream));
+        });
+        wait_stream(set->stream);
+        pt[set != ctx].mark("frame groups: runs copied");
+        return (const float *) d;
+    });
+}
 int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes)
 {
     return encode_call(who, ctx, d_frames, n, cfg, outs, sizes, [&] {
-        return encode_batches_alternating(ctx, n, cfg, outs, sizes, [&](ebcc_hip_ctx *, size_t lo, size_t) { return d_frames + lo * ctx->n_pix; });
+        const std::vector<FrameConfig> fc(n, FrameConfig(*cfg));
+        return encode_device_frames(ctx, FrameSource(d_frames, n), fc.data(), outs, sizes);
     });
 }
+// ---- frame groups (include/ebcc_hip.h): arrays of frames with a config each, coded as one call
+// What ebcc_hip_groups_check checks, for frames of height x width: the total number of frames, or -1 with the message set.
+long groups_total(const char *who, size_t height, size_t width, const ebcc_hip_frame_group *groups, size_t n_groups)
+{
+    if (!groups || n_groups < 1) { set_error("%s: no groups", who); return -1; }
+    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("%s: unsupported geometry %zu x %zu", who, height, width); return -1; }
+    size_t total = 0, bytes = 0;
+    for (size_t g = 0; g < n_groups; g++) {
+        const ebcc_hip_frame_group &G = groups[g];
+        if (!G.frames || G.n_frames < 1) { set_error("%s: group %zu has no frames", who, g); return -1; }
+        if ((uintptr_t) G.frames & 3) { set_error("%s: the frames of group %zu are not 4-byte aligned", who, g); return -1; }
+        if (G.config.dims[0] != 1 || G.config.dims[1] != height || G.config.dims[2] != width) {
+            set_error("%s: group %zu: config dims (%zu, %zu, %zu) are not (1, %zu, %zu)", who, g, G.config.dims[0], G.config.dims[1], G.config.dims[2], height, width);
+            return -1;
+        }
+        if (__builtin_add_overflow(total, G.n_frames, &total) || total > (size_t) LONG_MAX ||
+            __builtin_mul_overflow(total, height * width * sizeof(float), &bytes)) {
+            set_error("%s: the number of frames overflows at group %zu", who, g);
+            return -1;
+        }
+    }
+    return (long) total;
+}
+
+enum class GroupForm { Frames, Shard, Host };
+// The three encode entry points: the check, the context, the capacity (frames form); then, in the device prologue, the ranges
+// of the groups whose bound is relative to the range of the whole group - one launch and one wait for all of them (device
+// forms), a scan on the host pool (host form: nothing extra is uploaded) - restated as MAX_ERROR with error * (max - min) in
+// host float arithmetic as ebcc_encode_chunking_compat does (:1078-1087), and the frames of all groups as one list with a
+// config each.  NaN / Inf: 2 with the group named - before anything is coded for a group range, else when a batch meets it.
+int encode_groups(const char *who, ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **outs, size_t *sizes,
+                  GroupForm form)
+{
+    if (!ctx || !outs || !sizes) { set_error("%s: bad arguments", who); return 1; }
+    if (ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
+    const long checked = groups_total(who, (size_t) ctx->height, (size_t) ctx->width, groups, n_groups);
+    if (checked < 0) return 1;
+    const size_t total = (size_t) checked, n_pix = ctx->n_pix;
+    if (form == GroupForm::Frames && total > ctx->max_frames) {
+        for (size_t f = 0; f < total; f++) { outs[f] = nullptr; sizes[f] = 0; }
+        set_error("%s: %zu frames, the context holds %zu", who, total, ctx->max_frames);
+        return 1;
+    }
+    std::vector<FrameConfig> fc;
+    fc.reserve(total);
+    FrameSource src;
+    std::vector<size_t> first(n_groups), ranged, all(n_groups);
+    for (size_t g = 0; g < n_groups; g++) {
+        const ebcc_hip_frame_group &G = groups[g];
+        first[g] = fc.size(); all[g] = g;
+        fc.insert(fc.end(), G.n_frames, FrameConfig(G.config));
+        src.add(G.frames, G.n_frames, n_pix);
+        if (G.range_of_group && G.config.residual_compression_type == RELATIVE_ERROR) ranged.push_back(g);
+    }
+    auto range_keys = [&](const std::vector<size_t> &list) {
+        std::vector<const float *> ptrs;
+        std::vector<size_t> lens;
+        for (size_t g : list) { ptrs.push_back(groups[g].frames); lens.push_back(groups[g].n_frames * n_pix); }
+        std::vector<unsigned> keys(3 * list.size());
+        if (form == GroupForm::Host) host_range_keys(ptrs.data(), lens.data(), list.size(), keys.data());
+        else group_range_keys(ctx, ptrs.data(), lens.data(), list.size(), keys.data());
+        return keys;
+    };
+    auto nonfinite = [&](size_t g) {
+        log_fatal("NaN or Inf found in data of group %zu", g);
+        set_error("%s: NaN or Inf found in the data of group %zu", who, g);
+        return 2;
+    };
+    return encode_checked(ctx, total, outs, sizes, [&] {
+        if (!ranged.empty()) {
+            const std::vector<unsigned> keys = range_keys(ranged);
+            for (size_t i = 0; i < ranged.size(); i++) if (keys[3 * i + 2]) return nonfinite(ranged[i]);
+            for (size_t i = 0; i < ranged.size(); i++) {
+                const ebcc_hip_frame_group &G = groups[ranged[i]];
+                FrameConfig c(G.config);
+                c.error *= float_of_order_key(keys[3 * i + 1]) - float_of_order_key(keys[3 * i]);
+                c.mode = MAX_ERROR;
+                std::fill_n(fc.begin() + first[ranged[i]], G.n_frames, c);
+            }
+        }
+        const int rc = form == GroupForm::Host ? encode_from_host(ctx, nullptr, 1, ctx->max_frames, src, fc.data(), outs, sizes)
+                                               : encode_device_frames(ctx, src, fc.data(), outs, sizes);
+        if (rc == 2) {                                              // (a batch met it: which group was it)
+            const std::vector<unsigned> keys = range_keys(all);
+            for (size_t g = 0; g < n_groups; g++) if (keys[3 * g + 2]) return nonfinite(g);
+            set_error("%s: NaN or Inf found in the data", who);
+        }
+        return rc;
+    });
+}
+
 // The list of a list entry point, as the call it stands for: the streams of the frames the boxes name, in their order, with the
 // boxes' frames counted over those.  A frame no box names is not looked at - not even its pointer.
 struct BoxCall {
@@ -1048,8 +1303,9 @@ int encode_array_chunks(const char *who, ebcc_hip_ctx *ctx, const float *d_array
     for (int i = 0; i < 3; i++) { cc.dims[i] = box.cd[i]; cc.chunk_dims[i] = 0; }
     const size_t csize = plan.csize, cap = std::min(count, ctx->max_frames);
     PhaseTimer pt[2];
+    const std::vector<FrameConfig> fc(count, FrameConfig(cc));
     return encode_call(who, ctx, d_array, count, &cc, outs, sizes, [&] {
-        return encode_batches_alternating(ctx, count, &cc, outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
+        return encode_batches_alternating(ctx, count, fc.data(), outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
             if (box.slabs()) return d_array + (first + lo) * csize;
             float *d = io_buffer(set, cap * csize * sizeof(float));
             launch_gather_chunks(d_array, box.dims[1], box.dims[2], box.cd[1], box.cd[2], first + lo, cnt, d, set->stream);
@@ -1465,6 +1721,52 @@ int ebcc_hip_encode_shard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_fra
                           uint8_t **out_streams, size_t *out_sizes)
 {
     return encode_resident("ebcc_hip_encode_shard", ctx, d_frames, n_frames, config, out_streams, out_sizes);
+}
+
+// ---- frame groups: many arrays of frames, a config each, in one call (encode_groups above)
+long ebcc_hip_groups_check(size_t height, size_t width, const ebcc_hip_frame_group *groups, size_t n_groups)
+{
+    EBCC_API_TRY
+    return groups_total("ebcc_hip_groups_check", height, width, groups, n_groups);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_encode_frames_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **out_streams, size_t *out_sizes)
+{
+    EBCC_API_TRY
+    return encode_groups("ebcc_hip_encode_frames_groups", ctx, groups, n_groups, out_streams, out_sizes, GroupForm::Frames);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_encode_shard_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **out_streams, size_t *out_sizes)
+{
+    EBCC_API_TRY
+    return encode_groups("ebcc_hip_encode_shard_groups", ctx, groups, n_groups, out_streams, out_sizes, GroupForm::Shard);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_encode_host_frames_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **out_streams, size_t *out_sizes)
+{
+    EBCC_API_TRY
+    return encode_groups("ebcc_hip_encode_host_frames_groups", ctx, groups, n_groups, out_streams, out_sizes, GroupForm::Host);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_group_ranges(ebcc_hip_ctx *ctx, const float *const *d_ptrs, const size_t *n_floats, size_t n_groups, float *minmax, int *nonfinite)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_group_ranges";
+    if (!ctx || !d_ptrs || !n_floats || !minmax || !nonfinite || n_groups < 1) { set_error("%s: bad arguments", who); return 1; }
+    for (size_t g = 0; g < n_groups; g++)
+        if (!d_ptrs[g] || n_floats[g] < 1 || ((uintptr_t) d_ptrs[g] & 3)) { set_error("%s: group %zu is empty or not 4-byte aligned", who, g); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        std::vector<unsigned> keys(3 * n_groups);
+        group_range_keys(ctx, d_ptrs, n_floats, n_groups, keys.data());
+        int rc = 0;
+        for (size_t g = 0; g < n_groups; g++) {
+            nonfinite[g] = keys[3 * g + 2] != 0;
+            if (nonfinite[g]) { if (!rc) set_error("%s: NaN or Inf found in the data of group %zu", who, g); rc = 2; continue; }
+            minmax[2 * g] = float_of_order_key(keys[3 * g]); minmax[2 * g + 1] = float_of_order_key(keys[3 * g + 1]);
+        }
+        return rc;
+    });
+    EBCC_API_CATCH(1)
 }
 
 // Any number of streams decoded to consecutive frames on the device, in batches of the context's capacity on the two

@@ -40,6 +40,11 @@ def frame_config(height, width, base_cr, residual_opt=("none", None)):
     return c
 
 
+class FrameGroup(ctypes.Structure):
+    """ebcc_hip_frame_group, include/ebcc_hip.h: an array of frames with its own config."""
+    _fields_ = [("frames", ctypes.c_void_p), ("n_frames", ctypes.c_size_t), ("config", CodecConfig), ("range_of_group", ctypes.c_int)]
+
+
 def _stream_arrays(streams, named=None):
     """(the streams as bytes - the caller keeps them alive for the call -, their ctypes pointer array, their size array);
     `named`: only the streams at these indices are read, the others (None allowed) become a null pointer of size 0"""
@@ -102,6 +107,8 @@ class BatchCodec:
                                                           ctypes.c_void_p]
         lib.ebcc_hip_decode_host_frames_placed.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+        lib.ebcc_hip_encode_host_frames_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameGroup), ctypes.c_size_t,
+                                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -137,6 +144,37 @@ class BatchCodec:
         res = []
         for i in range(n):
             res.append(ctypes.string_at(outs[i], sizes[i]))
+            self.lib.free_buffer(outs[i])
+        return res
+
+    def encode_groups(self, groups):
+        """Many variables in one device call: `groups` is a list of (frames, base_cr, residual_opt[, range_of_group]) - frames
+        (n, H, W) float32 in host memory (each group its own array, any n), base_cr and residual_opt as for frame_config,
+        range_of_group=True: a relative error target counts against (max - min) over the whole group, as
+        ebcc_encode_chunking_compat restates it.  -> one list of EBCC frame streams (bytes) per group; every stream is what
+        encode() gives for that frame with the group's config.  All frames run as one list, in batches on the two engine sets."""
+        if not groups:
+            raise ValueError("no groups")
+        arrays, table = [], (FrameGroup * len(groups))()
+        for g, item in enumerate(groups):
+            frames, base_cr, residual_opt = item[:3]
+            a = np.ascontiguousarray(frames, np.float32)
+            if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (self.h, self.w):
+                raise ValueError(f"group {g}: frames must be (n, {self.h}, {self.w}) with n >= 1, got {a.shape}")
+            arrays.append(a)                                            # (kept alive for the call)
+            table[g].frames, table[g].n_frames = a.ctypes.data, a.shape[0]
+            table[g].config = frame_config(self.h, self.w, base_cr, residual_opt)
+            table[g].range_of_group = int(bool(item[3])) if len(item) > 3 else 0
+        total = sum(a.shape[0] for a in arrays)
+        outs = (ctypes.c_void_p * total)()
+        sizes = (ctypes.c_size_t * total)()
+        if self.lib.ebcc_hip_encode_host_frames_groups(self.ctx, table, len(groups), outs, sizes):
+            self._fail("ebcc_hip_encode_host_frames_groups")
+        res, at = [], 0
+        for a in arrays:
+            res.append([ctypes.string_at(outs[i], sizes[i]) for i in range(at, at + a.shape[0])])
+            at += a.shape[0]
+        for i in range(total):
             self.lib.free_buffer(outs[i])
         return res
 
@@ -288,6 +326,52 @@ def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, co
         streams = codec.encode(flat[lo:lo + step], cfg)
         for i, s in enumerate(streams):
             idx = np.unravel_index(lo + i, lead) if lead else ()
+            dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
+
+
+def filter_options(dset):
+    """(base_cr, residual_opt) of an EBCC-filtered dataset, from the cd_values of its filter 308 as
+    /root/reference/src/h5z_ebcc.c:38-93 reads them: (height, width, f32 bits of base_cr, mode[, f32 bits of the error])."""
+    plist = dset.id.get_create_plist()
+    for i in range(plist.get_nfilters()):
+        code, _flags, cd, _name = plist.get_filter(i)
+        if code == EBCC_Filter.FILTER_ID:
+            if len(cd) < 4 or (cd[3] and len(cd) < 5) or (int(cd[0]), int(cd[1])) != tuple(dset.shape[-2:]):
+                raise ValueError(f"{dset.name}: filter 308 parameters {tuple(cd)} do not describe frames of {dset.shape[-2:]}")
+            bits = lambda v: float(np.array([v], np.uint32).view(np.float32)[0])  # noqa: E731
+            mode = {0: "none", 1: "max_error_target", 2: "relative_error_target"}.get(int(cd[3]))
+            if mode is None:
+                raise ValueError(f"{dset.name}: unknown residual mode {cd[3]}")
+            return bits(cd[2]), (mode, bits(cd[4]) if cd[3] else None)
+    raise ValueError(f"{dset.name}: not an EBCC-filtered dataset")
+
+
+def write_variables(items, batch=256, codec=None):
+    """Several variables in one device call: `items` is a list of (dset, first_frame, frames) over one-frame-per-chunk
+    EBCC-filtered datasets of one frame geometry - frames (n, H, W) float32 go to the chunks first_frame .. first_frame + n - 1
+    of dset, counted in C order over its leading axes.  Every dataset's own filter-308 parameters are its group's config
+    (filter_options), all groups are coded by one BatchCodec.encode_groups call, then every chunk is stored pre-filtered.
+    The chunk bytes are those write_frames gives dataset by dataset."""
+    if not items:
+        raise ValueError("no items")
+    h, w = items[0][0].shape[-2:]
+    groups, total = [], 0
+    for dset, first, frames in items:
+        frames = np.ascontiguousarray(frames, np.float32)
+        lead = dset.shape[:-2]
+        n = int(np.prod(lead)) if lead else 1
+        if tuple(dset.shape[-2:]) != (h, w) or dset.chunks != (1,) * len(lead) + (h, w):
+            raise ValueError(f"{dset.name}: one-frame chunks of {h} x {w} are needed, got chunks {dset.chunks}")
+        if frames.ndim != 3 or frames.shape[1:] != (h, w) or first < 0 or first + len(frames) > n or len(frames) < 1:
+            raise ValueError(f"{dset.name}: frames {frames.shape} from frame {first} on do not fit the dataset's {n} frames")
+        base_cr, opt = filter_options(dset)
+        groups.append((frames, base_cr, opt))
+        total += len(frames)
+    codec = codec or cached_codec(h, w, min(batch, total))
+    for (dset, first, _), streams in zip(items, codec.encode_groups(groups)):
+        lead = dset.shape[:-2]
+        for i, s in enumerate(streams):
+            idx = np.unravel_index(first + i, lead) if lead else ()
             dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
 
 

@@ -307,6 +307,53 @@ int ebcc_hip_encode_array_chunks(ebcc_hip_ctx *ctx, const float *d_array, const 
 int ebcc_hip_encode_container(ebcc_hip_ctx *ctx, const float *d_array, const codec_config_t *config, int compat,
                               uint8_t **out, size_t *out_size);
 
+/* ---- frame groups: many variables in one call ------------------------------------------------------
+ * An archive step is many variables, a few dozen levels each, every variable with its own rate, bound and often its own
+ * mode - temperature to 0.02 K, humidity relative to its range, a mask without a residual layer - and the variables are
+ * separate arrays.  A group is one such array with its config; the calls below code the frames of all groups as one list,
+ * in batches and slices as the uniform entry points do (the cuts fall where they fall, inside a group if need be), every
+ * frame with its group's config.  The reference has one config per call (ebcc_encode, src/ebcc_codec.h:41).
+ * Streams come out in group order, frame order within a group.  Frame f of a group is, byte for byte,
+ * ebcc_hip_encode_frames of that frame alone with the group's config; for a group with range_of_group it is chunk f of
+ * ebcc_hip_encode_container(ctx, group.frames, {dims {n, H, W}, chunk_dims {1, H, W}, ...}, compat = 1).  Results do not
+ * depend on how groups, batches, slices and engine sets cut the frames.  The environment switches of the encoder stay
+ * process-wide.  A batch whose frames are adjacent in memory is read where it lies; otherwise its runs are copied into the
+ * engine set's staging buffer (device forms), or uploaded there run by run (host form).
+ * Return and ownership as ebcc_hip_encode_shard: 0 = ok, 1 = error, 2 = NaN / Inf (the message names the group; a group
+ * with range_of_group is found before anything is coded); on failure every stream is freed and every out_streams entry is
+ * NULL (a list ebcc_hip_groups_check refuses: out_streams is not touched - its length is not known).  One-frame chunks only. */
+typedef struct {
+    const float   *frames;        /* the group's [n_frames][H][W] floats, 4-byte aligned; device pointer in the frames / shard
+                                     forms, host pointer in the host form; read only */
+    size_t         n_frames;      /* > 0 */
+    codec_config_t config;        /* dims {1, H, W} of the context; base_cr, residual_compression_type, error of this group;
+                                     chunk_dims ignored */
+    int            range_of_group;/* RELATIVE_ERROR only: error is relative to (max - min) over the whole group, restated as
+                                     MAX_ERROR with error * range exactly as ebcc_encode_chunking_compat does
+                                     (/root/reference/src/ebcc_codec.c:1078-1087); otherwise ignored, as compat ignores it */
+} ebcc_hip_frame_group;
+/* total frames <= the context's capacity */
+int ebcc_hip_encode_frames_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **out_streams,
+                                  size_t *out_sizes);
+/* any number of frames, batches on the two engine sets */
+int ebcc_hip_encode_shard_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **out_streams,
+                                 size_t *out_sizes);
+/* groups in pageable host memory, any number of frames; group ranges are taken by host threads, nothing extra is uploaded */
+int ebcc_hip_encode_host_frames_groups(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups,
+                                       uint8_t **out_streams, size_t *out_sizes);
+/* unit level: min / max of n_groups device arrays in ONE launch - d_ptrs[g] (a host array of device pointers, each at any
+ * 4-byte aligned address) holds n_floats[g] > 0 floats; minmax [n_groups][2], nonfinite [n_groups].  Exact: -0 counts as +0.
+ * A group with a NaN or an Inf sets its flag and leaves its minmax pair untouched; the other groups' results are still
+ * exact.  0 = ok, 1 = error, 2 = a flag is set.  ctx: any context of the device. */
+int ebcc_hip_group_ranges(ebcc_hip_ctx *ctx, const float *const *d_ptrs, const size_t *n_floats, size_t n_groups, float *minmax,
+                          int *nonfinite);
+/* Host only, no device: the total number of frames of a list the encode calls above accept for frames of height x width, or
+ * -1 with a message for what they refuse before touching a device: n_groups 0 or a null list, a group with n_frames 0 or a
+ * null (or misaligned) pointer, config.dims other than {1, height, width}, a geometry ebcc_hip_create refuses, a frame total
+ * that overflows.  (The encode calls also refuse a context of another geometry, a context for chunks of several frames, and
+ * in the frames form a total beyond the capacity.) */
+long ebcc_hip_groups_check(size_t height, size_t width, const ebcc_hip_frame_group *groups, size_t n_groups);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is

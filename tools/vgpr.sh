@@ -2,7 +2,7 @@
 # VGPR / SGPR / scratch / spills of the kernels whose name matches a pattern (development aid; needs no GPU):
 #   tools/vgpr.sh                                          the tier-1 kernels (t1_)
 #   tools/vgpr.sh 'j2k_level|j2k_cols_fin|rows_inv'        the fused inverse levels and the last residual row passes
-#   tools/vgpr.sh 'gather_chunks|array_range'              the chunk gather and the range of a device array (host_codec.hip)
+#   tools/vgpr.sh 'gather_chunks|array_range|group_ranges' the chunk gather, the range of a device array and of many (host_codec.hip)
 # Compiled with the Makefile's code-generation flags; run it at two commits to compare their register use.
 pat="${1:-t1_}"
 cd "$(dirname "$0")/../ebcc_amd/csrc"
