@@ -421,6 +421,10 @@ void ebcc_hip_destroy(ebcc_hip_ctx *ctx)
     if (ctx->h_boxes) hipHostFree(ctx->h_boxes);
     if (ctx->d_boxes) hipFree(ctx->d_boxes);
     if (ctx->h_bounce) hipHostFree(ctx->h_bounce);
+    if (ctx->d_audit) hipFree(ctx->d_audit);
+    if (ctx->d_offenders) hipFree(ctx->d_offenders);
+    if (ctx->d_errs) hipFree(ctx->d_errs);
+    if (ctx->h_errs) hipHostFree(ctx->h_errs);
     if (ctx->ev_a) hipEventDestroy(ctx->ev_a);
     if (ctx->ev_b) hipEventDestroy(ctx->ev_b);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);

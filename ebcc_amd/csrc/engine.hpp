@@ -49,7 +49,14 @@ struct ebcc_hip_ctx {
     unsigned long long *h_pack = nullptr, *d_pack = nullptr;   // [2 pieces per frame][offset, length]
     void *h_boxes = nullptr, *d_boxes = nullptr;               // boxes_cap bytes: the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use); an encode of frame groups keeps the table and the result words of k_group_ranges there (host_codec.hip)
     size_t boxes_cap = 0;
-    ebcc::CutSlots cut{};                   // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
+    // Audit and hard-bound encode (host_codec.hip), all made on first use and freed with the engine set: the decoded frames of
+    // one batch, the originals of a round's offenders gathered side by side, and the records of k_frame_errors (one per
+    // workgroup, then one per frame, with the frames' bounds behind them) on the device and pinned.
+    float *d_audit = nullptr, *d_offenders = nullptr;
+    size_t audit_cap = 0, offenders_cap = 0;                    // bytes
+    void *d_errs = nullptr, *h_errs = nullptr;
+    size_t errs_cap = 0;                                        // bytes
+    ebcc::CutSlots cut{};                 // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
     bool cut_failed = false;                // (no memory for it: the search probes one cut per round)
 };
 

@@ -1,7 +1,8 @@
 // host_codec.hip - the reference's C API (include/ebcc_codec.h) on top of the MI355X engine: engines per device and
 // frame geometry, concurrent slices and alternating engine sets of a batch, host <-> device copies, the EBCK chunk
 // container (/root/reference/src/ebcc_codec.c:920-1090, :1322-1449), and the batch entry points of include/ebcc_hip.h.
-// Two kernels live here, beside the host loops they stand for: the chunk gather and the range of an array on the device.
+// A few kernels live here, beside the host loops they stand for: the chunk gather, the range of an array (and of many) on the
+// device, and the per-frame error statistics of the audit and the hard-bound encode.
 // The frame codec itself is batch_codec.hip, the HDF5 plugin h5z_filter.hip, the host services host_pool.hip (host.hpp).
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <climits>
@@ -491,6 +492,143 @@ void host_range_keys(const float *const *ptrs, const size_t *lens, size_t n, uns
     }
 }
 
+// Per-frame error statistics of decoded frames d against their originals x, both [gridDim.y][n_pix] (include/ebcc_hip.h:
+// ebcc_hip_frame_error): blockIdx.y is the frame, blockIdx.x one of the frame's pieces - as many as frame_error_pieces gives for
+// the pixel count, whatever the batch.  A lane takes the quads (pixels 4q .. 4q + 3) q = its index, + step, .., two of them in
+// flight; a quad is one 16-byte load from a frame that begins on a 16-byte boundary and four 4-byte loads from one that does
+// not (each array on its own: x and d need not agree), and the last n_pix % 4 pixels go one by one.  Quads count from the
+// frame's first pixel, not from an address: which lane adds which difference, and in which order, depends on n_pix alone, so
+// the sums in double come out the same bits for a frame wherever it lies - in the caller's tensor, in a staging buffer, in a
+// gathered list of offenders.  No atomics: the lanes of a wave reduce by a butterfly of shuffles (a + b on both sides of an
+// exchange: every lane ends with the same bits), the four waves through LDS in wave order, and the workgroup writes one
+// record; k_frame_errors_fold adds a frame's records in piece order.
+//   key   bits(|x - d|, float) << 32 | ~pixel: the maximum is the largest error at its first pixel
+//   kmin, kmax   order keys of x (float_order_key: -0 is +0);  bad   x holds a NaN or an Inf
+struct ErrRecord { unsigned long long key, n_over; double sum, sum_sq; unsigned kmin, kmax, bad, pad; };
+static_assert(sizeof(ErrRecord) == 48, "one record is 48 bytes");
+__device__ inline void err_fold(ErrRecord &a, const ErrRecord &b)
+{
+    a.key = max(a.key, b.key); a.n_over += b.n_over; a.sum += b.sum; a.sum_sq += b.sum_sq;
+    a.kmin = min(a.kmin, b.kmin); a.kmax = max(a.kmax, b.kmax); a.bad |= b.bad;
+}
+__global__ __launch_bounds__(256) void k_frame_errors(const float *__restrict__ x, const float *__restrict__ d, size_t n_pix,
+                                                      const float *__restrict__ bound, ErrRecord *__restrict__ part)
+{
+    const float *__restrict__ xf = x + (size_t) blockIdx.y * n_pix, *__restrict__ df = d + (size_t) blockIdx.y * n_pix;
+    const float lim = bound ? bound[blockIdx.y] : 0.0f;
+    ErrRecord r{0, 0, 0.0, 0.0, ~0u, 0u, 0u, 0u};
+    auto take = [&](float a, float b, size_t pixel) {
+        if (isnan(a) || isinf(a)) r.bad = 1;
+        const unsigned k = float_order_key(a);
+        r.kmin = min(r.kmin, k);
+        r.kmax = max(r.kmax, k);
+        const float ab = fabsf(a - b);
+        r.key = max(r.key, ((unsigned long long) __float_as_uint(ab) << 32) | (unsigned) ~(unsigned) pixel);
+        if (bound && ab > lim) r.n_over++;
+        const double e = (double) a - (double) b;
+        r.sum += e;
+        r.sum_sq += e * e;
+    };
+    auto take4 = [&](const f32x4 &a, const f32x4 &b, size_t q) {
+        take(a.x, b.x, 4 * q); take(a.y, b.y, 4 * q + 1); take(a.z, b.z, 4 * q + 2); take(a.w, b.w, 4 * q + 3);
+    };
+    // (uniform over the workgroup: a frame's base address)
+    const bool xv = ((uintptr_t) xf & 15) == 0, dv = ((uintptr_t) df & 15) == 0;
+    auto quad = [](const float *p, bool vec, size_t q) {
+        if (vec) return reinterpret_cast<const f32x4 *>(p)[q];
+        const float *s = p + 4 * q;
+        return f32x4{s[0], s[1], s[2], s[3]};
+    };
+    const size_t gid = (size_t) blockIdx.x * blockDim.x + threadIdx.x, step = (size_t) gridDim.x * blockDim.x, n4 = n_pix >> 2;
+    size_t i = gid;
+    for (; i + step < n4; i += 2 * step) {
+        const f32x4 a0 = quad(xf, xv, i), a1 = quad(xf, xv, i + step), b0 = quad(df, dv, i), b1 = quad(df, dv, i + step);
+        take4(a0, b0, i);
+        take4(a1, b1, i + step);
+    }
+    if (i < n4) take4(quad(xf, xv, i), quad(df, dv, i), i);
+    if (4 * n4 + gid < n_pix) take(xf[4 * n4 + gid], df[4 * n4 + gid], 4 * n4 + gid);
+    for (int o = 32; o >= 1; o >>= 1) {
+        ErrRecord t;
+        t.key = __shfl_xor(r.key, o); t.n_over = __shfl_xor(r.n_over, o); t.sum = __shfl_xor(r.sum, o); t.sum_sq = __shfl_xor(r.sum_sq, o);
+        t.kmin = (unsigned) __shfl_xor((int) r.kmin, o); t.kmax = (unsigned) __shfl_xor((int) r.kmax, o); t.bad = (unsigned) __shfl_xor((int) r.bad, o);
+        err_fold(r, t);
+    }
+    __shared__ ErrRecord waves[4];
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) err_fold(r, waves[w]);
+        part[(size_t) blockIdx.y * gridDim.x + blockIdx.x] = r;
+    }
+}
+// out[f] = the records part[f][0 .. pieces) of frame f added in piece order; a lane per frame
+__global__ __launch_bounds__(64) void k_frame_errors_fold(const ErrRecord *__restrict__ part, unsigned pieces, unsigned n, ErrRecord *__restrict__ out)
+{
+    const unsigned f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    ErrRecord r = part[(size_t) f * pieces];
+    for (unsigned p = 1; p < pieces; p++) err_fold(r, part[(size_t) f * pieces + p]);
+    out[f] = r;
+}
+// workgroups a frame of n_pix pixels is cut into: two quads in flight a lane make 2048 pixels a step
+unsigned frame_error_pieces(size_t n_pix) { return (unsigned) std::min<size_t>(std::max<size_t>(1, n_pix / 4096), 64); }
+// a device buffer of an engine set that lives until the set is destroyed (engine.hpp: d_audit, d_offenders), grown on demand
+float *set_buffer(float *&p, size_t &cap, size_t bytes)
+{
+    if (cap >= bytes) return p;
+    if (p) { hipFree(p); p = nullptr; cap = 0; }
+    void *q = nullptr;
+    const hipError_t e = device_malloc(&q, bytes);
+    if (e != hipSuccess) { char b[128]; snprintf(b, sizeof b, "device buffer of %zu bytes: %s", bytes, hipGetErrorString(e)); throw HipFailure(b); }
+    p = (float *) q; cap = bytes;
+    poison_alloc(q, bytes);
+    return p;
+}
+// report[f] for the n frames d_d against d_x (device, [n][n_pix], any 4-byte alignment), counting |x - d| > bound[f] (host, may
+// be null) -> 0, or 2 when a frame of d_x holds a NaN or an Inf.  Two launches, the bounds up and the records down per 4096
+// frames, on ctx's stream, which is waited for.  Device current, the context the caller's alone.
+int frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n, size_t n_pix, const float *bound, ebcc_hip_frame_error *report)
+{
+    constexpr size_t kFrames = 4096;
+    const unsigned pieces = frame_error_pieces(n_pix);
+    const size_t most = std::min(n, kFrames), need = most * ((pieces + 1) * sizeof(ErrRecord) + sizeof(float));
+    if (ctx->errs_cap < need) {
+        if (ctx->d_errs) { hipFree(ctx->d_errs); ctx->d_errs = nullptr; }
+        if (ctx->h_errs) { hipHostFree(ctx->h_errs); ctx->h_errs = nullptr; }
+        ctx->errs_cap = 0;
+        EBCC_HIP_CHECK(hipHostMalloc(&ctx->h_errs, need));
+        EBCC_HIP_CHECK(device_malloc(&ctx->d_errs, need));
+        ctx->errs_cap = need;
+    }
+    ErrRecord *d_part = (ErrRecord *) ctx->d_errs, *d_res = d_part + most * pieces, *h_res = (ErrRecord *) ctx->h_errs;
+    float *d_bound = (float *) (d_res + most), *h_bound = (float *) (h_res + most);
+    int rc = 0;
+    for (size_t lo = 0; lo < n; lo += kFrames) {
+        const size_t m = std::min(kFrames, n - lo);
+        if (bound) {
+            memcpy(h_bound, bound + lo, m * sizeof(float));
+            EBCC_HIP_CHECK(hipMemcpyAsync(d_bound, h_bound, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        }
+        {
+            ScopedTiming timing("frame_errors", ctx->stream);
+            hipLaunchKernelGGL(k_frame_errors, dim3(pieces, (unsigned) m), dim3(256), 0, ctx->stream, d_x + lo * n_pix, d_d + lo * n_pix, n_pix,
+                               bound ? (const float *) d_bound : nullptr, d_part);
+            hipLaunchKernelGGL(k_frame_errors_fold, dim3((unsigned) ((m + 63) / 64)), dim3(64), 0, ctx->stream, (const ErrRecord *) d_part, pieces, (unsigned) m, d_res);
+        }
+        EBCC_HIP_LAUNCH_CHECK();
+        EBCC_HIP_CHECK(hipMemcpyAsync(h_res, d_res, m * sizeof(ErrRecord), hipMemcpyDeviceToHost, ctx->stream));
+        wait_stream(ctx->stream);
+        for (size_t f = 0; f < m; f++) {
+            const ErrRecord &r = h_res[f];
+            if (r.bad) rc = 2;
+            report[lo + f] = ebcc_hip_frame_error{u2f((uint32_t) (r.key >> 32)), ~(uint32_t) r.key, r.n_over, r.sum, r.sum_sq,
+                                                  float_of_order_key(r.kmin), float_of_order_key(r.kmax)};
+        }
+    }
+    return rc;
+}
+
 // Where the chunks of an encode call lie: runs of chunks, each contiguous in (device or host) memory - one run for an
 // array, one per frame group unless the groups' arrays happen to follow one another.  The cuts of batches and slices fall
 // where they fall: each(lo, cnt, ...) visits the parts of the runs that make up chunks [lo, lo + cnt).
@@ -688,11 +826,18 @@ struct TwoSets {
 // GPU phase, the next enters it when every slice of the current one has reached its entropy stage (GpuPhase / PhaseNote).
 // stage(set, first frame, count) -> where the batch's frames are on the device (a host array is uploaded there: that copy
 // runs beside the other batch's kernels too).  fc: a config per frame; a batch takes its part of it with its frames.
-template <class Stage>
-int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const FrameConfig *fc, uint8_t **outs, size_t *sizes, Stage stage)
+// after(set, where, first frame, count, phase), if given, runs on the batch's thread once its streams are made, before the set
+// takes its next batch - the frames are still at `where` (the hard-bound loop, harden_batch; its status is the batch's).
+template <class Stage, class After = std::nullptr_t>
+int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const FrameConfig *fc, uint8_t **outs, size_t *sizes, Stage stage, After after = nullptr)
 {
     const size_t cap = ctx->max_frames, batches = (n_frames + cap - 1) / cap;
-    if (batches == 1) return run_encode_slices(ctx, stage(ctx, (size_t) 0, n_frames), n_frames, fc, outs, sizes);
+    auto one_batch = [&](ebcc_hip_ctx *set, const float *where, size_t lo, size_t cnt, GpuPhase *ph) {
+        int r = run_encode_slices(set, where, cnt, fc + lo, outs + lo, sizes + lo, ph);
+        if constexpr (!std::is_same<After, std::nullptr_t>::value) { if (!r) r = after(set, where, lo, cnt, ph); }
+        return r;
+    };
+    if (batches == 1) return one_batch(ctx, stage(ctx, (size_t) 0, n_frames), 0, n_frames, nullptr);
     TwoSets two(ctx);
     GpuPhase phase;
     std::atomic<size_t> next{0};
@@ -721,7 +866,7 @@ int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const FrameCo
                 for (size_t r = next++; r < batches; r = next++) redo.push_back(r);
                 return;
             }
-            two.note(t, run_encode_slices(two.set[t], where, cnt, fc + lo, outs + lo, sizes + lo, &phase));
+            two.note(t, one_batch(two.set[t], where, lo, cnt, &phase));
         }
     };
     two.both(work);
@@ -749,6 +894,95 @@ int decode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, Each each)
 }
 
 // ================================================================================================
+// hard error bound: a batch's streams audited on the device, the frames over their bound coded again
+// ================================================================================================
+// The encoder's bound is soft: it holds on the reconstruction the search looked at, before the mean error is folded into the
+// header's min / max (/root/reference/src/ebcc_codec.c:863-868), and a search that could not reach the target only warns.  A
+// batch is made hard before its streams leave it (include/ebcc_hip.h): its streams are decoded as any reader decodes them,
+// k_frame_errors measures a = max |x - x^| per frame against the frames where the batch read them, and a frame with a > T -
+// T: the config's error, times the frame's own range for RELATIVE_ERROR, in float as the encoder multiplies it - is coded
+// again with the error e' = (e * (T / a)) * 0.9f, same mode and rate, until it is met, max_rounds re-encodes are spent, or e'
+// is 0 or no longer below e.  Only a round's offenders run: their frames as FrameSource runs (adjacent ones where they lie,
+// scattered ones copied side by side into the set's offenders buffer), a FrameConfig each.  A frame that ends not met keeps
+// the stream of the round with the smallest a, the earliest on ties.  Every stream is what the plain call gives for some error.
+constexpr float kHardShrink = 0.9f;                                // (design constants, DESIGN 2.8: with 0.99 a frame can stall)
+constexpr int kHardRounds = 6;
+struct HardBound { int max_rounds; ebcc_hip_bound_report *report; };           // report: one entry per frame of the call
+struct OwnedStreams {                                              // a round's new streams until a frame takes its own over
+    std::vector<uint8_t *> p;
+    std::vector<size_t> n;
+    explicit OwnedStreams(size_t m) : p(m, nullptr), n(m, 0) {}
+    ~OwnedStreams() { for (uint8_t *q : p) free(q); }
+};
+int harden_batch(ebcc_hip_ctx *set, const float *where, size_t cnt, const FrameConfig *fc, uint8_t **outs, size_t *sizes, int max_rounds,
+                 ebcc_hip_bound_report *report, GpuPhase *phase)
+{
+    const size_t n_pix = set->n_pix;
+    if (max_rounds <= 0) max_rounds = kHardRounds;
+    for (size_t f = 0; f < cnt; f++) report[f] = ebcc_hip_bound_report{INFINITY, 0.0f, fc[f].error, 0, 1};
+    if (std::none_of(fc, fc + cnt, [](const FrameConfig &c) { return c.searching(); })) return 0;
+    PhaseTimer pt;
+    float *dec = set_buffer(set->d_audit, set->audit_cap, set->max_frames * n_pix * sizeof(float));
+    std::vector<ebcc_hip_frame_error> errs(cnt);
+    if (const int rc = run_decode_slices(set, outs, sizes, cnt, dec)) return rc;
+    frame_errors(set, where, dec, cnt, n_pix, nullptr, errs.data());
+    pt.mark("hard bound: audit");
+    struct Offender { size_t f; float e; };
+    std::vector<Offender> live, next;
+    // what a frame over its bound is coded with next; false: it stops as not met
+    auto shrink = [](float e, float T, float a, float *to) { *to = (e * (T / a)) * kHardShrink; return *to != 0.0f && *to < e; };
+    for (size_t f = 0; f < cnt; f++) {
+        ebcc_hip_bound_report &R = report[f];
+        R.achieved = errs[f].max_abs;
+        if (!fc[f].searching()) continue;
+        R.target = fc[f].mode == RELATIVE_ERROR ? fc[f].error * (errs[f].x_max - errs[f].x_min) : fc[f].error;
+        R.met = R.achieved <= R.target;
+        float e;
+        if (!R.met && shrink(fc[f].error, R.target, R.achieved, &e)) live.push_back(Offender{f, e});
+    }
+    for (int k = 1; !live.empty(); k++, live.swap(next), next.clear()) {
+        const size_t m = live.size();
+        FrameSource src;
+        std::vector<FrameConfig> cfg(m);
+        for (size_t i = 0; i < m; i++) {
+            src.add(where + live[i].f * n_pix, 1, n_pix);
+            cfg[i] = fc[live[i].f];
+            cfg[i].error = live[i].e;
+        }
+        const float *xs = src.in_place(0, m, n_pix);
+        if (!xs) {
+            float *side = set_buffer(set->d_offenders, set->offenders_cap, m * n_pix * sizeof(float));
+            src.each(0, m, n_pix, [&](const float *p, size_t at, size_t run) {
+                EBCC_HIP_CHECK(hipMemcpyAsync(side + at * n_pix, p, run * n_pix * sizeof(float), hipMemcpyDeviceToDevice, set->stream));
+            });
+            wait_stream(set->stream);
+            xs = side;
+        }
+        OwnedStreams made(m);
+        if (const int rc = run_encode_slices(set, xs, m, cfg.data(), made.p.data(), made.n.data(), phase)) return rc;
+        if (const int rc = run_decode_slices(set, made.p.data(), made.n.data(), m, dec)) return rc;
+        errs.resize(m);
+        frame_errors(set, xs, dec, m, n_pix, nullptr, errs.data());
+        for (size_t i = 0; i < m; i++) {
+            const size_t f = live[i].f;
+            ebcc_hip_bound_report &R = report[f];
+            const float a = errs[i].max_abs;
+            R.rounds = k;
+            if (a < R.achieved) {
+                std::swap(outs[f], made.p[i]);                           // (the stream it had is freed with the round's)
+                sizes[f] = made.n[i];
+                R.achieved = a; R.error_used = live[i].e;
+            }
+            R.met = a <= R.target;
+            float e;
+            if (!R.met && k < max_rounds && shrink(live[i].e, R.target, a, &e)) next.push_back(Offender{f, e});
+        }
+        pt.mark("hard bound: round");
+    }
+    return 0;
+}
+
+// ================================================================================================
 // frames in pageable host memory <-> streams
 // ================================================================================================
 // The chunks of `src` (FrameSource: runs in host memory), `tiles` frames each (tiles > 1: rc is the engine of the stacked chunk
@@ -757,7 +991,7 @@ int decode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, Each each)
 // 7.1 against 6.5).  One-frame chunks in batches that fill the engine run on the alternating sets, anything else batch
 // after batch.  0 ok, 1 error, 2 NaN / Inf in the data.
 int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t cap, const FrameSource &src, const FrameConfig *fc,
-                     uint8_t **outs, size_t *sizes)
+                     uint8_t **outs, size_t *sizes, const HardBound *hard = nullptr)
 {
     const size_t n_pix = ctx->n_pix * tiles, n = src.total;
     PhaseTimer pt[2];                                               // (one per engine set: each has its own thread)
@@ -769,6 +1003,10 @@ int encode_from_host(ebcc_hip_ctx *ctx, ebcc_hip_ctx *rc, size_t tiles, size_t c
         pt[set != ctx].mark("host frames: upload");
         return (const float *) d;
     };
+    // (hard: the batch is audited against its image in the set's staging buffer, where its offenders are coded again from)
+    if (hard) return encode_batches_alternating(ctx, n, fc, outs, sizes, stage, [&](ebcc_hip_ctx *set, const float *where, size_t lo, size_t cnt, GpuPhase *ph) {
+        return harden_batch(set, where, cnt, fc + lo, outs + lo, sizes + lo, hard->max_rounds, hard->report + lo, ph);
+    });
     if (tiles == 1 && ctx->max_frames == cap) return encode_batches_alternating(ctx, n, fc, outs, sizes, stage);
     for (size_t lo = 0; lo < n; lo += cap) {
         const size_t k = std::min(cap, n - lo);
@@ -932,11 +1170,11 @@ int encode_call(const char *who, ebcc_hip_ctx *ctx, const void *frames, size_t n
 // batch whose frames are adjacent in memory is coded where it lies; otherwise its runs are brought into the engine set's
 // staging buffer, one device-to-device copy per run on that set's stream, and the stage waits for them (the slices read
 // them on streams of their own) - as the container stage does with the chunks it gathers.
-int encode_device_frames(ebcc_hip_ctx *ctx, const FrameSource &src, const FrameConfig *fc, uint8_t **outs, size_t *sizes)
+int encode_device_frames(ebcc_hip_ctx *ctx, const FrameSource &src, const FrameConfig *fc, uint8_t **outs, size_t *sizes, const HardBound *hard = nullptr)
 {
     const size_t n_pix = ctx->n_pix, cap = std::min(src.total, ctx->max_frames);
     PhaseTimer pt[2];
-    return encode_batches_alternating(ctx, src.total, fc, outs, sizes, [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
+    auto stage = [&](ebcc_hip_ctx *set, size_t lo, size_t cnt) {
         if (const float *where = src.in_place(lo, cnt, n_pix)) return where;
         float *d = io_buffer(set, cap * n_pix * sizeof(float));
         src.each(lo, cnt, n_pix, [&](const float *p, size_t at, size_t k) {
@@ -945,6 +1183,10 @@ int encode_device_frames(ebcc_hip_ctx *ctx, const FrameSource &src, const FrameC
         wait_stream(set->stream);
         pt[set != ctx].mark("frame groups: runs copied");
         return (const float *) d;
+    };
+    if (!hard) return encode_batches_alternating(ctx, src.total, fc, outs, sizes, stage);
+    return encode_batches_alternating(ctx, src.total, fc, outs, sizes, stage, [&](ebcc_hip_ctx *set, const float *where, size_t lo, size_t cnt, GpuPhase *ph) {
+        return harden_batch(set, where, cnt, fc + lo, outs + lo, sizes + lo, hard->max_rounds, hard->report + lo, ph);
     });
 }
 int encode_resident(const char *who, ebcc_hip_ctx *ctx, const float *d_frames, size_t n, const codec_config_t *cfg, uint8_t **outs, size_t *sizes)
@@ -984,8 +1226,9 @@ enum class GroupForm { Frames, Shard, Host };
 // forms), a scan on the host pool (host form: nothing extra is uploaded) - restated as MAX_ERROR with error * (max - min) in
 // host float arithmetic as ebcc_encode_chunking_compat does (:1078-1087), and the frames of all groups as one list with a
 // config each.  NaN / Inf: 2 with the group named - before anything is coded for a group range, else when a batch meets it.
+// hard: the batches are made hard (harden_batch) and the call returns 3 when every frame is coded but some are not met.
 int encode_groups(const char *who, ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, uint8_t **outs, size_t *sizes,
-                  GroupForm form)
+                  GroupForm form, const HardBound *hard = nullptr)
 {
     if (!ctx || !outs || !sizes) { set_error("%s: bad arguments", who); return 1; }
     if (ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
@@ -1022,7 +1265,14 @@ int encode_groups(const char *who, ebcc_hip_ctx *ctx, const ebcc_hip_frame_group
         set_error("%s: NaN or Inf found in the data of group %zu", who, g);
         return 2;
     };
-    return encode_checked(ctx, total, outs, sizes, [&] {
+    std::vector<ebcc_hip_bound_report> own_report;
+    HardBound bound{0, nullptr};
+    if (hard) {
+        bound = *hard;
+        if (!bound.report) { own_report.resize(total); bound.report = own_report.data(); }
+        hard = &bound;
+    }
+    const int status = encode_checked(ctx, total, outs, sizes, [&] {
         if (!ranged.empty()) {
             const std::vector<unsigned> keys = range_keys(ranged);
             for (size_t i = 0; i < ranged.size(); i++) if (keys[3 * i + 2]) return nonfinite(ranged[i]);
@@ -1034,8 +1284,8 @@ int encode_groups(const char *who, ebcc_hip_ctx *ctx, const ebcc_hip_frame_group
                 std::fill_n(fc.begin() + first[ranged[i]], G.n_frames, c);
             }
         }
-        const int rc = form == GroupForm::Host ? encode_from_host(ctx, nullptr, 1, ctx->max_frames, src, fc.data(), outs, sizes)
-                                               : encode_device_frames(ctx, src, fc.data(), outs, sizes);
+        const int rc = form == GroupForm::Host ? encode_from_host(ctx, nullptr, 1, ctx->max_frames, src, fc.data(), outs, sizes, hard)
+                                               : encode_device_frames(ctx, src, fc.data(), outs, sizes, hard);
         if (rc == 2) {                                              // (a batch met it: which group was it)
             const std::vector<unsigned> keys = range_keys(all);
             for (size_t g = 0; g < n_groups; g++) if (keys[3 * g + 2]) return nonfinite(g);
@@ -1043,6 +1293,10 @@ int encode_groups(const char *who, ebcc_hip_ctx *ctx, const ebcc_hip_frame_group
         }
         return rc;
     });
+    if (status || !hard) return status;
+    const size_t missed = (size_t) std::count_if(bound.report, bound.report + total, [](const ebcc_hip_bound_report &r) { return !r.met; });
+    if (missed) { set_error("%s: %zu of %zu frames are coded but not within their bound", who, missed, total); return 3; }
+    return 0;
 }
 
 // The list of a list entry point, as the call it stands for: the streams of the frames the boxes name, in their order, with the
@@ -1125,6 +1379,42 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     if (!j2k_boxes_as_placed(who, boxes, n_boxes, rows, cols, placed, &out_floats)) return 1;
     const DecodeRegion region = DecodeRegion::placed_list(placed.data(), placed.size(), out_floats);
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
+}
+
+// ---- audit: the error of what the streams decode to, against the originals, measured on the device
+// The streams run through the full decode (decode_call's checks, batches on the two sets, each as its slices) into the set's
+// audit buffer - no decoded frame reaches the caller - and k_frame_errors takes each batch against the originals: where they lie
+// on the device, or uploaded batch by batch into the set's staging buffer.  NaN / Inf in the originals: the other frames are
+// still reported, the call returns 2.
+enum class AuditForm { Frames, Shard, Host };
+int audit(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *originals,
+          const float *bound, ebcc_hip_frame_error *report, AuditForm form)
+{
+    if (ctx && ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
+    if (ctx && (!report || ((uintptr_t) originals & 3))) { set_error("%s: bad arguments", who); return 1; }
+    return decode_call(who, ctx, streams, sizes, n_frames, originals, DecodeRegion{}, form == AuditForm::Frames,
+                       [&](const DecodeRegion &, const uint8_t *const *st, const size_t *sz, size_t n) {
+        const size_t n_pix = ctx->n_pix, cap = std::min(n, ctx->max_frames);
+        std::atomic<int> nonfinite{0};
+        const int rc = decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            PhaseTimer pt;
+            float *dec = set_buffer(set->d_audit, set->audit_cap, cap * n_pix * sizeof(float));
+            if (const int r = run_decode_slices(set, st + lo, sz + lo, k, dec)) return r;
+            pt.mark("audit: decode");
+            const float *x = originals + lo * n_pix;
+            if (form == AuditForm::Host) {
+                float *up = io_buffer(set, cap * n_pix * sizeof(float));
+                copy_pageable(set, const_cast<float *>(x), up, k * n_pix * sizeof(float), false);
+                pt.mark("audit: upload");
+                x = up;
+            }
+            if (frame_errors(set, x, dec, k, n_pix, bound ? bound + lo : nullptr, report + lo) == 2) nonfinite = 1;
+            pt.mark("audit: statistics");
+            return 0;
+        });
+        if (!rc && nonfinite.load()) { set_error("%s: NaN or Inf found in the originals", who); return 2; }
+        return rc;
+    });
 }
 
 // ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
@@ -1766,6 +2056,82 @@ int ebcc_hip_group_ranges(ebcc_hip_ctx *ctx, const float *const *d_ptrs, const s
         }
         return rc;
     });
+    EBCC_API_CATCH(1)
+}
+
+// ---- hard error bound (harden_batch above): the group entry points with the loop in every batch; one array is one group
+int ebcc_hip_encode_shard_groups_hard(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, int max_rounds, uint8_t **out_streams,
+                                      size_t *out_sizes, ebcc_hip_bound_report *report)
+{
+    EBCC_API_TRY
+    const HardBound hard{max_rounds, report};
+    return encode_groups("ebcc_hip_encode_shard_groups_hard", ctx, groups, n_groups, out_streams, out_sizes, GroupForm::Shard, &hard);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_encode_host_frames_groups_hard(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, int max_rounds,
+                                            uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report)
+{
+    EBCC_API_TRY
+    const HardBound hard{max_rounds, report};
+    return encode_groups("ebcc_hip_encode_host_frames_groups_hard", ctx, groups, n_groups, out_streams, out_sizes, GroupForm::Host, &hard);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_encode_shard_hard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *config, int max_rounds,
+                               uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report)
+{
+    EBCC_API_TRY
+    if (!config) { set_error("ebcc_hip_encode_shard_hard: bad arguments"); return 1; }
+    const ebcc_hip_frame_group one{d_frames, n_frames, *config, 0};
+    const HardBound hard{max_rounds, report};
+    return encode_groups("ebcc_hip_encode_shard_hard", ctx, &one, 1, out_streams, out_sizes, GroupForm::Shard, &hard);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_encode_host_frames_hard(ebcc_hip_ctx *ctx, const float *h_frames, size_t n_frames, const codec_config_t *config, int max_rounds,
+                                     uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report)
+{
+    EBCC_API_TRY
+    if (!config) { set_error("ebcc_hip_encode_host_frames_hard: bad arguments"); return 1; }
+    const ebcc_hip_frame_group one{h_frames, n_frames, *config, 0};
+    const HardBound hard{max_rounds, report};
+    return encode_groups("ebcc_hip_encode_host_frames_hard", ctx, &one, 1, out_streams, out_sizes, GroupForm::Host, &hard);
+    EBCC_API_CATCH(1)
+}
+
+// ---- audit (audit above): what the streams decode to against the originals, per frame
+int ebcc_hip_frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n_frames, size_t height, size_t width, const float *bound,
+                          ebcc_hip_frame_error *report)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_frame_errors";
+    size_t n_pix = 0;
+    if (!ctx || !d_x || !d_d || !report || n_frames < 1 || ((uintptr_t) d_x & 3) || ((uintptr_t) d_d & 3) || height < 1 || width < 1 ||
+        __builtin_mul_overflow(height, width, &n_pix) || n_pix > 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        const int rc = frame_errors(ctx, d_x, d_d, n_frames, n_pix, bound, report);
+        if (rc == 2) set_error("%s: NaN or Inf found in the originals", who);
+        return rc;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_audit_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *d_originals,
+                          const float *bound, ebcc_hip_frame_error *report)
+{
+    EBCC_API_TRY
+    return audit("ebcc_hip_audit_frames", ctx, streams, sizes, n_frames, d_originals, bound, report, AuditForm::Frames);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_audit_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *d_originals,
+                         const float *bound, ebcc_hip_frame_error *report)
+{
+    EBCC_API_TRY
+    return audit("ebcc_hip_audit_shard", ctx, streams, sizes, n_frames, d_originals, bound, report, AuditForm::Shard);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_audit_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *h_originals,
+                               const float *bound, ebcc_hip_frame_error *report)
+{
+    EBCC_API_TRY
+    return audit("ebcc_hip_audit_host_frames", ctx, streams, sizes, n_frames, h_originals, bound, report, AuditForm::Host);
     EBCC_API_CATCH(1)
 }
 

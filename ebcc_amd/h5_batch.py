@@ -45,6 +45,21 @@ class FrameGroup(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("n_frames", ctypes.c_size_t), ("config", CodecConfig), ("range_of_group", ctypes.c_int)]
 
 
+# ebcc_hip_frame_error and ebcc_hip_bound_report, include/ebcc_hip.h, as numpy record types
+FRAME_ERROR = np.dtype([("max_abs", "<f4"), ("at", "<u4"), ("n_over", "<u8"), ("sum", "<f8"), ("sum_sq", "<f8"), ("x_min", "<f4"), ("x_max", "<f4")])
+BOUND_REPORT = np.dtype([("target", "<f4"), ("achieved", "<f4"), ("error_used", "<f4"), ("rounds", "<i4"), ("met", "<i4")])
+assert FRAME_ERROR.itemsize == 40 and BOUND_REPORT.itemsize == 20
+
+
+class BoundNotMet(RuntimeError):
+    """A hard-bound write found frames that stay over their bound (return value 3 of the _hard entry points); `report` is
+    the BOUND_REPORT array of the call that found them.  Nothing of that call has been written."""
+
+    def __init__(self, message, report):
+        super().__init__(message)
+        self.report = report
+
+
 def _stream_arrays(streams, named=None):
     """(the streams as bytes - the caller keeps them alive for the call -, their ctypes pointer array, their size array);
     `named`: only the streams at these indices are read, the others (None allowed) become a null pointer of size 0"""
@@ -109,6 +124,12 @@ class BatchCodec:
                                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
         lib.ebcc_hip_encode_host_frames_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameGroup), ctypes.c_size_t,
                                                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        lib.ebcc_hip_encode_host_frames_hard.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(CodecConfig), ctypes.c_int,
+                                                         ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+        lib.ebcc_hip_encode_host_frames_groups_hard.argtypes = [ctypes.c_void_p, ctypes.POINTER(FrameGroup), ctypes.c_size_t, ctypes.c_int,
+                                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+        lib.ebcc_hip_audit_host_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                                   ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -130,29 +151,59 @@ class BatchCodec:
     def __exit__(self, *exc):
         self.close()
 
-    def encode(self, frames, cfg):
+    def encode(self, frames, cfg, hard=False, max_rounds=0):
         """frames: (n, H, W) float32 in host memory, any n -> list of EBCC frame streams (bytes).  More frames than the
         engine holds are coded in batches on two alternating engine sets (the host part of one batch beside the upload and
-        the kernels of the next)."""
+        the kernels of the next).  hard=True: every batch is audited on the device and the frames over their bound are coded
+        again with a smaller error, at most max_rounds times (0: 6) - ebcc_hip_encode_host_frames_hard; the result is then
+        (streams, report), report a BOUND_REPORT array with one record per frame (met == 0: still over its bound)."""
         frames = np.ascontiguousarray(frames, np.float32)
         n = frames.shape[0]
         assert frames.shape[1:] == (self.h, self.w) and n >= 1
         outs = (ctypes.c_void_p * n)()
         sizes = (ctypes.c_size_t * n)()
-        if self.lib.ebcc_hip_encode_host_frames(self.ctx, frames.ctypes.data, n, ctypes.byref(cfg), outs, sizes):
+        report = np.zeros(n, BOUND_REPORT)
+        if hard:
+            if self.lib.ebcc_hip_encode_host_frames_hard(self.ctx, frames.ctypes.data, n, ctypes.byref(cfg), int(max_rounds), outs, sizes,
+                                                         report.ctypes.data) not in (0, 3):
+                self._fail("ebcc_hip_encode_host_frames_hard")
+        elif self.lib.ebcc_hip_encode_host_frames(self.ctx, frames.ctypes.data, n, ctypes.byref(cfg), outs, sizes):
             self._fail("ebcc_hip_encode_host_frames")
         res = []
         for i in range(n):
             res.append(ctypes.string_at(outs[i], sizes[i]))
             self.lib.free_buffer(outs[i])
-        return res
+        return (res, report) if hard else res
 
-    def encode_groups(self, groups):
+    def audit(self, streams, frames, bound=None):
+        """What a reader of `streams` gets against the originals `frames` ((n, H, W) float32 in host memory, any n), measured on
+        the device -> a FRAME_ERROR array with one record per frame: max_abs and the pixel `at` which it occurs, n_over (pixels
+        with |x - x^| > bound[frame]; `bound`: a float or n floats, None: not counted), sum and sum_sq of x - x^, x_min and
+        x_max.  No decoded frame comes back.  ValueError for NaN / Inf in the originals, RuntimeError for what the decode
+        refuses."""
+        n = len(streams)
+        frames = np.ascontiguousarray(frames, np.float32)
+        if n < 1 or frames.shape != (n, self.h, self.w):
+            raise ValueError(f"{n} streams need originals of shape ({n}, {self.h}, {self.w}), got {frames.shape}")
+        streams, ptrs, sizes = _stream_arrays(streams)
+        b = None if bound is None else np.ascontiguousarray(np.broadcast_to(np.asarray(bound, np.float32), (n,)))
+        report = np.zeros(n, FRAME_ERROR)
+        rc = self.lib.ebcc_hip_audit_host_frames(self.ctx, ptrs, sizes, n, frames.ctypes.data, None if b is None else b.ctypes.data,
+                                                 report.ctypes.data)
+        if rc == 2:
+            raise ValueError("NaN or Inf in the originals")
+        if rc:
+            self._fail("ebcc_hip_audit_host_frames")
+        return report
+
+    def encode_groups(self, groups, hard=False, max_rounds=0):
         """Many variables in one device call: `groups` is a list of (frames, base_cr, residual_opt[, range_of_group]) - frames
         (n, H, W) float32 in host memory (each group its own array, any n), base_cr and residual_opt as for frame_config,
         range_of_group=True: a relative error target counts against (max - min) over the whole group, as
         ebcc_encode_chunking_compat restates it.  -> one list of EBCC frame streams (bytes) per group; every stream is what
-        encode() gives for that frame with the group's config.  All frames run as one list, in batches on the two engine sets."""
+        encode() gives for that frame with the group's config.  All frames run as one list, in batches on the two engine sets.
+        hard=True: as in encode(); the result is then (lists of streams, report) with one BOUND_REPORT record per frame, all
+        groups in order."""
         if not groups:
             raise ValueError("no groups")
         arrays, table = [], (FrameGroup * len(groups))()
@@ -168,7 +219,12 @@ class BatchCodec:
         total = sum(a.shape[0] for a in arrays)
         outs = (ctypes.c_void_p * total)()
         sizes = (ctypes.c_size_t * total)()
-        if self.lib.ebcc_hip_encode_host_frames_groups(self.ctx, table, len(groups), outs, sizes):
+        report = np.zeros(total, BOUND_REPORT)
+        if hard:
+            if self.lib.ebcc_hip_encode_host_frames_groups_hard(self.ctx, table, len(groups), int(max_rounds), outs, sizes,
+                                                                report.ctypes.data) not in (0, 3):
+                self._fail("ebcc_hip_encode_host_frames_groups_hard")
+        elif self.lib.ebcc_hip_encode_host_frames_groups(self.ctx, table, len(groups), outs, sizes):
             self._fail("ebcc_hip_encode_host_frames_groups")
         res, at = [], 0
         for a in arrays:
@@ -176,7 +232,7 @@ class BatchCodec:
             at += a.shape[0]
         for i in range(total):
             self.lib.free_buffer(outs[i])
-        return res
+        return (res, report) if hard else res
 
     def decode(self, streams, out=None, window=None):
         """list of EBCC frame streams (bytes), any number -> (n, H, W) float32; `out`: a C-contiguous float32 array to decode
@@ -311,9 +367,18 @@ def create_dataset(group, name, shape, base_cr, residual_opt=("none", None), **k
                                 **EBCC_Filter(base_cr=base_cr, height=h, width=w, residual_opt=residual_opt, data_dim=len(shape)), **kw)
 
 
-def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, codec=None):
+def _not_met(report, what):
+    missed = int((report["met"] == 0).sum())
+    if missed:
+        raise BoundNotMet(f"{what}: {missed} of {len(report)} frames stay over their bound "
+                          f"(worst {float((report['achieved'] / report['target']).max()):.4f} of it); nothing of this call was written", report)
+
+
+def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, codec=None, hard=False, max_rounds=0):
     """Code `data` (same shape as `dset`, frames in its last two axes) in device batches and store every frame
-    as a pre-filtered chunk.  `base_cr` / `residual_opt` must be the dataset's filter parameters."""
+    as a pre-filtered chunk.  `base_cr` / `residual_opt` must be the dataset's filter parameters.  hard=True: the chunks hold
+    their bound for every reader (BatchCodec.encode(hard=True)); returns the BOUND_REPORT array, shaped as the leading axes,
+    and raises BoundNotMet - before the frames of that device call are stored - when a frame stays over its bound."""
     data = np.asarray(data, np.float32)
     assert tuple(data.shape) == tuple(dset.shape) and dset.chunks == (1,) * (data.ndim - 2) + data.shape[-2:]
     h, w = data.shape[-2:]
@@ -322,11 +387,18 @@ def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, co
     cfg = frame_config(h, w, base_cr, residual_opt)
     codec = codec or cached_codec(h, w, min(batch, len(flat)))
     step = _SUPER * codec.max_frames                            # (several batches per call: they alternate between two engine sets)
+    reports = []
     for lo in range(0, len(flat), step):
-        streams = codec.encode(flat[lo:lo + step], cfg)
+        if hard:
+            streams, report = codec.encode(flat[lo:lo + step], cfg, hard=True, max_rounds=max_rounds)
+            _not_met(report, f"{dset.name}, frames {lo}..{lo + len(report) - 1}")
+            reports.append(report)
+        else:
+            streams = codec.encode(flat[lo:lo + step], cfg)
         for i, s in enumerate(streams):
             idx = np.unravel_index(lo + i, lead) if lead else ()
             dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
+    return np.concatenate(reports).reshape(tuple(lead)) if hard else None
 
 
 def filter_options(dset):
@@ -346,12 +418,13 @@ def filter_options(dset):
     raise ValueError(f"{dset.name}: not an EBCC-filtered dataset")
 
 
-def write_variables(items, batch=256, codec=None):
+def write_variables(items, batch=256, codec=None, hard=False, max_rounds=0):
     """Several variables in one device call: `items` is a list of (dset, first_frame, frames) over one-frame-per-chunk
     EBCC-filtered datasets of one frame geometry - frames (n, H, W) float32 go to the chunks first_frame .. first_frame + n - 1
     of dset, counted in C order over its leading axes.  Every dataset's own filter-308 parameters are its group's config
     (filter_options), all groups are coded by one BatchCodec.encode_groups call, then every chunk is stored pre-filtered.
-    The chunk bytes are those write_frames gives dataset by dataset."""
+    The chunk bytes are those write_frames gives dataset by dataset.  hard=True: as in write_frames; returns one BOUND_REPORT
+    array per item and raises BoundNotMet, with nothing stored, when a frame stays over its bound."""
     if not items:
         raise ValueError("no items")
     h, w = items[0][0].shape[-2:]
@@ -368,11 +441,48 @@ def write_variables(items, batch=256, codec=None):
         groups.append((frames, base_cr, opt))
         total += len(frames)
     codec = codec or cached_codec(h, w, min(batch, total))
-    for (dset, first, _), streams in zip(items, codec.encode_groups(groups)):
+    report = None
+    if hard:
+        coded, report = codec.encode_groups(groups, hard=True, max_rounds=max_rounds)
+        _not_met(report, "write_variables")
+    else:
+        coded = codec.encode_groups(groups)
+    for (dset, first, _), streams in zip(items, coded):
         lead = dset.shape[:-2]
         for i, s in enumerate(streams):
             idx = np.unravel_index(first + i, lead) if lead else ()
             dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
+    if hard:
+        cuts = np.cumsum([len(g[0]) for g in groups])[:-1]
+        return np.split(report, cuts)
+
+
+def audit_dataset(dset, data, batch=256, codec=None):
+    """The error of an EBCC-filtered one-frame-per-chunk dataset against `data` (same shape), measured on the device: the raw
+    chunks are fetched as read_frames fetches them and audited (BatchCodec.audit) against the dataset's own filter bound - the
+    error of a max_error_target, error * (max - min) of the frame for a relative_error_target in float32 as the encoder
+    multiplies it, none for a dataset without a residual layer -> a FRAME_ERROR array shaped as the leading axes; a frame
+    holds its bound where n_over == 0."""
+    data = np.asarray(data, np.float32)
+    if tuple(data.shape) != tuple(dset.shape):
+        raise ValueError(f"{dset.name}: data of shape {data.shape} against a dataset of {dset.shape}")
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    flat = data.reshape((-1, h, w))
+    n = len(flat)
+    _base_cr, (mode, err) = filter_options(dset)
+    codec = codec or cached_codec(h, w, min(batch, n))
+    step = _SUPER * codec.max_frames
+    out = np.zeros(n, FRAME_ERROR)
+    for lo in range(0, n, step):
+        part = flat[lo:lo + step]
+        bound = None
+        if mode == "max_error_target":
+            bound = np.float32(err)
+        elif mode == "relative_error_target":
+            bound = np.float32(err) * (part.max(axis=(1, 2)) - part.min(axis=(1, 2))).astype(np.float32)
+        out[lo:lo + len(part)] = codec.audit(_read_chunks(dset, range(lo, lo + len(part))), part, bound)
+    return out.reshape(tuple(lead))
 
 
 def _box(sl, n, what):

@@ -354,6 +354,71 @@ int ebcc_hip_group_ranges(ebcc_hip_ctx *ctx, const float *const *d_ptrs, const s
  * in the frames form a total beyond the capacity.) */
 long ebcc_hip_groups_check(size_t height, size_t width, const ebcc_hip_frame_group *groups, size_t n_groups);
 
+/* ---- audit: the achieved error, measured on the device ---------------------------------------------------
+ * The encoder's bound is soft.  ebcc_encode checks max |x - x^| <= target on the reconstruction its search looked at and then folds
+ * the mean error into the header's min / max (/root/reference/src/ebcc_codec.c:863-868), which shifts every decoded sample; a
+ * search that could not reach the target only logs a warning.  These calls say what a reader of the streams gets: the streams
+ * are decoded by the full decode into a buffer of the engine set (made on first use, freed with the set; no decoded frame
+ * reaches the caller) and compared with the originals, which are never written.  Per frame: */
+typedef struct {
+    float    max_abs;   /* max fabsf(x - x^), float arithmetic */
+    uint32_t at;        /* the smallest pixel index (row * width + column) where it occurs */
+    uint64_t n_over;    /* pixels with fabsf(x - x^) > bound[frame]; 0 without bounds */
+    double   sum;       /* sum of (x - x^) and of (x - x^)^2, differences and sums in double */
+    double   sum_sq;
+    float    x_min;     /* range of the original (-0 counts as +0) */
+    float    x_max;
+} ebcc_hip_frame_error;
+/* The report is the same bytes from run to run and whatever the batch size, the slices, the engine sets and the alignment of
+ * the arrays: no atomics, a fixed order of every sum (ebcc_amd/csrc/host_codec.hip: k_frame_errors).  `bound`: host, one float per
+ * frame, may be NULL.  Return 0 = ok, 1 = error (streams are refused exactly as ebcc_hip_decode_frames refuses them), 2 = NaN /
+ * Inf in the originals (the frames without one are still reported).  One-frame chunks only.
+ * unit level, the kernel alone: n_frames frames of height x width at d_x (originals) and d_d (decoded), each at any 4-byte
+ * aligned device address; ctx: any context of the device */
+int ebcc_hip_frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n_frames, size_t height, size_t width,
+                          const float *bound, ebcc_hip_frame_error *report);
+/* at most the context's capacity of frames, originals on the device */
+int ebcc_hip_audit_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *d_originals,
+                          const float *bound, ebcc_hip_frame_error *report);
+/* any number of frames, batches on the two engine sets */
+int ebcc_hip_audit_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *d_originals,
+                         const float *bound, ebcc_hip_frame_error *report);
+/* originals in pageable host memory, uploaded batch by batch through the staged upload */
+int ebcc_hip_audit_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const float *h_originals,
+                               const float *bound, ebcc_hip_frame_error *report);
+
+/* ---- hard error bound ---------------------------------------------------------------------------------
+ * Encode calls whose streams hold their bound for every reader: a batch is audited before its streams leave it, and the frames
+ * over their bound are coded again with a smaller error.  Per frame of mode MAX_ERROR or RELATIVE_ERROR, all in float:
+ *   T   = error (MAX_ERROR; also the restated bound of a group with range_of_group), error * (x_max - x_min) (RELATIVE_ERROR)
+ *   e_0 = error; round k codes the frame with e_k (same mode, same base_cr) and audits that stream: a_k = max_abs
+ *   a_k <= T: the frame is met.  Else e_{k+1} = (e_k * (T / a_k)) * 0.9f, and the frame stops as not met when k == max_rounds
+ *   (0 means 6) or e_{k+1} is 0 or not below e_k; it then keeps the stream of the round with the smallest a_k, the earliest on ties.
+ * Only the offenders of a round are coded again, and the loop runs inside a batch's turn on its engine set: the next batch
+ * still runs on the other set, and host frames are still in the set's staging buffer.  Every stream is byte for byte what the
+ * plain call gives for the error in error_used; with no offenders the streams are those of the plain call.  NONE-mode frames
+ * are never coded again: target = +inf, met = 1, rounds = 0 (achieved is still measured).
+ * Return 0 = every frame met, 3 = every frame coded and valid but some not met (report says which), 1 / 2 as the plain calls,
+ * with every stream freed.  report: one entry per frame in stream order, may be NULL.  One-frame chunks only.
+ * Not covered: chunks of several frames, ebcc_hip_encode_container / ebcc_hip_encode_array_chunks, the reference-compatible entry
+ * points and the filter callback, an audit of windows or boxes. */
+typedef struct {
+    float target;       /* T */
+    float achieved;     /* max_abs of the stream the frame keeps */
+    float error_used;   /* the error that stream was coded with */
+    int   rounds;       /* re-encodes run for the frame */
+    int   met;          /* achieved <= target */
+} ebcc_hip_bound_report;
+int ebcc_hip_encode_shard_groups_hard(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, int max_rounds,
+                                      uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report);
+int ebcc_hip_encode_host_frames_groups_hard(ebcc_hip_ctx *ctx, const ebcc_hip_frame_group *groups, size_t n_groups, int max_rounds,
+                                            uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report);
+/* one array, one config (one group) */
+int ebcc_hip_encode_shard_hard(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const codec_config_t *config, int max_rounds,
+                               uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report);
+int ebcc_hip_encode_host_frames_hard(ebcc_hip_ctx *ctx, const float *h_frames, size_t n_frames, const codec_config_t *config, int max_rounds,
+                                     uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -393,7 +458,7 @@ int ebcc_hip_selfcheck(void);
 void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4]);
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
- * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode".  Process-wide switch. */
+ * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
