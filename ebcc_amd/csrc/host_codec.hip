@@ -2,7 +2,7 @@
 // frame geometry, concurrent slices and alternating engine sets of a batch, host <-> device copies, the EBCK chunk
 // container (/root/reference/src/ebcc_codec.c:920-1090, :1322-1449), and the batch entry points of include/ebcc_hip.h.
 // A few kernels live here, beside the host loops they stand for: the chunk gather, the range of an array (and of many) on the
-// device, and the per-frame error statistics of the audit and the hard-bound encode.
+// device, the per-frame error statistics of the audit and the hard-bound encode, and the fold over time of the reduce decode.
 // The frame codec itself is batch_codec.hip, the HDF5 plugin h5z_filter.hip, the host services host_pool.hip (host.hpp).
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <climits>
@@ -627,6 +627,157 @@ int frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n
         }
     }
     return rc;
+}
+
+// Statistics over time (include/ebcc_hip.h: ebcc_hip_time_stats): the items [.][n_pix] that `list` names - (item, bin) pairs -
+// folded into the accumulators [n_bins][n_pix] of their bins.  A lane owns pixels and walks the list from its first entry to its
+// last, one item after the other: acc = acc + x, nothing else ever adds to a sample's accumulators, so for every bin and pixel
+// the order of the additions is the order of the list - frames never meet in a reduction tree, and there are no atomics.  The
+// lane keeps the current bin's accumulators in registers, writes them back and loads the other bin's only when the bin
+// changes; time_fold hands over the list grouped by bin (a stable sort: within a bin still in increasing item index, which is
+// all the order rule fixes), so a batch costs one load and one store of every bin it names.
+// A lane takes a quad (pixels 4q .. 4q + 3): one 16-byte load from an item that begins on a 16-byte boundary, four 4-byte loads
+// from one that does not, four items in flight; the accumulators of a bin the same way, each array on its own.  Quads count
+// from the item's first pixel, not from an address, and the last n_pix % 4 pixels go one to a lane - but which lane adds a
+// sample does not matter here: the additions of a pixel are one lane's, in list order, wherever the arrays lie.
+struct FoldAcc { double *sum, *sum_sq; float *mn, *mx; unsigned *over; float threshold; };
+struct FoldEntry { unsigned item, bin; };
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <class T> struct Vec16;                                   // the 16-byte vector of T
+template <> struct Vec16<double> { typedef f64x2 type; };
+template <> struct Vec16<float> { typedef f32x4 type; };
+template <> struct Vec16<unsigned> { typedef u32x4 type; };
+// W samples at p: as 16-byte accesses where W == 4 and p is on a 16-byte boundary (the same answer in every lane of a
+// workgroup's quads: they lie whole quads apart), else one by one
+template <class T, int W> __device__ inline void fold_get(const T *p, T (&r)[W])
+{
+    typedef typename Vec16<T>::type V;
+    constexpr int per = 16 / sizeof(T);
+    if constexpr (W == 4) {
+        if (((uintptr_t) p & 15) == 0) {
+#pragma unroll
+            for (int v = 0; v < W / per; v++) {
+                const V q = reinterpret_cast<const V *>(p)[v];
+#pragma unroll
+                for (int i = 0; i < per; i++) r[v * per + i] = q[i];
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < W; i++) r[i] = p[i];
+}
+template <class T, int W> __device__ inline void fold_put(T *p, const T (&r)[W])
+{
+    typedef typename Vec16<T>::type V;
+    constexpr int per = 16 / sizeof(T);
+    if constexpr (W == 4) {
+        if (((uintptr_t) p & 15) == 0) {
+#pragma unroll
+            for (int v = 0; v < W / per; v++) {
+                V q;
+#pragma unroll
+                for (int i = 0; i < per; i++) q[i] = r[v * per + i];
+                reinterpret_cast<V *>(p)[v] = q;
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < W; i++) p[i] = r[i];
+}
+// the pixels p0 .. p0 + W - 1 through the list
+template <int W>
+__device__ inline void time_fold_pixels(const float *__restrict__ items, size_t n_pix, size_t p0, const FoldEntry *__restrict__ list, unsigned m, const FoldAcc &a)
+{
+    constexpr unsigned kNone = 0xFFFFFFFFu;
+    constexpr int kDepth = 4;                                       // items in flight
+    double s[W], s2[W];
+    float lo[W], hi[W];
+    unsigned ov[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) { s[i] = 0.0; s2[i] = 0.0; lo[i] = 0.0f; hi[i] = 0.0f; ov[i] = 0u; }
+    unsigned cur = kNone;
+    auto get = [&](unsigned b) {
+        const size_t at = (size_t) b * n_pix + p0;
+        if (a.sum) fold_get<double, W>(a.sum + at, s);
+        if (a.sum_sq) fold_get<double, W>(a.sum_sq + at, s2);
+        if (a.mn) fold_get<float, W>(a.mn + at, lo);
+        if (a.mx) fold_get<float, W>(a.mx + at, hi);
+        if (a.over) fold_get<unsigned, W>(a.over + at, ov);
+    };
+    auto put = [&](unsigned b) {
+        const size_t at = (size_t) b * n_pix + p0;
+#pragma unroll
+        for (int i = 0; i < W; i++) { lo[i] = lo[i] + 0.0f; hi[i] = hi[i] + 0.0f; }      // (-0 -> +0)
+        if (a.sum) fold_put<double, W>(a.sum + at, s);
+        if (a.sum_sq) fold_put<double, W>(a.sum_sq + at, s2);
+        if (a.mn) fold_put<float, W>(a.mn + at, lo);
+        if (a.mx) fold_put<float, W>(a.mx + at, hi);
+        if (a.over) fold_put<unsigned, W>(a.over + at, ov);
+    };
+    for (unsigned j0 = 0; j0 < m; j0 += kDepth) {
+        float x[kDepth][W];
+#pragma unroll
+        for (int j = 0; j < kDepth; j++)
+            if (j0 + j < m) fold_get<float, W>(items + (size_t) list[j0 + j].item * n_pix + p0, x[j]);
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) {
+            if (j0 + j >= m) break;
+            const unsigned b = list[j0 + j].bin;
+            if (b != cur) {
+                if (cur != kNone) put(cur);
+                get(b);
+                cur = b;
+            }
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                const float v = x[j][i];
+                const double d = (double) v;
+                s[i] = s[i] + d;
+                s2[i] = s2[i] + d * d;
+                lo[i] = fminf(lo[i], v);
+                hi[i] = fmaxf(hi[i], v);
+                ov[i] += v > a.threshold ? 1u : 0u;
+            }
+        }
+    }
+    if (cur != kNone) put(cur);
+}
+// a lane per quad of an item, then a lane per pixel of the last n_pix % 4
+__global__ __launch_bounds__(256) void k_time_fold(const float *__restrict__ items, size_t n_pix, const FoldEntry *__restrict__ list, unsigned m, FoldAcc a)
+{
+    const size_t u = (size_t) blockIdx.x * blockDim.x + threadIdx.x, n4 = n_pix >> 2;
+    if (u < n4) time_fold_pixels<4>(items, n_pix, 4 * u, list, m, a);
+    else if (u - n4 < (n_pix & 3)) time_fold_pixels<1>(items, n_pix, 4 * n4 + (u - n4), list, m, a);
+}
+// The items of d_items [n][n_pix] (device, any 4-byte alignment) that `bin` names (host, null: all bin 0; EBCC_HIP_NO_BIN: the
+// item is not read) folded into st's accumulators, in index order within every bin.  The list goes up through the context's
+// pinned table (boxes_reserve), launches of at most kList entries follow one another on ctx's stream, which is waited for.
+// st.count is the caller's.  Device current, the context the caller's alone, st checked (time_stats_named).
+void time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n, size_t n_pix, const uint32_t *bin, const ebcc_hip_time_stats &st)
+{
+    constexpr size_t kList = 65536;
+    std::vector<FoldEntry> list;
+    list.reserve(n);
+    for (size_t k = 0; k < n; k++)
+        if (!bin || bin[k] != EBCC_HIP_NO_BIN) list.push_back(FoldEntry{(unsigned) k, bin ? bin[k] : 0u});
+    if (list.empty()) return;
+    std::stable_sort(list.begin(), list.end(), [](const FoldEntry &p, const FoldEntry &q) { return p.bin < q.bin; });
+    boxes_reserve(ctx, list.size(), sizeof(FoldEntry));
+    memcpy(ctx->h_boxes, list.data(), list.size() * sizeof(FoldEntry));
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_boxes, ctx->h_boxes, list.size() * sizeof(FoldEntry), hipMemcpyHostToDevice, ctx->stream));
+    const FoldAcc a{st.d_sum, st.d_sum_sq, st.d_min, st.d_max, st.d_over, st.threshold};
+    const size_t lanes = (n_pix >> 2) + (n_pix & 3);
+    {
+        ScopedTiming timing("time_fold", ctx->stream);
+        for (size_t lo = 0; lo < list.size(); lo += kList)
+            hipLaunchKernelGGL(k_time_fold, dim3((unsigned) ((lanes + 255) / 256)), dim3(256), 0, ctx->stream, d_items, n_pix,
+                               (const FoldEntry *) ctx->d_boxes + lo, (unsigned) std::min(kList, list.size() - lo), a);
+    }
+    EBCC_HIP_LAUNCH_CHECK();
+    wait_stream(ctx->stream);
 }
 
 // Where the chunks of an encode call lie: runs of chunks, each contiguous in (device or host) memory - one run for an
@@ -1417,6 +1568,143 @@ int audit(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, con
     });
 }
 
+// ---- reduce decode: statistics over time from the streams (include/ebcc_hip.h: ebcc_hip_time_stats; k_time_fold above)
+// What ebcc_hip_time_stats_check checks: the accumulators alone (time_stats_shape: also what ebcc_hip_time_stats_init needs),
+// then the window in a height x width frame and the bins -> the number of named frames, or -1 with the message set.
+bool time_stats_shape(const char *who, const ebcc_hip_time_stats *st)
+{
+    if (!st || !st->count) { set_error("%s: no statistics, or no count array", who); return false; }
+    if (st->n_bins < 1 || st->rows < 1 || st->cols < 1) { set_error("%s: n_bins, rows and cols must not be zero", who); return false; }
+    if (!st->d_sum && !st->d_sum_sq && !st->d_min && !st->d_max && !st->d_over) { set_error("%s: every accumulator is NULL", who); return false; }
+    if (((uintptr_t) st->d_sum & 7) || ((uintptr_t) st->d_sum_sq & 7)) { set_error("%s: d_sum and d_sum_sq must be 8-byte aligned", who); return false; }
+    if (((uintptr_t) st->d_min & 3) || ((uintptr_t) st->d_max & 3) || ((uintptr_t) st->d_over & 3)) {
+        set_error("%s: d_min, d_max and d_over must be 4-byte aligned", who);
+        return false;
+    }
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(st->rows, st->cols, &bytes) || __builtin_mul_overflow(bytes, st->n_bins, &bytes) ||
+        __builtin_mul_overflow(bytes, sizeof(double), &bytes)) { set_error("%s: the size of the accumulators overflows", who); return false; }
+    return true;
+}
+long time_stats_named(const char *who, size_t height, size_t width, const ebcc_hip_time_stats *st, const uint32_t *bin, size_t n_frames,
+                      size_t row0, size_t col0)
+{
+    if (!time_stats_shape(who, st)) return -1;
+    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("%s: unsupported geometry %zu x %zu", who, height, width); return -1; }
+    if (row0 >= height || col0 >= width || st->rows > height - row0 || st->cols > width - col0) {
+        set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is not inside the %zu x %zu frame", who, row0, st->rows, col0, st->cols, height, width);
+        return -1;
+    }
+    if (n_frames > (size_t) LONG_MAX) { set_error("%s: too many frames", who); return -1; }
+    size_t named = 0;
+    for (size_t f = 0; f < n_frames; f++) {
+        const uint32_t b = bin ? bin[f] : 0u;
+        if (b == EBCC_HIP_NO_BIN) continue;
+        if (b >= st->n_bins) { set_error("%s: frame %zu names bin %u of %zu", who, f, b, st->n_bins); return -1; }
+        named++;
+    }
+    if (!named) { set_error("%s: no frame is named", who); return -1; }
+    return (long) named;
+}
+
+// Whose turn it is to fold: batch b folds after batch b - 1 has passed its turn on, while the two sets decode side by side.
+// A batch passes its turn on when its iteration of the batch loop ends, however it ends (reduce_batches: a destructor), every
+// batch has an iteration - a loop that has seen a failure goes on and only passes -, and a thread that is left any other way
+// (TwoSets::run could not make the device current) says so: await returns when the batch before has passed OR its thread has
+// left.  The batches of a thread are in increasing order, so the thread batch b waits for is at a batch below b, which in turn
+// waits only for batches this thread is through with: no wait without someone on the way to end it, whatever fails.
+struct FoldTurn {
+    std::mutex m;
+    std::condition_variable cv;
+    std::vector<char> passed;
+    bool left[2] = {false, false};
+    explicit FoldTurn(size_t batches) : passed(batches, 0) {}
+    void await(size_t b, int other)
+    {
+        if (b == 0) return;
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return passed[b - 1] != 0 || left[other]; });
+    }
+    void pass(size_t b) { { std::lock_guard<std::mutex> l(m); passed[b] = 1; } cv.notify_all(); }
+    void leave(int t) { { std::lock_guard<std::mutex> l(m); left[t] = true; } cv.notify_all(); }
+};
+// n frames in batches of the context's capacity, the sets free-running on the odd and the even batches as in
+// decode_batches_alternating: decode(set, first frame, count) -> status, then - in batch order, and only while nothing has
+// failed - fold(set, first frame, count).
+template <class Decode, class Fold>
+int reduce_batches(ebcc_hip_ctx *ctx, size_t n, Decode decode, Fold fold)
+{
+    const size_t cap = ctx->max_frames, batches = (n + cap - 1) / cap;
+    if (batches == 1) {
+        if (const int r = decode(ctx, (size_t) 0, n)) return r;
+        fold(ctx, (size_t) 0, n);
+        return 0;
+    }
+    TwoSets two(ctx);
+    FoldTurn turn(batches);
+    auto work = [&](int t) {
+        for (size_t b = (size_t) t; b < batches; b += two.set[1] ? 2 : 1) {
+            struct Pass { FoldTurn &turn; size_t b; ~Pass() { turn.pass(b); } } pass{turn, b};      // whatever happens to the batch
+            if (two.failed()) continue;
+            try {
+                const size_t lo = b * cap, k = std::min(cap, n - lo);
+                const int r = decode(two.set[t], lo, k);
+                two.note(t, r);
+                if (r) continue;
+                turn.await(b, 1 - t);
+                if (!two.failed()) fold(two.set[t], lo, k);
+            } catch (const std::exception &e) { two.fail(t, 1, e.what()); }
+        }
+    };
+    if (!two.set[1]) two.run(0, work);
+    else {
+        std::thread second([&] { two.run(1, work); turn.leave(1); });
+        two.run(0, work);
+        turn.leave(0);
+        second.join();
+    }
+    return two.status();
+}
+
+int reduce_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                 size_t row0, size_t col0, const ebcc_hip_time_stats *stats)
+{
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    if (ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
+    const size_t H = (size_t) ctx->height, W = (size_t) ctx->width;
+    if (time_stats_named(who, H, W, stats, bin, n_frames, row0, col0) < 0) return 1;
+    if (!streams || !sizes) { set_error("%s: bad arguments", who); return 1; }
+    // the named frames as the call the decode sees; their headers are parsed before anything is written
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz;
+    std::vector<uint32_t> bn;
+    for (size_t f = 0; f < n_frames; f++) {
+        const uint32_t b = bin ? bin[f] : 0u;
+        if (b == EBCC_HIP_NO_BIN) continue;
+        ParsedFrame pf;
+        if (!streams[f] || !parse_frame(streams[f], sizes[f], pf)) { set_error("%s: frame %zu: not a frame stream", who, f); return 1; }
+        st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b);
+    }
+    const ebcc_hip_time_stats &S = *stats;
+    const size_t pix = S.rows * S.cols;
+    const DecodeRegion asked = S.rows == H && S.cols == W ? DecodeRegion{} : DecodeRegion::window(row0, col0, S.rows, S.cols);
+    return decode_call(who, ctx, st.data(), sz.data(), st.size(), stats, asked, false, [&](const DecodeRegion &region, const uint8_t *const *sp, const size_t *zp, size_t n) {
+        const size_t cap = std::min(n, ctx->max_frames);
+        PhaseTimer pt[2];
+        const int rc = reduce_batches(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            float *dec = set_buffer(set->d_audit, set->audit_cap, cap * pix * sizeof(float));
+            const int r = run_decode_slices(set, sp + lo, zp + lo, k, dec, region);
+            pt[set != ctx].mark("reduce: decode");
+            return r;
+        }, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            time_fold(set, set->d_audit, k, pix, bn.data() + lo, S);
+            pt[set != ctx].mark("reduce: fold");
+        });
+        if (!rc) for (const uint32_t b : bn) S.count[b]++;
+        return rc;
+    });
+}
+
 // ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
 // The container as ebcc_decode_chunking checks it: the header, then the chain of `u64 nbytes | stream` entries - of a chunk only
 // the length field is read.  parse: "" or what is wrong with it (the reference's messages).
@@ -2132,6 +2420,55 @@ int ebcc_hip_audit_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams,
 {
     EBCC_API_TRY
     return audit("ebcc_hip_audit_host_frames", ctx, streams, sizes, n_frames, h_originals, bound, report, AuditForm::Host);
+    EBCC_API_CATCH(1)
+}
+
+// ---- reduce decode (reduce_shard above): statistics over time, folded on the device
+long ebcc_hip_time_stats_check(size_t height, size_t width, const ebcc_hip_time_stats *stats, const uint32_t *bin, size_t n_frames, size_t row0,
+                               size_t col0)
+{
+    EBCC_API_TRY
+    return time_stats_named("ebcc_hip_time_stats_check", height, width, stats, bin, n_frames, row0, col0);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_time_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_time_stats_init";
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    if (!time_stats_shape(who, stats)) return 1;
+    return on_device(ctx->device, 1, [&] {
+        const size_t n = stats->n_bins * stats->rows * stats->cols;
+        if (stats->d_sum) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_sum, 0, n * sizeof(double), ctx->stream));
+        if (stats->d_sum_sq) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_sum_sq, 0, n * sizeof(double), ctx->stream));
+        if (stats->d_over) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_over, 0, n * sizeof(uint32_t), ctx->stream));
+        if (stats->d_min) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_min, (int) 0x7F800000u, n, ctx->stream));     // +inf
+        if (stats->d_max) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max, (int) 0xFF800000u, n, ctx->stream));     // -inf
+        wait_stream(ctx->stream);
+        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const ebcc_hip_time_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_time_fold";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
+    if (time_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0) < 0) return 1;
+    return on_device(ctx->device, 1, [&] {
+        time_fold(ctx, d_items, n_items, stats->rows * stats->cols, bin, *stats);
+        for (size_t k = 0; k < n_items; k++)
+            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_reduce_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin, size_t row0,
+                          size_t col0, const ebcc_hip_time_stats *stats)
+{
+    EBCC_API_TRY
+    return reduce_shard("ebcc_hip_reduce_shard", ctx, streams, sizes, n_frames, bin, row0, col0, stats);
     EBCC_API_CATCH(1)
 }
 

@@ -51,6 +51,92 @@ BOUND_REPORT = np.dtype([("target", "<f4"), ("achieved", "<f4"), ("error_used", 
 assert FRAME_ERROR.itemsize == 40 and BOUND_REPORT.itemsize == 20
 
 
+class TimeStats(ctypes.Structure):
+    """ebcc_hip_time_stats, include/ebcc_hip.h: per-pixel accumulators [n_bins][rows][cols] on the device, count on the host."""
+    _fields_ = [("n_bins", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t),
+                ("d_sum", ctypes.c_void_p), ("d_sum_sq", ctypes.c_void_p), ("d_min", ctypes.c_void_p), ("d_max", ctypes.c_void_p),
+                ("d_over", ctypes.c_void_p), ("threshold", ctypes.c_float), ("count", ctypes.c_void_p)]
+
+
+NO_BIN = 0xFFFFFFFF                                               # EBCC_HIP_NO_BIN
+
+
+class ReduceResult:
+    """Statistics over time, per bin and pixel: count (n_bins,) uint64 - the frames folded into each bin -, sum and sum_sq
+    (n_bins, rows, cols) float64, min and max float32, over uint32 (None without a threshold: the frames with sample >
+    threshold).  The sums are those of a loop over the frames in increasing index, acc = acc + x in float64.  mean and var
+    (the variance over the bin's frames, sum_sq / count - mean^2) are float64; a bin without frames gives NaN."""
+
+    def __init__(self, count, sum, sum_sq, min, max, over):       # noqa: A002
+        self.count, self.sum, self.sum_sq, self.min, self.max, self.over = count, sum, sum_sq, min, max, over
+
+    @property
+    def mean(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.sum / self.count.astype(np.float64)[:, None, None]
+
+    @property
+    def var(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = self.mean
+            return self.sum_sq / self.count.astype(np.float64)[:, None, None] - m * m
+
+
+class ReduceState:
+    """The accumulators of BatchCodec.reduce, resident on the device from call to call (BatchCodec.reduce_state makes one):
+    result() downloads them, close() frees them."""
+
+    def __init__(self, codec, n_bins, window, threshold):
+        self.codec, self.n_bins = codec, int(n_bins)
+        if self.n_bins < 1:
+            raise ValueError("n_bins must be at least 1")
+        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
+        row0, col0, rows, cols = self.window
+        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
+            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
+        self.shape = (self.n_bins, rows, cols)
+        self.count = np.zeros(self.n_bins, np.uint64)
+        self.stats = TimeStats(self.n_bins, rows, cols, None, None, None, None, None, 0.0 if threshold is None else float(threshold),
+                               self.count.ctypes.data)
+        self.fields = [("d_sum", np.float64), ("d_sum_sq", np.float64), ("d_min", np.float32), ("d_max", np.float32)]
+        if threshold is not None:
+            self.fields.append(("d_over", np.uint32))
+        lib = codec.lib
+        try:
+            for name, dtype in self.fields:
+                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
+                if not p:
+                    codec._fail("ebcc_hip_malloc")
+                setattr(self.stats, name, p)
+            if lib.ebcc_hip_time_stats_init(codec.ctx, ctypes.byref(self.stats)):
+                codec._fail("ebcc_hip_time_stats_init")
+        except BaseException:
+            self.close()
+            raise
+
+    def result(self):
+        lib, got = self.codec.lib, {}
+        for name, dtype in self.fields:
+            a = np.empty(self.shape, dtype)
+            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, name), a.nbytes):
+                self.codec._fail("ebcc_hip_memcpy_d2h")
+            got[name] = a
+        return ReduceResult(self.count.copy(), got["d_sum"], got["d_sum_sq"], got["d_min"], got["d_max"], got.get("d_over"))
+
+    def close(self):
+        for name, _ in self.fields:
+            p = getattr(self.stats, name)
+            if p:
+                self.codec.lib.ebcc_hip_free(p)
+                setattr(self.stats, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class BoundNotMet(RuntimeError):
     """A hard-bound write found frames that stay over their bound (return value 3 of the _hard entry points); `report` is
     the BOUND_REPORT array of the call that found them.  Nothing of that call has been written."""
@@ -130,6 +216,9 @@ class BatchCodec:
                                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
         lib.ebcc_hip_audit_host_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                                    ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.ebcc_hip_time_stats_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(TimeStats)]
+        lib.ebcc_hip_reduce_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeStats)]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -195,6 +284,43 @@ class BatchCodec:
         if rc:
             self._fail("ebcc_hip_audit_host_frames")
         return report
+
+    def reduce_state(self, n_bins=1, window=None, threshold=None):
+        """Device-resident accumulators for reduce(state=...): n_bins bins of the window (row0, col0, rows, cols) - None: the
+        whole frame -, with an exceedance count when a threshold is given.  A ReduceState; close() it when done."""
+        return ReduceState(self, n_bins, window, threshold)
+
+    def reduce(self, streams, bins=None, n_bins=1, window=None, threshold=None, state=None):
+        """Statistics over time straight from the streams (ebcc_hip_reduce_shard): every frame - or its `window` = (row0, col0,
+        rows, cols), decoded from the code-blocks it depends on alone - is folded on the device into the accumulators of the
+        bin `bins` names for it (an integer per stream, None: all bin 0, -1: the frame is skipped and not read - its entry of
+        `streams` may be None) -> a ReduceResult.  No decoded frame leaves the device; the sums are the bytes of a loop over
+        the frames in order, whatever the engine's capacity.  `state`: a ReduceState (reduce_state) that is added to and
+        returned instead - n_bins, window and threshold are then the state's -, so that a series walked call by call in frame
+        order gives the bytes of one call; state.result() downloads the accumulators.  ValueError for bins the engine refuses,
+        RuntimeError for what the call reports, such as a malformed stream (the state must then be made anew)."""
+        n = len(streams)
+        own = state is None
+        if own:
+            state = ReduceState(self, n_bins, window, threshold)
+        try:
+            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
+                raise ValueError(f"bins must be {n} integers, one per stream")
+            b = b.astype(np.int64)
+            if b.min() < -1 or b.max() >= state.n_bins:
+                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
+            if not (b >= 0).any():
+                raise ValueError("no frame is named")
+            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.nonzero(b >= 0)[0]))
+            row0, col0 = state.window[:2]
+            if self.lib.ebcc_hip_reduce_shard(self.ctx, ptrs, sizes, n, table.ctypes.data, row0, col0, ctypes.byref(state.stats)):
+                self._fail("ebcc_hip_reduce_shard")
+            return state.result() if own else state
+        finally:
+            if own:
+                state.close()
 
     def encode_groups(self, groups, hard=False, max_rounds=0):
         """Many variables in one device call: `groups` is a list of (frames, base_cr, residual_opt[, range_of_group]) - frames
@@ -537,6 +663,56 @@ def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
             if t:
                 t.join()
     return out.reshape(tuple(lead) + (nrows, ncols))
+
+
+def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=None, batch=256, codec=None):
+    """Statistics over time of an EBCC-filtered one-frame-per-chunk dataset, folded on the device (BatchCodec.reduce): `bins`
+    is an integer array shaped like the leading axes - the bin of every frame, -1: skip the frame (its chunk is not fetched);
+    None: everything in one bin -, n_bins defaults to bins.max() + 1, `rows` / `cols` are slices (step 1) as in read_frames.
+    -> a ReduceResult whose every statistic equals the same reduction - a loop over the frames in C order of the leading axes,
+    in float64 - of read_frames(dset)[..., rows, cols]; no frame is downloaded.  The chunks are fetched as read_frames fetches
+    them, the next call's on a helper thread, and folded call after call into one device-resident state, so the dataset need
+    not fit into host memory."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
+        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
+    b = b.astype(np.int64).reshape(-1)
+    named = np.nonzero(b >= 0)[0]
+    if len(named) < 1 or b.min() < -1:
+        raise ValueError("bins must name at least one frame, and -1 is the only negative value")
+    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
+    if b.max() >= n_bins:
+        raise ValueError(f"a frame names bin {int(b.max())} of {n_bins}")
+    codec = codec or cached_codec(h, w, min(batch, len(named)))
+    step = _SUPER * codec.max_frames
+
+    def fetch(lo, box):
+        try:
+            box.append(_read_chunks(dset, named[lo:lo + step]))
+        except BaseException as e:                                  # (handed to the caller's thread)
+            box.append(e)
+
+    box = []
+    fetch(0, box)
+    with codec.reduce_state(n_bins, (row0, col0, nrows, ncols), threshold) as state:
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                codec.reduce(raw, bins=b[named[lo:lo + step]], state=state)
+            finally:
+                if t:
+                    t.join()
+        return state.result()
 
 
 def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):

@@ -419,6 +419,57 @@ int ebcc_hip_encode_shard_hard(ebcc_hip_ctx *ctx, const float *d_frames, size_t 
 int ebcc_hip_encode_host_frames_hard(ebcc_hip_ctx *ctx, const float *h_frames, size_t n_frames, const codec_config_t *config, int max_rounds,
                                      uint8_t **out_streams, size_t *out_sizes, ebcc_hip_bound_report *report);
 
+/* ---- reduce decode: statistics over time from the streams, on the device ------------------------------
+ * A mean, a minimum, a maximum, a variance or an exceedance count over time - daily means from hourly steps, a monthly
+ * climatology, the diurnal cycle, "days above 30 C" - needs no decoded sample.  Streams go in, per-pixel accumulators come out:
+ * the frames (or one window of every frame: only the code-blocks it needs are decoded) are decoded batch by batch into a buffer
+ * of the engine set and folded into the accumulators of the bin each frame names; no decoded frame reaches the caller.  The
+ * reference has no counterpart (ebcc_decode / ebcc_decode_chunking, src/ebcc_codec.h:42,47, return every sample).
+ * The order is the contract: for every bin and pixel the frames of that bin are folded in increasing frame index, one after
+ * the other (acc = acc + x), so the accumulators are the same bytes whatever the batch size, the slices, the engine sets, the
+ * alignment of the arrays and the split of a series over several calls - the bytes of a plain loop over the decoded fields:
+ *   sum += (double) x;  sum_sq += (double) x * (double) x (the product is exact, the sum rounds);  min / max in float, -0
+ *   counts as +0 and +0 is written;  over += x > threshold, compared in float.
+ * No atomics, and frames never meet in a reduction tree (ebcc_amd/csrc/host_codec.hip: k_time_fold).
+ * Not covered: chunks of several frames, a slab of an EBCK container whose region crosses chunks, a host-pointer form, weighted
+ * area statistics per frame, the reference-compatible entry points and the filter callback. */
+#define EBCC_HIP_NO_BIN UINT32_MAX
+typedef struct {
+    size_t    n_bins, rows, cols;        /* the accumulators are [n_bins][rows][cols] */
+    double   *d_sum, *d_sum_sq;          /* device, 8-byte aligned; each may be NULL */
+    float    *d_min, *d_max;             /* device, 4-byte aligned; each may be NULL */
+    uint32_t *d_over; float threshold;   /* device, may be NULL: frames with sample > threshold */
+    uint64_t *count;                     /* host [n_bins]: frames folded into each bin */
+} ebcc_hip_time_stats;
+/* Host only, no device: the number of frames `bin` names (bin: host [n_frames], NULL = every frame in bin 0, EBCC_HIP_NO_BIN =
+ * the frame is skipped), or -1 with a message for what the calls below refuse before touching a device: a null stats or a null
+ * count, every device array NULL, n_bins, rows or cols zero, a window [row0, row0 + rows) x [col0, col0 + cols) not inside the
+ * height x width frame, a d_sum or d_sum_sq that is not 8-byte aligned or another array that is not 4-byte aligned, a bin >=
+ * n_bins, no frame named, a geometry ebcc_hip_create refuses. */
+long ebcc_hip_time_stats_check(size_t height, size_t width, const ebcc_hip_time_stats *stats, const uint32_t *bin, size_t n_frames,
+                               size_t row0, size_t col0);
+/* sums and over = 0, min = +inf, max = -inf, count = 0.  ctx: any context of the device.  0 = ok, 1 = error. */
+int ebcc_hip_time_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_stats *stats);
+/* unit level, the kernel alone: d_items [n_items][rows][cols] at any 4-byte aligned device address are folded in index order
+ * into the bins they name; an item with EBCC_HIP_NO_BIN is not read, a bin no item names is not touched.  The items are never
+ * written.  ctx: any context of the device.  Adds to what stats holds (count included).  0 = ok, 1 = error, nothing written. */
+int ebcc_hip_time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const ebcc_hip_time_stats *stats);
+/* Any number of one-frame streams: the frames `bin` names are decoded - the window [row0, row0 + stats->rows) x [col0, col0 +
+ * stats->cols) by the window decode, the whole frame by the full decode when the window is the frame - in batches of the
+ * context's capacity on the two engine sets, each into its set's audit buffer (the one ebcc_hip_audit_* use: a context runs
+ * one call at a time), and folded.  The decodes of two batches run side by side; the folds take turns in batch order.  A frame
+ * with EBCC_HIP_NO_BIN is not read at all: its streams[f] may be NULL with size 0, and it takes no slot of a batch.  The call
+ * adds to what stats holds: a series folded by several calls in frame order gives the bytes of one call.
+ * Return 0 = ok, 1 = error (ebcc_hip_last_error).  Refused before anything is written, accumulators and count included: what
+ * ebcc_hip_time_stats_check refuses for the context's frames, a context for chunks of several frames, a named frame without a
+ * stream or with one whose frame header does not parse (truncated, sizes that do not add up).  A stream found damaged inside a
+ * batch - its codestream or its residual layer - is refused as ebcc_hip_decode_frames refuses it; a batch folds only after all
+ * of it has decoded, so streams that all fail (a context of another geometry) leave everything untouched, but after batches
+ * that succeeded the accumulators hold an unspecified mixture and must be initialised again (count is only advanced by a call
+ * that succeeds).  Nothing outside the accumulators is written in either case. */
+int ebcc_hip_reduce_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                          size_t row0, size_t col0, const ebcc_hip_time_stats *stats);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -458,7 +509,7 @@ int ebcc_hip_selfcheck(void);
 void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4]);
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
- * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors".  Process-wide switch. */
+ * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
