@@ -320,6 +320,11 @@ ebcc_hip_ctx *ebcc::create_engine(int device, size_t max_frames, size_t height, 
         set_error("ebcc_hip_create: unsupported geometry %zu x %zu x %zu", max_frames, height, width);
         return nullptr;
     }
+    if (max_frames > kMaxEngineFrames) {                    // (blockIdx.y is the frame: gridDim.y ends at 65535)
+        set_error("ebcc_hip_create: %zu frames in one context, the limit is %zu (frames times tiles for chunks of several frames)",
+                  max_frames, kMaxEngineFrames);
+        return nullptr;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
         set_error("ebcc_hip_create: no HIP device %d (found %d) - the MI355X engine has no CPU fallback", device, ndev);

@@ -64,6 +64,9 @@ struct ebcc_hip_ctx {
 namespace ebcc {
 
 void set_error(const char *fmt, ...);
+// Frames one context holds at the most: every batch kernel takes its frame from blockIdx.y, and gridDim.y ends at 65535.  For
+// chunks of several frames the count is frames times tiles.  create_engine refuses more; batch_capacity never asks for more.
+constexpr size_t kMaxEngineFrames = 65535;
 // ebcc_hip_create for frames that are the tiles of images of `tile_period` tiles each (1: plain frames)
 ebcc_hip_ctx *create_engine(int device, size_t max_frames, size_t height, size_t width, int tile_period);
 template <typename T>

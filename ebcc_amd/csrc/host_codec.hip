@@ -211,14 +211,14 @@ struct Prefault {
 
 // Frames per device batch of the host-pointer entry points: EBCC_HIP_MAX_BATCH (default 256), reduced for large
 // frames so that an engine's workspace (about 160 bytes per pixel and frame with the worst-case slots) stays
-// under ~48 GB.
-size_t batch_capacity(size_t n_pix)
+// under ~48 GB, and never more than a context holds (kMaxEngineFrames frames: chunks of `tiles` frames count as that many).
+size_t batch_capacity(size_t n_pix, size_t tiles = 1)
 {
     const char *e = getenv("EBCC_HIP_MAX_BATCH");
     size_t v = e ? strtoul(e, nullptr, 10) : 256;
     if (!v) v = 256;
     const size_t fit = ((size_t) 48 << 30) / (n_pix * 160 + 1);
-    return std::max<size_t>(1, std::min(v, fit));
+    return std::max<size_t>(1, std::min({v, fit, ebcc::kMaxEngineFrames / std::max<size_t>(1, tiles)}));
 }
 
 // the engine of the tiles and, for chunks of several frames, the engine of the stacked chunk image (false: logged)
@@ -1258,7 +1258,7 @@ int encode_on_device(int device, const float *data, size_t n, int H, int W, cons
                      size_t tiles = 1)
 {
     return on_codec(device, 1, [&] {
-        const size_t cap = std::min(n, batch_capacity((size_t) H * W * tiles));
+        const size_t cap = std::min(n, batch_capacity((size_t) H * W * tiles, tiles));
         ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
         PhaseTimer pt;
         if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) return 1;
@@ -2664,7 +2664,7 @@ size_t ebcc_decode_chunking(uint8_t *data, size_t data_size, float **out_buffer)
     const size_t tiles = cd[0];
     const int rcode = run_on_devices(nchunks, [&](int device, size_t first, size_t count) {
         return on_codec(device, 1, [&] {
-            const size_t cap = std::min(count, batch_capacity(csize));
+            const size_t cap = std::min(count, batch_capacity(csize, tiles));
             ebcc_hip_ctx *ctx = nullptr, *rc = nullptr;
             if (!chunk_engines(device, H, W, cap, tiles, &ctx, &rc)) return 1;
             return decode_to_host(ctx, rc, tiles, cap, ptrs.data() + first, lens.data() + first, count, h_chunks + first * csize, &prefault);

@@ -36,7 +36,12 @@ typedef struct ebcc_hip_ctx ebcc_hip_ctx;
 /* ---- context -------------------------------------------------------------------------------- */
 int ebcc_hip_device_count(void);
 /* One context per (device, frame geometry); owns a HIP stream and all workspaces for up to
- * max_frames frames of height x width.  Returns NULL on failure. */
+ * max_frames frames of height x width.  Returns NULL on failure.
+ * max_frames is at most EBCC_HIP_MAX_FRAMES: the batch kernels take the frame from blockIdx.y, whose range ends there.  A
+ * larger context is refused with a message (ebcc_hip_last_error) before anything is allocated; larger arrays go through the
+ * shard and host-frames entry points, which run batches of the context's capacity.  (For the chunks of several frames of the
+ * reference-compatible entry points the limit is on frames times tiles; EBCC_HIP_MAX_BATCH is capped accordingly.) */
+#define EBCC_HIP_MAX_FRAMES 65535
 ebcc_hip_ctx *ebcc_hip_create(int device, size_t max_frames, size_t height, size_t width);
 void ebcc_hip_destroy(ebcc_hip_ctx *ctx);
 /* the context's hipStream_t (so callers can order their own work against it) */
