@@ -52,7 +52,9 @@ struct ebcc_hip_ctx {
     // Audit and hard-bound encode (host_codec.hip), all made on first use and freed with the engine set: the decoded frames of
     // one batch, the originals of a round's offenders gathered side by side, and the records of k_frame_errors (one per
     // workgroup, then one per frame, with the frames' bounds behind them) on the device and pinned.  The reduce decode decodes
-    // its batches into d_audit too (a context runs one call at a time) and keeps the fold's (item, bin) list in h_boxes / d_boxes.
+    // its batches into d_audit too (a context runs one call at a time) and keeps the fold's (item, bin) list in h_boxes / d_boxes;
+    // so does the area series, whose row weights and region table lie in h_boxes / d_boxes and whose records (per row of a
+    // region, then per region) lie in d_errs / h_errs.
     float *d_audit = nullptr, *d_offenders = nullptr;
     size_t audit_cap = 0, offenders_cap = 0;                    // bytes
     void *d_errs = nullptr, *h_errs = nullptr;

@@ -588,19 +588,23 @@ float *set_buffer(float *&p, size_t &cap, size_t bytes)
 // report[f] for the n frames d_d against d_x (device, [n][n_pix], any 4-byte alignment), counting |x - d| > bound[f] (host, may
 // be null) -> 0, or 2 when a frame of d_x holds a NaN or an Inf.  Two launches, the bounds up and the records down per 4096
 // frames, on ctx's stream, which is waited for.  Device current, the context the caller's alone.
+// room for `need` bytes of records in ctx->d_errs and in its pinned mirror ctx->h_errs (engine.hpp), grown on demand
+void errs_reserve(ebcc_hip_ctx *ctx, size_t need)
+{
+    if (ctx->errs_cap >= need) return;
+    if (ctx->d_errs) { hipFree(ctx->d_errs); ctx->d_errs = nullptr; }
+    if (ctx->h_errs) { hipHostFree(ctx->h_errs); ctx->h_errs = nullptr; }
+    ctx->errs_cap = 0;
+    EBCC_HIP_CHECK(hipHostMalloc(&ctx->h_errs, need));
+    EBCC_HIP_CHECK(device_malloc(&ctx->d_errs, need));
+    ctx->errs_cap = need;
+}
 int frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n, size_t n_pix, const float *bound, ebcc_hip_frame_error *report)
 {
     constexpr size_t kFrames = 4096;
     const unsigned pieces = frame_error_pieces(n_pix);
     const size_t most = std::min(n, kFrames), need = most * ((pieces + 1) * sizeof(ErrRecord) + sizeof(float));
-    if (ctx->errs_cap < need) {
-        if (ctx->d_errs) { hipFree(ctx->d_errs); ctx->d_errs = nullptr; }
-        if (ctx->h_errs) { hipHostFree(ctx->h_errs); ctx->h_errs = nullptr; }
-        ctx->errs_cap = 0;
-        EBCC_HIP_CHECK(hipHostMalloc(&ctx->h_errs, need));
-        EBCC_HIP_CHECK(device_malloc(&ctx->d_errs, need));
-        ctx->errs_cap = need;
-    }
+    errs_reserve(ctx, need);
     ErrRecord *d_part = (ErrRecord *) ctx->d_errs, *d_res = d_part + most * pieces, *h_res = (ErrRecord *) ctx->h_errs;
     float *d_bound = (float *) (d_res + most), *h_bound = (float *) (h_res + most);
     int rc = 0;
@@ -778,6 +782,220 @@ void time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n, size_t n_pix, 
     }
     EBCC_HIP_LAUNCH_CHECK();
     wait_stream(ctx->stream);
+}
+
+// Area statistics per item (include/ebcc_hip.h: ebcc_hip_area_stat, and the order rule stated there): the weighted sums, the
+// minimum and the maximum of every region of every item, by the fold the header fixes - fold64 over a row's terms with groups
+// of four columns, then fold64 over a region's rows one by one.  Two launches, a wave (not a workgroup: nothing is shared, no
+// LDS, no barrier) per row of a region, then a wave per region:
+//   k_area_rows   lane l takes the quads l, l + 64, .. of its row, two of them in flight, term after term in column order
+//                 (p = p + t: the partial sum l of the rule), the last cols % 4 columns in the quad they fall in; then the
+//                 butterfly of shuffles (a + b on both sides of an exchange: every lane ends with the same bits) and lane 0
+//                 writes the row's record.  Quads count from the region's first column, not from an address: a full quad is
+//                 one 16-byte load where the row of the region happens to begin on a 16-byte boundary and four 4-byte loads
+//                 where it does not (samples and weights each on their own), which changes no term and no order.
+//   k_area_fold   lane l adds the row records l, l + 64, .. of its region in row order, the same butterfly, one record out.
+// The items are windows [win rows][pitch] of their frames with the origin (row0, col0); regions and weights are in frame
+// coordinates.  Region, row and weight of a wave are wave-uniform (the wave's index goes through readfirstlane: the tables are
+// read by scalar loads).  No atomics.  A pixel whose weight is 0 adds nothing - the same bytes as a term of +0.0, since a
+// partial sum that starts at +0.0 never becomes -0.0.
+struct AreaRegion { unsigned row0, col0, rows, cols, first, pad; };    // first: the region's first row record within an item
+struct AreaRec { double sum, sum_sq, over; float mn, mx; };
+static_assert(sizeof(AreaRec) == 32 && sizeof(ebcc_hip_area_stat) == 32, "one record is 32 bytes");
+struct AreaItems { const float *d; size_t stride; unsigned pitch, row0, col0; };   // item k: d + k * stride, rows of `pitch` samples
+struct AreaWeights { const double *row; const float *pix; unsigned width; int use_threshold; float threshold; };   // (device pointers)
+__device__ inline void area_add(AreaRec &a, const AreaRec &b)
+{
+    a.sum = a.sum + b.sum; a.sum_sq = a.sum_sq + b.sum_sq; a.over = a.over + b.over;
+    a.mn = fminf(a.mn, b.mn); a.mx = fmaxf(a.mx, b.mx);
+}
+// every lane of the wave ends with the fold of all 64 records; -0 leaves as +0
+__device__ inline void area_butterfly(AreaRec &r)
+{
+    for (int o = 32; o >= 1; o >>= 1) {
+        AreaRec t;
+        t.sum = __shfl_xor(r.sum, o); t.sum_sq = __shfl_xor(r.sum_sq, o); t.over = __shfl_xor(r.over, o);
+        t.mn = __shfl_xor(r.mn, o); t.mx = __shfl_xor(r.mx, o);
+        area_add(r, t);
+    }
+    r.mn = r.mn + 0.0f; r.mx = r.mx + 0.0f;
+}
+// the largest r with regions[r].first <= job (regions[0].first == 0)
+__device__ inline unsigned area_region_of(const AreaRegion *__restrict__ regions, unsigned n_regions, unsigned job)
+{
+    unsigned lo = 0, hi = n_regions;
+    while (hi - lo > 1) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if (regions[mid].first <= job) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// wave w of the grid: row record w % jobs of item w / jobs, for w < n_items * jobs
+__global__ __launch_bounds__(256) void k_area_rows(AreaItems items, unsigned n_items, const AreaRegion *__restrict__ regions, unsigned n_regions,
+                                                   unsigned jobs, AreaWeights wt, AreaRec *__restrict__ rows)
+{
+    const unsigned wave = (unsigned) __builtin_amdgcn_readfirstlane((int) (blockIdx.x * 4u + (threadIdx.x >> 6))), lane = threadIdx.x & 63u;
+    if (wave >= n_items * jobs) return;
+    const unsigned item = wave / jobs, job = wave - item * jobs;
+    const AreaRegion reg = regions[area_region_of(regions, n_regions, job)];
+    const unsigned row = reg.row0 + (job - reg.first);                                  // (of the frame)
+    const float *__restrict__ xs = items.d + (size_t) item * items.stride + (size_t) (row - items.row0) * items.pitch + (reg.col0 - items.col0);
+    const float *__restrict__ ws = wt.pix ? wt.pix + (size_t) row * wt.width + reg.col0 : nullptr;
+    const double wr = wt.row ? wt.row[row] : 1.0;
+    AreaRec r{0.0, 0.0, 0.0, __builtin_inff(), -__builtin_inff()};
+    auto take = [&](float x, float wp) {
+        const double w = wr * (double) wp;
+        if (w != 0.0) {
+            const double xd = (double) x;
+            r.sum = r.sum + xd * w;
+            r.sum_sq = r.sum_sq + (xd * xd) * w;
+            r.over = r.over + (wt.use_threshold && x > wt.threshold ? w : 0.0);
+            r.mn = fminf(r.mn, x);
+            r.mx = fmaxf(r.mx, x);
+        }
+    };
+    auto take4 = [&](const f32x4 &x, const f32x4 &w) { take(x.x, w.x); take(x.y, w.y); take(x.z, w.z); take(x.w, w.w); };
+    // (uniform over the wave: where the row of the region begins)
+    const bool xv = ((uintptr_t) xs & 15) == 0, wv = ((uintptr_t) ws & 15) == 0;
+    auto quad = [](const float *p, bool vec, unsigned q) {
+        if (!p) return f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+        if (vec) return reinterpret_cast<const f32x4 *>(p)[q];
+        const float *s = p + 4 * (size_t) q;
+        return f32x4{s[0], s[1], s[2], s[3]};
+    };
+    const unsigned n4 = reg.cols >> 2, tail = reg.cols & 3u;
+    unsigned q = lane;
+    for (; q + 64 < n4; q += 128) {
+        const f32x4 x0 = quad(xs, xv, q), x1 = quad(xs, xv, q + 64), w0 = quad(ws, wv, q), w1 = quad(ws, wv, q + 64);
+        take4(x0, w0);
+        take4(x1, w1);
+    }
+    if (q < n4) take4(quad(xs, xv, q), quad(ws, wv, q));
+    if (tail && lane == (n4 & 63u))                                                     // (quad n4 is this lane's last)
+        for (unsigned c = 4 * n4; c < reg.cols; c++) take(xs[c], ws ? ws[c] : 1.0f);
+    area_butterfly(r);
+    if (lane == 0) rows[(size_t) item * jobs + job] = r;
+}
+// wave w of the grid: region w % n_regions of item w / n_regions, from its row records
+__global__ __launch_bounds__(256) void k_area_fold(const AreaRec *__restrict__ rows, unsigned n_items, const AreaRegion *__restrict__ regions, unsigned n_regions,
+                                                   unsigned jobs, AreaRec *__restrict__ out)
+{
+    const unsigned wave = (unsigned) __builtin_amdgcn_readfirstlane((int) (blockIdx.x * 4u + (threadIdx.x >> 6))), lane = threadIdx.x & 63u;
+    if (wave >= n_items * n_regions) return;
+    const unsigned item = wave / n_regions, g = wave - item * n_regions;
+    const AreaRegion reg = regions[g];
+    const AreaRec *__restrict__ mine = rows + (size_t) item * jobs + reg.first;
+    AreaRec r{0.0, 0.0, 0.0, __builtin_inff(), -__builtin_inff()};
+    for (unsigned j = lane; j < reg.rows; j += 64) area_add(r, mine[j]);
+    area_butterfly(r);
+    if (lane == 0) out[wave] = r;
+}
+// 1 into *bad when a weight of the box [row0, +rows) x [col0, +cols) of pix [.][width] is negative, a NaN or an Inf (every
+// lane that finds one stores the same word)
+__global__ __launch_bounds__(256) void k_area_weights_bad(const float *__restrict__ pix, unsigned width, unsigned row0, unsigned col0, unsigned rows, unsigned cols,
+                                                          unsigned *__restrict__ bad)
+{
+    const size_t n = (size_t) rows * cols;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
+        const float w = pix[(size_t) (row0 + i / cols) * width + col0 + i % cols];
+        if (!(w >= 0.0f) || isinf(w)) *bad = 1u;
+    }
+}
+// What ebcc_hip_area_check checks -> n_regions and the bounding box of the regions, or -1 with the message set.
+long area_checked(const char *who, size_t height, size_t width, const ebcc_hip_area_spec *spec, ebcc_hip_region *bounding)
+{
+    if (!spec || !spec->regions) { set_error("%s: no spec, or no region list", who); return -1; }
+    if (spec->n_regions < 1) { set_error("%s: n_regions must not be zero", who); return -1; }
+    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("%s: unsupported geometry %zu x %zu", who, height, width); return -1; }
+    size_t bytes = 0;
+    if (spec->n_regions > (size_t) LONG_MAX || __builtin_mul_overflow(spec->n_regions, sizeof(AreaRegion) + sizeof(AreaRec), &bytes)) {
+        set_error("%s: the size of the region table overflows", who);
+        return -1;
+    }
+    if ((uintptr_t) spec->d_w_pix & 3) { set_error("%s: d_w_pix must be 4-byte aligned", who); return -1; }
+    size_t r0 = height, c0 = width, r1 = 0, c1 = 0;
+    for (size_t g = 0; g < spec->n_regions; g++) {
+        const ebcc_hip_region &R = spec->regions[g];
+        if (R.rows < 1 || R.cols < 1 || R.row0 >= height || R.col0 >= width || R.rows > height - R.row0 || R.cols > width - R.col0) {
+            set_error("%s: region %zu, [%zu, +%zu) x [%zu, +%zu), is empty or not inside the %zu x %zu frame", who, g, R.row0, R.rows, R.col0, R.cols, height, width);
+            return -1;
+        }
+        r0 = std::min(r0, R.row0); c0 = std::min(c0, R.col0); r1 = std::max(r1, R.row0 + R.rows); c1 = std::max(c1, R.col0 + R.cols);
+    }
+    if (spec->w_row)
+        for (size_t r = 0; r < height; r++)
+            if (!(spec->w_row[r] >= 0.0) || std::isinf(spec->w_row[r])) { set_error("%s: w_row[%zu] is negative, a NaN or an Inf", who, r); return -1; }
+    if (bounding) *bounding = ebcc_hip_region{r0, c0, r1 - r0, c1 - c0};
+    return (long) spec->n_regions;
+}
+// The device pass over the weights of the box `bb` -> true when one of them is negative, a NaN or an Inf.  On ctx's stream,
+// which is waited for; the word lies in the context's record buffer.  Device current, the context the caller's alone.
+bool area_weights_bad(ebcc_hip_ctx *ctx, const float *d_w_pix, size_t width, const ebcc_hip_region &bb)
+{
+    errs_reserve(ctx, 256);
+    unsigned *d_bad = (unsigned *) ctx->d_errs, *h_bad = (unsigned *) ctx->h_errs;
+    EBCC_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned), ctx->stream));
+    const size_t n = bb.rows * bb.cols;
+    hipLaunchKernelGGL(k_area_weights_bad, dim3((unsigned) std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, ctx->stream, d_w_pix, (unsigned) width,
+                       (unsigned) bb.row0, (unsigned) bb.col0, (unsigned) bb.rows, (unsigned) bb.cols, d_bad);
+    EBCC_HIP_LAUNCH_CHECK();
+    EBCC_HIP_CHECK(hipMemcpyAsync(h_bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    wait_stream(ctx->stream);
+    return *h_bad != 0;
+}
+// out[k][g] (host, [n][n_regions]) for the n items and the regions of a checked spec (area_checked).  w_row and the region
+// table go up through the context's pinned table (boxes_reserve); row records and records lie in the context's record buffer
+// (errs_reserve), and no launch makes more than kAreaRecords of either: the regions are cut into groups of at most that many
+// rows, the items of a group into runs of at most that many row records (at least one item).  The records of a run come home
+// in one copy.  On ctx's stream, which is waited for.  Device current, the context the caller's alone.
+constexpr size_t kAreaRecords = (size_t) 1 << 18;
+void area_fold(ebcc_hip_ctx *ctx, const AreaItems &items, size_t n, size_t height, size_t width, const ebcc_hip_area_spec &spec, ebcc_hip_area_stat *out)
+{
+    const size_t R = spec.n_regions, row_bytes = spec.w_row ? height * sizeof(double) : 0;
+    boxes_reserve(ctx, 1, row_bytes + R * sizeof(AreaRegion));
+    AreaRegion *h_reg = (AreaRegion *) ((char *) ctx->h_boxes + row_bytes);
+    const AreaRegion *d_reg = (const AreaRegion *) ((const char *) ctx->d_boxes + row_bytes);
+    if (spec.w_row) memcpy(ctx->h_boxes, spec.w_row, row_bytes);
+    // regions [g0, g0 + G) with J rows in all, at most kAreaRecords (a region has at most 2047), taken `run` items a time
+    struct Group { size_t g0, G, J, run; };
+    std::vector<Group> groups;
+    size_t need = 0;
+    auto close = [&](size_t g0, size_t g1, size_t J) {
+        const size_t run = std::min(n, std::max<size_t>(1, kAreaRecords / J));
+        groups.push_back(Group{g0, g1 - g0, J, run});
+        need = std::max(need, run * (J + (g1 - g0)) * sizeof(AreaRec));
+    };
+    size_t g0 = 0, jobs = 0;
+    for (size_t g = 0; g < R; g++) {
+        const ebcc_hip_region &S = spec.regions[g];
+        if (jobs + S.rows > kAreaRecords) { close(g0, g, jobs); g0 = g; jobs = 0; }
+        h_reg[g] = AreaRegion{(unsigned) S.row0, (unsigned) S.col0, (unsigned) S.rows, (unsigned) S.cols, (unsigned) jobs, 0u};
+        jobs += S.rows;
+    }
+    close(g0, R, jobs);
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_boxes, ctx->h_boxes, row_bytes + R * sizeof(AreaRegion), hipMemcpyHostToDevice, ctx->stream));
+    errs_reserve(ctx, need);
+    const AreaWeights wt{spec.w_row ? (const double *) ctx->d_boxes : nullptr, spec.d_w_pix, (unsigned) width, spec.use_threshold, spec.threshold};
+    for (const Group &gr : groups) {
+        AreaRec *d_rows = (AreaRec *) ctx->d_errs, *d_out = d_rows + gr.run * gr.J;
+        const AreaRec *h_out = (const AreaRec *) ctx->h_errs;
+        for (size_t lo = 0; lo < n; lo += gr.run) {
+            const size_t m = std::min(gr.run, n - lo);
+            AreaItems part = items;
+            part.d += lo * items.stride;
+            {
+                ScopedTiming timing("area_fold", ctx->stream);
+                hipLaunchKernelGGL(k_area_rows, dim3((unsigned) ((m * gr.J + 3) / 4)), dim3(256), 0, ctx->stream, part, (unsigned) m, d_reg + gr.g0, (unsigned) gr.G,
+                                   (unsigned) gr.J, wt, d_rows);
+                hipLaunchKernelGGL(k_area_fold, dim3((unsigned) ((m * gr.G + 3) / 4)), dim3(256), 0, ctx->stream, (const AreaRec *) d_rows, (unsigned) m, d_reg + gr.g0,
+                                   (unsigned) gr.G, (unsigned) gr.J, d_out);
+            }
+            EBCC_HIP_LAUNCH_CHECK();
+            EBCC_HIP_CHECK(hipMemcpyAsync(ctx->h_errs, d_out, m * gr.G * sizeof(AreaRec), hipMemcpyDeviceToHost, ctx->stream));
+            wait_stream(ctx->stream);
+            for (size_t k = 0; k < m; k++) memcpy(out + (lo + k) * R + gr.g0, h_out + k * gr.G, gr.G * sizeof(AreaRec));
+        }
+    }
 }
 
 // Where the chunks of an encode call lie: runs of chunks, each contiguous in (device or host) memory - one run for an
@@ -1705,6 +1923,45 @@ int reduce_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     });
 }
 
+// ---- area series: statistics over a region at every time step (include/ebcc_hip.h: ebcc_hip_area_spec; k_area_rows above)
+// The bounding box of the regions is what is decoded - a window, or the frame when the box is the frame -, batch by batch into
+// the set's audit buffer, and every batch is folded there and writes its own rows of `out`: batches never meet, so the two
+// sets run free (decode_batches_alternating).  The weights are looked at once, on the first set, before any decode.
+int series_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_area_spec *spec,
+                 ebcc_hip_area_stat *out)
+{
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    if (ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
+    const size_t H = (size_t) ctx->height, W = (size_t) ctx->width;
+    ebcc_hip_region bb{};
+    if (area_checked(who, H, W, spec, &bb) < 0) return 1;
+    size_t bytes = 0;
+    if (!streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return 1; }
+    if (__builtin_mul_overflow(n_frames, spec->n_regions, &bytes) || __builtin_mul_overflow(bytes, sizeof(ebcc_hip_area_stat), &bytes)) {
+        set_error("%s: the size of the records overflows", who);
+        return 1;
+    }
+    for (size_t f = 0; f < n_frames; f++) {
+        ParsedFrame pf;
+        if (!streams[f] || !parse_frame(streams[f], sizes[f], pf)) { set_error("%s: frame %zu: not a frame stream", who, f); return 1; }
+    }
+    const size_t pix = bb.rows * bb.cols;
+    const DecodeRegion asked = bb.rows == H && bb.cols == W ? DecodeRegion{} : DecodeRegion::window(bb.row0, bb.col0, bb.rows, bb.cols);
+    return decode_call(who, ctx, streams, sizes, n_frames, out, asked, false, [&](const DecodeRegion &region, const uint8_t *const *sp, const size_t *zp, size_t n) {
+        if (spec->d_w_pix && area_weights_bad(ctx, spec->d_w_pix, W, bb)) { set_error("%s: d_w_pix holds a negative value, a NaN or an Inf", who); return 1; }
+        const size_t cap = std::min(n, ctx->max_frames);
+        return decode_batches_alternating(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
+            PhaseTimer pt;
+            float *dec = set_buffer(set->d_audit, set->audit_cap, cap * pix * sizeof(float));
+            if (const int r = run_decode_slices(set, sp + lo, zp + lo, k, dec, region)) return r;
+            pt.mark("series: decode");
+            area_fold(set, AreaItems{dec, pix, (unsigned) bb.cols, (unsigned) bb.row0, (unsigned) bb.col0}, k, H, W, *spec, out + lo * spec->n_regions);
+            pt.mark("series: fold");
+            return 0;
+        });
+    });
+}
+
 // ---- EBCK chunk container (:920-1052, :1322-1449) --------------------------------------------------
 // The container as ebcc_decode_chunking checks it: the header, then the chain of `u64 nbytes | stream` entries - of a chunk only
 // the length field is read.  parse: "" or what is wrong with it (the reference's messages).
@@ -2469,6 +2726,39 @@ int ebcc_hip_reduce_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, cons
 {
     EBCC_API_TRY
     return reduce_shard("ebcc_hip_reduce_shard", ctx, streams, sizes, n_frames, bin, row0, col0, stats);
+    EBCC_API_CATCH(1)
+}
+
+// ---- area series (series_shard above): statistics over regions per frame, folded on the device
+long ebcc_hip_area_check(size_t height, size_t width, const ebcc_hip_area_spec *spec, ebcc_hip_region *bounding)
+{
+    EBCC_API_TRY
+    return area_checked("ebcc_hip_area_check", height, width, spec, bounding);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_area_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, size_t height, size_t width, const ebcc_hip_area_spec *spec,
+                       ebcc_hip_area_stat *out)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_area_fold";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || !out || n_items < 1) { set_error("%s: bad arguments", who); return 1; }
+    ebcc_hip_region bb{};
+    if (area_checked(who, height, width, spec, &bb) < 0) return 1;
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(n_items, spec->n_regions, &bytes) || __builtin_mul_overflow(bytes, sizeof(ebcc_hip_area_stat), &bytes) ||
+        __builtin_mul_overflow(n_items, height * width * sizeof(float), &bytes)) { set_error("%s: the size of the items or of the records overflows", who); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        if (spec->d_w_pix && area_weights_bad(ctx, spec->d_w_pix, width, bb)) { set_error("%s: d_w_pix holds a negative value, a NaN or an Inf", who); return 1; }
+        area_fold(ctx, AreaItems{d_items, height * width, (unsigned) width, 0u, 0u}, n_items, height, width, *spec, out);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_series_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_area_spec *spec,
+                          ebcc_hip_area_stat *out)
+{
+    EBCC_API_TRY
+    return series_shard("ebcc_hip_series_shard", ctx, streams, sizes, n_frames, spec, out);
     EBCC_API_CATCH(1)
 }
 

@@ -137,6 +137,111 @@ class ReduceState:
         self.close()
 
 
+class Region(ctypes.Structure):
+    """ebcc_hip_region, include/ebcc_hip.h: a box of a frame"""
+    _fields_ = [("row0", ctypes.c_size_t), ("col0", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t)]
+
+
+class AreaSpec(ctypes.Structure):
+    """ebcc_hip_area_spec, include/ebcc_hip.h: the regions, the row weights (host) and the pixel weights (device) of an area series"""
+    _fields_ = [("n_regions", ctypes.c_size_t), ("regions", ctypes.POINTER(Region)), ("w_row", ctypes.c_void_p), ("d_w_pix", ctypes.c_void_p),
+                ("use_threshold", ctypes.c_int), ("threshold", ctypes.c_float)]
+
+
+# ebcc_hip_area_stat, include/ebcc_hip.h, as a numpy record type
+AREA_STAT = np.dtype([("sum", "<f8"), ("sum_sq", "<f8"), ("over", "<f8"), ("min", "<f4"), ("max", "<f4")])
+assert AREA_STAT.itemsize == 32
+
+
+class SeriesResult:
+    """Statistics over regions, per frame and region: sum, sum_sq and over (n, R) float64 - the weighted sums of x and x^2 and
+    the weight of the pixels with x > threshold (zeros without one) -, min and max (n, R) float32 over the pixels of non-zero
+    weight, weight (R,) float64: the total weight of each region (math.fsum: order-free).  The sums are those of the fold
+    include/ebcc_hip.h states, whatever the engine's capacity.  mean = sum / weight and var = sum_sq / weight - mean^2 are
+    float64; a region without weight gives NaN."""
+
+    def __init__(self, records, weight):
+        self.sum, self.sum_sq, self.over = (np.ascontiguousarray(records[name]) for name in ("sum", "sum_sq", "over"))
+        self.min, self.max = np.ascontiguousarray(records["min"]), np.ascontiguousarray(records["max"])
+        self.weight = weight
+
+    @property
+    def mean(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.sum / self.weight[None, :]
+
+    @property
+    def var(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = self.mean
+            return self.sum_sq / self.weight[None, :] - m * m
+
+
+def lat_weights(lat_degrees):
+    """cos(latitude) in float64: the row weights of an area mean on a regular latitude-longitude grid"""
+    return np.cos(np.deg2rad(np.asarray(lat_degrees, np.float64)))
+
+
+class _Area:
+    """The checked arguments of an area series: the region table, the row weights and - uploaded once, freed by close() - the
+    pixel weights on the device, as the ebcc_hip_area_spec the calls take."""
+
+    def __init__(self, codec, regions, w_row, w_pix, threshold):
+        h, w = codec.h, codec.w
+        r = np.asarray(regions)
+        if r.ndim != 2 or r.shape[1] != 4 or r.shape[0] < 1 or r.dtype.kind not in "iu":
+            raise ValueError("regions must be a non-empty integer array of shape (R, 4): row0, col0, rows, cols")
+        r = r.astype(np.int64)
+        if (r[:, :2] < 0).any() or (r[:, 2:] < 1).any() or (r[:, 0] + r[:, 2] > h).any() or (r[:, 1] + r[:, 3] > w).any():
+            raise ValueError(f"a region is empty or not inside the {h} x {w} frame")
+        self.codec, self.regions = codec, r
+        self.table = (Region * len(r))(*[Region(*(int(v) for v in row)) for row in r])
+        self.w_row = None if w_row is None else np.ascontiguousarray(w_row, np.float64)
+        if self.w_row is not None and (self.w_row.shape != (h,) or not np.isfinite(self.w_row).all() or (self.w_row < 0).any()):
+            raise ValueError(f"w_row must be {h} finite weights that are not negative")
+        self.w_pix = None if w_pix is None else np.ascontiguousarray(w_pix, np.float32)
+        if self.w_pix is not None and self.w_pix.shape != (h, w):
+            raise ValueError(f"w_pix must have the shape ({h}, {w})")
+        self.d_w_pix = None
+        if self.w_pix is not None:
+            self.d_w_pix = codec.lib.ebcc_hip_malloc(self.w_pix.nbytes)
+            if not self.d_w_pix:
+                codec._fail("ebcc_hip_malloc")
+            if codec.lib.ebcc_hip_memcpy_h2d(self.d_w_pix, self.w_pix.ctypes.data, self.w_pix.nbytes):
+                self.close()
+                codec._fail("ebcc_hip_memcpy_h2d")
+        self.spec = AreaSpec(len(r), self.table, None if self.w_row is None else self.w_row.ctypes.data, self.d_w_pix,
+                             0 if threshold is None else 1, 0.0 if threshold is None else float(threshold))
+
+    def weight(self):
+        """the total weight of every region, order-free"""
+        import math
+        out = np.empty(len(self.regions), np.float64)
+        for g, (row0, col0, rows, cols) in enumerate(self.regions):
+            wr = np.ones(rows, np.float64) if self.w_row is None else self.w_row[row0:row0 + rows]
+            if self.w_pix is None:
+                out[g] = math.fsum(np.repeat(wr, cols).tolist()) if self.w_row is not None else float(rows * cols)
+            else:
+                out[g] = math.fsum((wr[:, None] * self.w_pix[row0:row0 + rows, col0:col0 + cols].astype(np.float64)).ravel().tolist())
+        return out
+
+    def run(self, streams):
+        """the records (n, R) of the streams"""
+        n = len(streams)
+        if n < 1:
+            raise ValueError("no streams")
+        streams, ptrs, sizes = _stream_arrays(streams)
+        records = np.zeros((n, len(self.regions)), AREA_STAT)
+        if self.codec.lib.ebcc_hip_series_shard(self.codec.ctx, ptrs, sizes, n, ctypes.byref(self.spec), records.ctypes.data):
+            self.codec._fail("ebcc_hip_series_shard")
+        return records
+
+    def close(self):
+        if self.d_w_pix:
+            self.codec.lib.ebcc_hip_free(self.d_w_pix)
+            self.d_w_pix = None
+
+
 class BoundNotMet(RuntimeError):
     """A hard-bound write found frames that stay over their bound (return value 3 of the _hard entry points); `report` is
     the BOUND_REPORT array of the call that found them.  Nothing of that call has been written."""
@@ -219,6 +324,8 @@ class BatchCodec:
         lib.ebcc_hip_time_stats_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(TimeStats)]
         lib.ebcc_hip_reduce_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeStats)]
+        lib.ebcc_hip_series_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                              ctypes.POINTER(AreaSpec), ctypes.c_void_p]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -321,6 +428,19 @@ class BatchCodec:
         finally:
             if own:
                 state.close()
+
+    def series(self, streams, regions, w_row=None, w_pix=None, threshold=None):
+        """Statistics over regions at every time step straight from the streams (ebcc_hip_series_shard): `regions` is an int
+        array (R, 4) of (row0, col0, rows, cols) - boxes of the frame, which may overlap and repeat -, w_row (H,) float64 a
+        weight per row (lat_weights), w_pix (H, W) float32 a weight per pixel, 0 where a pixel is masked out; both default to
+        1 and must be finite and not negative.  Only the bounding box of the regions is decoded, and no decoded frame leaves
+        the device -> a SeriesResult with one record per stream and region.  w_pix is uploaded once for the call.  ValueError
+        for arguments the engine would refuse, RuntimeError for what the call reports, such as a malformed stream."""
+        area = _Area(self, regions, w_row, w_pix, threshold)
+        try:
+            return SeriesResult(area.run(streams), area.weight())
+        finally:
+            area.close()
 
     def encode_groups(self, groups, hard=False, max_rounds=0):
         """Many variables in one device call: `groups` is a list of (frames, base_cr, residual_opt[, range_of_group]) - frames
@@ -713,6 +833,50 @@ def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=
                 if t:
                     t.join()
         return state.result()
+
+
+def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=None, batch=256, codec=None):
+    """Statistics over regions at every time step of an EBCC-filtered one-frame-per-chunk dataset, folded on the device
+    (BatchCodec.series): `frames` names the frames - counted in C order over the leading axes, in any order; None: all of them
+    -, regions, w_row, w_pix and threshold are those of BatchCodec.series -> a SeriesResult with one record per named frame, in
+    their order, and region; every statistic equals the fold of include/ebcc_hip.h over read_frames(dset) at those frames.  No
+    frame is downloaded.  The chunks are fetched as read_frames fetches them, the next call's on a helper thread, w_pix is
+    uploaded once, and the records of the calls are concatenated, so the dataset need not fit into host memory."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    named = np.arange(n) if frames is None else np.asarray(frames)
+    if named.ndim != 1 or len(named) < 1 or named.dtype.kind not in "iu" or named.min() < 0 or named.max() >= n:
+        raise ValueError(f"frames must be a non-empty list of integers in [0, {n})")
+    codec = codec or cached_codec(h, w, min(batch, len(named)))
+    step = _SUPER * codec.max_frames
+
+    def fetch(lo, box):
+        try:
+            box.append(_read_chunks(dset, named[lo:lo + step]))
+        except BaseException as e:                                  # (handed to the caller's thread)
+            box.append(e)
+
+    area = _Area(codec, regions, w_row, w_pix, threshold)
+    try:
+        box, parts = [], []
+        fetch(0, box)
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                parts.append(area.run(raw))
+            finally:
+                if t:
+                    t.join()
+        return SeriesResult(np.concatenate(parts), area.weight())
+    finally:
+        area.close()
 
 
 def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):

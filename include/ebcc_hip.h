@@ -436,8 +436,8 @@ int ebcc_hip_encode_host_frames_hard(ebcc_hip_ctx *ctx, const float *h_frames, s
  *   sum += (double) x;  sum_sq += (double) x * (double) x (the product is exact, the sum rounds);  min / max in float, -0
  *   counts as +0 and +0 is written;  over += x > threshold, compared in float.
  * No atomics, and frames never meet in a reduction tree (ebcc_amd/csrc/host_codec.hip: k_time_fold).
- * Not covered: chunks of several frames, a slab of an EBCK container whose region crosses chunks, a host-pointer form, weighted
- * area statistics per frame, the reference-compatible entry points and the filter callback. */
+ * Not covered: chunks of several frames, a slab of an EBCK container whose region crosses chunks, a host-pointer form, the
+ * reference-compatible entry points and the filter callback.  (Statistics over an area per frame: the area series below.) */
 #define EBCC_HIP_NO_BIN UINT32_MAX
 typedef struct {
     size_t    n_bins, rows, cols;        /* the accumulators are [n_bins][rows][cols] */
@@ -474,6 +474,61 @@ int ebcc_hip_time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, 
  * that succeeds).  Nothing outside the accumulators is written in either case. */
 int ebcc_hip_reduce_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
                           size_t row0, size_t col0, const ebcc_hip_time_stats *stats);
+
+/* ---- area series: statistics over regions at every time step, from the streams, on the device --------
+ * The other question an archive is asked: the area-weighted mean, minimum or maximum over a region for every frame - a
+ * global-mean series, an index over a box, a zonal-mean diagram (one region per row), the fraction of an area above a
+ * threshold.  Streams go in, n_frames x n_regions records of 32 bytes come out; the bounding box of the regions is decoded
+ * (only the code-blocks it needs) batch by batch into a buffer of the engine set and folded there.  No decoded frame reaches
+ * the caller.  The reference has no counterpart.
+ * The order is the contract: a region's record depends on the region, the weights inside it and the decoded samples inside
+ * it, and on nothing else - not on the batch size, the slices, the engine sets, the alignment of any array, the other regions
+ * of the list, or whether the frame was decoded whole or as a window.  Here a reduction tree is acceptable where the reduce
+ * decode forbids one: frames never meet, and the tree of a region is fixed by the region alone.  It is this fold:
+ *   fold64(v, g), v[0 .. n) doubles, g a group size: 64 partial sums, each +0.0 at first; partial l adds the elements i with
+ *   (i / g) % 64 == l in increasing i (p = p + v[i]); then p[l] = p[l] + p[l ^ o] for o = 32, 16, 8, 4, 2, 1 (both sides of
+ *   an exchange add the same two numbers: all 64 end with the same bits); the result is p[0].
+ *   Per pixel (r, c) of a region, in frame coordinates: w = (w_row ? w_row[r] : 1.0) * (d_w_pix ? (double) d_w_pix[r][c] : 1.0).
+ *   A pixel with w == 0 takes part in nothing (that is how a mask is expressed).  Otherwise, x the decoded sample (float):
+ *     t_sum = (double) x * w;  t_sq = ((double) x * (double) x) * w (the square is exact, one rounding);
+ *     t_over = use_threshold && x > threshold ? w : 0.0 (compared in float);  min / max in float by fminf / fmaxf.
+ *   Per row of the region: fold64 of the row's terms with g = 4, columns counted from the region's first column.
+ *   Per region: fold64 of its row results with g = 1, rows counted from the region's first row.
+ *   min / max take the same way (the order does not show in them) and leave with + 0.0f: -0 counts as +0.  A region whose
+ *   weights are all zero gives sums of +0.0, min = +inf, max = -inf.  Products and sums are never contracted.
+ * No atomics (ebcc_amd/csrc/host_codec.hip: k_area_rows, k_area_fold).
+ * Not covered: chunks of several frames, regions that are not boxes beyond what a d_w_pix mask expresses, a host-pointer
+ * form, EBCK containers, the reference-compatible entry points and the filter callback. */
+typedef struct { size_t row0, col0, rows, cols; } ebcc_hip_region;     /* frame coordinates */
+typedef struct {
+    size_t n_regions; const ebcc_hip_region *regions;                   /* host; regions may overlap and repeat */
+    const double *w_row;     /* host [height], NULL = 1: a weight per row of the frame (cos(latitude)) */
+    const float  *d_w_pix;   /* device [height][width], 4-byte aligned, NULL = 1: a weight per pixel (a mask, land fraction) */
+    int use_threshold; float threshold;                                 /* over: the weight of the pixels with sample > threshold */
+} ebcc_hip_area_spec;
+typedef struct { double sum, sum_sq, over; float min, max; } ebcc_hip_area_stat;   /* 32 bytes */
+/* Host only, no device: n_regions and (bounding, may be NULL) the bounding box of all regions, or -1 with a message for what
+ * the calls below refuse before touching a device: a null spec or list, n_regions == 0, a region that is empty or not inside
+ * the height x width frame, a w_row entry (all `height` are looked at) that is negative, a NaN or an Inf, a d_w_pix that is
+ * not 4-byte aligned, a geometry ebcc_hip_create refuses, an n_regions whose tables overflow.  d_w_pix is never followed. */
+long ebcc_hip_area_check(size_t height, size_t width, const ebcc_hip_area_spec *spec, ebcc_hip_region *bounding);
+/* unit level, the kernels alone: d_items [n_items][height][width], whole frames at any 4-byte aligned device address, are
+ * folded into out (host, [n_items][n_regions]).  The items and the weights are never written.  ctx: any context of the
+ * device.  0 = ok, 1 = error with nothing written: what the check refuses, null or misaligned items, n_items == 0, a d_w_pix
+ * with a negative value, a NaN or an Inf inside the bounding box of the regions (one device pass before the fold; weights no
+ * region holds are not looked at). */
+int ebcc_hip_area_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, size_t height, size_t width, const ebcc_hip_area_spec *spec,
+                       ebcc_hip_area_stat *out);
+/* Any number of one-frame streams: the bounding box of the regions is decoded - by the window decode, by the full decode when
+ * it is the frame - in batches of the context's capacity on the two engine sets, each into its set's audit buffer (a context
+ * runs one call at a time), and every batch is folded there into its own rows of out (host, [n_frames][n_regions]): batches
+ * take no turns.  Return 0 = ok, 1 = error (ebcc_hip_last_error).  Refused before anything is written: what the check
+ * refuses for the context's frames, a context for chunks of several frames, a frame without a stream or with one whose frame
+ * header does not parse, a d_w_pix with a negative value, a NaN or an Inf inside the bounding box (one device pass before any
+ * decode).  A stream found damaged inside a batch is refused as ebcc_hip_decode_frames refuses it: out is then unspecified
+ * within its bounds, and nothing outside it is written. */
+int ebcc_hip_series_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_area_spec *spec,
+                          ebcc_hip_area_stat *out);
 
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -

@@ -5,6 +5,7 @@
 #   tools/vgpr.sh 'gather_chunks|array_range|group_ranges' the chunk gather, the range of a device array and of many (host_codec.hip)
 #   tools/vgpr.sh 'frame_errors'                           the per-frame error statistics of the audit (host_codec.hip)
 #   tools/vgpr.sh 'time_fold'                              the fold of the reduce decode: statistics over time (host_codec.hip)
+#   tools/vgpr.sh 'area_'                                  the two launches of the area series and its weight check (host_codec.hip)
 # Compiled with the Makefile's code-generation flags; run it at two commits to compare their register use.
 pat="${1:-t1_}"
 cd "$(dirname "$0")/../ebcc_amd/csrc"
