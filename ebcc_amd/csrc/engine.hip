@@ -231,7 +231,7 @@ void push_frame_states(ebcc_hip_ctx *ctx, size_t n, hipStream_t s)
 
 // ---- optional kernel timing -------------------------------------------------------------------------
 struct TimedSpan { std::string name; hipEvent_t a, b; hipStream_t s; bool closed; };
-static bool g_timing = false;
+static std::atomic<bool> g_timing{false};     // (read by every launch site, written by ebcc_hip_timing_enable on any thread)
 static std::vector<TimedSpan> g_spans;
 static std::mutex g_spans_mutex;             // sub-batches are driven by their own host threads (and streams)
 
@@ -267,6 +267,14 @@ bool j2k_create(ebcc_hip_ctx *ctx);
 void j2k_destroy(ebcc_hip_ctx *ctx);
 }  // namespace ebcc
 
+// ebcc_hip_create and ebcc_hip_destroy take no device lock and make the engine's device current: the calling thread's own
+// device is put back on the way out, as DeviceScope (host_codec.hip) does for the entry points that do take the lock.
+struct CallerDevice {
+    int prev = -1;
+    CallerDevice() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+    ~CallerDevice() { if (prev >= 0) hipSetDevice(prev); }
+};
+
 extern "C" {
 
 const char *ebcc_hip_last_error(void) { return g_last_error.c_str(); }
@@ -274,6 +282,7 @@ const char *ebcc_hip_last_error(void) { return g_last_error.c_str(); }
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on)
 {
     (void) ctx;
+    std::lock_guard<std::mutex> lock(g_spans_mutex);
     if (on) {
         for (auto &t : g_spans) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
         g_spans.clear();
@@ -287,6 +296,7 @@ int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, 
     if (ctx) EBCC_HIP_CHECK(hipDeviceSynchronize());
     double tot = 0;
     long n = 0;
+    std::lock_guard<std::mutex> lock(g_spans_mutex);
     for (auto &t : g_spans)
         if (t.closed && t.name == name) {
             float ms = 0;
@@ -307,6 +317,7 @@ int ebcc_hip_device_count(void)
 
 ebcc_hip_ctx *ebcc_hip_create(int device, size_t max_frames, size_t height, size_t width)
 {
+    CallerDevice restore;
     return ebcc::create_engine(device, max_frames, height, width, 1);
 }
 
@@ -402,6 +413,7 @@ void ebcc_hip_destroy(ebcc_hip_ctx *ctx)
 {
     EBCC_API_TRY
     if (!ctx) return;
+    CallerDevice restore;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     for (ebcc_hip_ctx *c : ctx->lanes) ebcc_hip_destroy(c);

@@ -2501,14 +2501,26 @@ int ebcc_hip_encode_container(ebcc_hip_ctx *ctx, const float *d_array, const cod
 void ebcc_hip_release_engines(void)
 {
     EBCC_API_TRY
-    std::vector<std::pair<int, ebcc_hip_ctx *>> victims;
+    std::vector<int> devices;
     {
         std::lock_guard<std::mutex> lock(g_map_mutex);
-        for (auto &kv : g_ctx) victims.emplace_back(std::get<0>(kv.first), kv.second);
-        g_ctx.clear();
+        for (auto &kv : g_ctx)
+            if (std::find(devices.begin(), devices.end(), std::get<0>(kv.first)) == devices.end()) devices.push_back(std::get<0>(kv.first));
     }
-    for (auto &v : victims)                                               // (a call that is using the engine finishes first)
-        on_device(v.first, 0, [&] { ebcc_hip_destroy(v.second); return 0; });
+    // Device by device, the device's lock first and the map's inside it - the order of on_device -> get_context: a call that
+    // is using an engine finishes first, and a call that holds the device's lock never sees the map change under it
+    // (chunk_engines looks its two engines up one after the other).
+    for (int dev : devices)
+        on_device(dev, 0, [&] {
+            std::vector<ebcc_hip_ctx *> victims;
+            {
+                std::lock_guard<std::mutex> lock(g_map_mutex);
+                for (auto i = g_ctx.begin(); i != g_ctx.end();)
+                    if (std::get<0>(i->first) == dev) { victims.push_back(i->second); i = g_ctx.erase(i); } else ++i;
+            }
+            for (ebcc_hip_ctx *c : victims) ebcc_hip_destroy(c);
+            return 0;
+        });
     EBCC_API_CATCH_VOID
 }
 

@@ -10,6 +10,7 @@ written through the callback are read here.
 
 Only numpy and ctypes are needed (h5py objects are passed in by the caller).
 """
+import contextlib
 import ctypes
 import os
 import sys
@@ -575,30 +576,87 @@ _SUPER = 16         # batches handed to the engine per call by write_frames / re
 # request for fewer, a larger request replaces it (the old one is closed first), and when the device has no room for a new
 # engine every cached one is closed and the creation is tried once more.  close_cached() gives the memory back; callers
 # that hold datasets of many geometries in one process and want the memory between them call it themselves.
+#
+# Threads may share the cache.  One lock guards it, and a codec made while it is held, so two threads that ask for a missing
+# geometry at once get one engine.  The helpers of this module hold their codec for as long as they are inside it
+# (held_codec); a replacement and close_cached() wait for the last holder before they close an engine, so no call loses its
+# engine under it.  A codec taken with cached_codec() alone is not held: whoever keeps one across calls of other threads
+# that may replace or close it uses held_codec.  A holder that asks for a larger codec of its own geometry, or calls
+# close_cached(), from inside its `with` block would wait for itself.
 _codecs = {}
+_cache = threading.Condition()                                  # guards _codecs and _holders; notified when a holder leaves
+_holders = {}                                                   # codec -> the number of held_codec blocks that are inside it
+
+
+def _close_idle(c):
+    """close `c` once nobody holds it (the cache's lock held; it is released while waiting)"""
+    while _holders.get(c):
+        _cache.wait()
+    c.close()
+
+
+def _cached(height, width, max_frames, device, hold):
+    key, max_frames = (int(height), int(width), int(device)), int(max_frames)
+    with _cache:
+        while True:
+            c = _codecs.get(key)
+            if c is not None and c.ctx and c.max_frames >= max_frames:
+                break
+            if c is not None:
+                _close_idle(c)
+                if _codecs.get(key) is c:
+                    del _codecs[key]
+                continue                                        # (another thread may have made the larger one meanwhile)
+            try:
+                c = BatchCodec(height, width, max_frames, device)
+            except RuntimeError:
+                _close_all()                                    # (other geometries' engines may hold the memory)
+                if key in _codecs:
+                    continue
+                c = BatchCodec(height, width, max_frames, device)
+            _codecs[key] = c
+            break
+        if hold:
+            _holders[c] = _holders.get(c, 0) + 1
+        return c
+
+
+def _release(c):
+    with _cache:
+        _holders[c] -= 1
+        if not _holders[c]:
+            del _holders[c]
+        _cache.notify_all()
 
 
 def cached_codec(height, width, max_frames=256, device=0):
-    key = (int(height), int(width), int(device))
-    c = _codecs.get(key)
-    if c is not None and c.ctx and c.max_frames >= int(max_frames):
-        return c
-    if c is not None:
-        c.close()
-        del _codecs[key]
+    return _cached(height, width, max_frames, device, hold=False)
+
+
+@contextlib.contextmanager
+def held_codec(height, width, max_frames=256, device=0, codec=None):
+    """The cached codec of a geometry, held for the `with` block: no other thread's larger request and no close_cached()
+    closes it before the block is left.  `codec`: a codec of the caller's own, handed through as it is."""
+    if codec is not None:
+        yield codec
+        return
+    c = _cached(height, width, max_frames, device, hold=True)
     try:
-        c = BatchCodec(height, width, max_frames, device)
-    except RuntimeError:
-        close_cached()                                          # (other geometries' engines may hold the memory)
-        c = BatchCodec(height, width, max_frames, device)
-    _codecs[key] = c
-    return c
+        yield c
+    finally:
+        _release(c)
+
+
+def _close_all():
+    for key, c in list(_codecs.items()):
+        _close_idle(c)
+        if _codecs.get(key) is c:
+            del _codecs[key]
 
 
 def close_cached():
-    for c in _codecs.values():
-        c.close()
-    _codecs.clear()
+    with _cache:
+        _close_all()
 
 
 import atexit  # noqa: E402
@@ -631,19 +689,19 @@ def write_frames(dset, data, base_cr, residual_opt=("none", None), batch=256, co
     flat = data.reshape((-1, h, w))
     lead = data.shape[:-2]
     cfg = frame_config(h, w, base_cr, residual_opt)
-    codec = codec or cached_codec(h, w, min(batch, len(flat)))
-    step = _SUPER * codec.max_frames                            # (several batches per call: they alternate between two engine sets)
     reports = []
-    for lo in range(0, len(flat), step):
-        if hard:
-            streams, report = codec.encode(flat[lo:lo + step], cfg, hard=True, max_rounds=max_rounds)
-            _not_met(report, f"{dset.name}, frames {lo}..{lo + len(report) - 1}")
-            reports.append(report)
-        else:
-            streams = codec.encode(flat[lo:lo + step], cfg)
-        for i, s in enumerate(streams):
-            idx = np.unravel_index(lo + i, lead) if lead else ()
-            dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
+    with held_codec(h, w, min(batch, len(flat)), codec=codec) as codec:
+        step = _SUPER * codec.max_frames                        # (several batches per call: they alternate between two engine sets)
+        for lo in range(0, len(flat), step):
+            if hard:
+                streams, report = codec.encode(flat[lo:lo + step], cfg, hard=True, max_rounds=max_rounds)
+                _not_met(report, f"{dset.name}, frames {lo}..{lo + len(report) - 1}")
+                reports.append(report)
+            else:
+                streams = codec.encode(flat[lo:lo + step], cfg)
+            for i, s in enumerate(streams):
+                idx = np.unravel_index(lo + i, lead) if lead else ()
+                dset.id.write_direct_chunk(tuple(int(v) for v in idx) + (0, 0), s, filter_mask=0)
     return np.concatenate(reports).reshape(tuple(lead)) if hard else None
 
 
@@ -686,13 +744,13 @@ def write_variables(items, batch=256, codec=None, hard=False, max_rounds=0):
         base_cr, opt = filter_options(dset)
         groups.append((frames, base_cr, opt))
         total += len(frames)
-    codec = codec or cached_codec(h, w, min(batch, total))
     report = None
-    if hard:
-        coded, report = codec.encode_groups(groups, hard=True, max_rounds=max_rounds)
-        _not_met(report, "write_variables")
-    else:
-        coded = codec.encode_groups(groups)
+    with held_codec(h, w, min(batch, total), codec=codec) as codec:
+        if hard:
+            coded, report = codec.encode_groups(groups, hard=True, max_rounds=max_rounds)
+            _not_met(report, "write_variables")
+        else:
+            coded = codec.encode_groups(groups)
     for (dset, first, _), streams in zip(items, coded):
         lead = dset.shape[:-2]
         for i, s in enumerate(streams):
@@ -717,17 +775,17 @@ def audit_dataset(dset, data, batch=256, codec=None):
     flat = data.reshape((-1, h, w))
     n = len(flat)
     _base_cr, (mode, err) = filter_options(dset)
-    codec = codec or cached_codec(h, w, min(batch, n))
-    step = _SUPER * codec.max_frames
     out = np.zeros(n, FRAME_ERROR)
-    for lo in range(0, n, step):
-        part = flat[lo:lo + step]
-        bound = None
-        if mode == "max_error_target":
-            bound = np.float32(err)
-        elif mode == "relative_error_target":
-            bound = np.float32(err) * (part.max(axis=(1, 2)) - part.min(axis=(1, 2))).astype(np.float32)
-        out[lo:lo + len(part)] = codec.audit(_read_chunks(dset, range(lo, lo + len(part))), part, bound)
+    with held_codec(h, w, min(batch, n), codec=codec) as codec:
+        step = _SUPER * codec.max_frames
+        for lo in range(0, n, step):
+            part = flat[lo:lo + step]
+            bound = None
+            if mode == "max_error_target":
+                bound = np.float32(err)
+            elif mode == "relative_error_target":
+                bound = np.float32(err) * (part.max(axis=(1, 2)) - part.min(axis=(1, 2))).astype(np.float32)
+            out[lo:lo + len(part)] = codec.audit(_read_chunks(dset, range(lo, lo + len(part))), part, bound)
     return out.reshape(tuple(lead))
 
 
@@ -755,33 +813,33 @@ def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
     (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
     window = None if (nrows, ncols) == (h, w) else (row0, col0, nrows, ncols)
     out = np.empty((n, nrows, ncols), np.float32)
-    codec = codec or cached_codec(h, w, min(batch, n))
-    step = _SUPER * codec.max_frames
+    with held_codec(h, w, min(batch, n), codec=codec) as codec:
+        step = _SUPER * codec.max_frames
 
-    def fetch(lo, box):
-        try:
-            box.append(_read_chunks(dset, range(lo, min(n, lo + step))))
-        except BaseException as e:                                  # (handed to the caller's thread)
-            box.append(e)
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, range(lo, min(n, lo + step))))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
 
-    box = []
-    t0 = time.perf_counter()
-    fetch(0, box)
-    if os.environ.get("EBCC_H5_TIMING"):
-        print(f"h5_batch.read_frames: first {min(n, step)} chunks fetched in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
-    for lo in range(0, n, step):
-        raw = box[0]
-        if isinstance(raw, BaseException):
-            raise raw
-        box, t = [], None
-        if lo + step < n:
-            t = threading.Thread(target=fetch, args=(lo + step, box))
-            t.start()
-        try:
-            codec.decode(raw, out=out[lo:lo + len(raw)], window=window)
-        finally:
-            if t:
-                t.join()
+        box = []
+        t0 = time.perf_counter()
+        fetch(0, box)
+        if os.environ.get("EBCC_H5_TIMING"):
+            print(f"h5_batch.read_frames: first {min(n, step)} chunks fetched in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
+        for lo in range(0, n, step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < n:
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                codec.decode(raw, out=out[lo:lo + len(raw)], window=window)
+            finally:
+                if t:
+                    t.join()
     return out.reshape(tuple(lead) + (nrows, ncols))
 
 
@@ -807,18 +865,19 @@ def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=
     n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
     if b.max() >= n_bins:
         raise ValueError(f"a frame names bin {int(b.max())} of {n_bins}")
-    codec = codec or cached_codec(h, w, min(batch, len(named)))
-    step = _SUPER * codec.max_frames
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
+        step = _SUPER * codec.max_frames
 
-    def fetch(lo, box):
-        try:
-            box.append(_read_chunks(dset, named[lo:lo + step]))
-        except BaseException as e:                                  # (handed to the caller's thread)
-            box.append(e)
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, named[lo:lo + step]))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
 
-    box = []
-    fetch(0, box)
-    with codec.reduce_state(n_bins, (row0, col0, nrows, ncols), threshold) as state:
+        box = []
+        fetch(0, box)
+        state = stack.enter_context(codec.reduce_state(n_bins, (row0, col0, nrows, ncols), threshold))
         for lo in range(0, len(named), step):
             raw = box[0]
             if isinstance(raw, BaseException):
@@ -848,17 +907,18 @@ def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=
     named = np.arange(n) if frames is None else np.asarray(frames)
     if named.ndim != 1 or len(named) < 1 or named.dtype.kind not in "iu" or named.min() < 0 or named.max() >= n:
         raise ValueError(f"frames must be a non-empty list of integers in [0, {n})")
-    codec = codec or cached_codec(h, w, min(batch, len(named)))
-    step = _SUPER * codec.max_frames
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
+        step = _SUPER * codec.max_frames
 
-    def fetch(lo, box):
-        try:
-            box.append(_read_chunks(dset, named[lo:lo + step]))
-        except BaseException as e:                                  # (handed to the caller's thread)
-            box.append(e)
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, named[lo:lo + step]))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
 
-    area = _Area(codec, regions, w_row, w_pix, threshold)
-    try:
+        area = _Area(codec, regions, w_row, w_pix, threshold)
+        stack.callback(area.close)
         box, parts = [], []
         fetch(0, box)
         for lo in range(0, len(named), step):
@@ -875,8 +935,6 @@ def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=
                 if t:
                     t.join()
         return SeriesResult(np.concatenate(parts), area.weight())
-    finally:
-        area.close()
 
 
 def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):
@@ -893,16 +951,16 @@ def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):
     order = np.argsort(b[:, 0], kind="stable")
     b = b[order]
     frames = np.unique(b[:, 0])                                         # (sorted)
-    codec = codec or cached_codec(h, w, min(batch, len(frames)))
     out = np.empty((len(b), int(rows), int(cols)), np.float32)
-    step = _SUPER * codec.max_frames
-    for lo in range(0, len(frames), step):
-        part = frames[lo:lo + step]
-        raw = _read_chunks(dset, part)
-        e0, e1 = np.searchsorted(b[:, 0], part[0], "left"), np.searchsorted(b[:, 0], part[-1], "right")
-        local = b[e0:e1].copy()
-        local[:, 0] = np.searchsorted(part, local[:, 0])
-        codec.decode_boxes(raw, local, rows, cols, out=out[e0:e1])
+    with held_codec(h, w, min(batch, len(frames)), codec=codec) as codec:
+        step = _SUPER * codec.max_frames
+        for lo in range(0, len(frames), step):
+            part = frames[lo:lo + step]
+            raw = _read_chunks(dset, part)
+            e0, e1 = np.searchsorted(b[:, 0], part[0], "left"), np.searchsorted(b[:, 0], part[-1], "right")
+            local = b[e0:e1].copy()
+            local[:, 0] = np.searchsorted(part, local[:, 0])
+            codec.decode_boxes(raw, local, rows, cols, out=out[e0:e1])
     res = np.empty_like(out)
     res[order] = out
     return res

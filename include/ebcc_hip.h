@@ -17,6 +17,16 @@
  * batch is touched, also by a call that fails.  Results do not depend on the alignment; the kernels use wider accesses
  * where base and frame size allow them, and a decode output on a 256-byte boundary is written directly instead of through
  * one device-to-device copy of the batch.  (tests/test_caller_buffers_gpu.py)
+ *
+ * Threads: every entry point that codes, decodes, audits, reduces or folds on a context - and ebcc_hip_upload, _download,
+ * _prepare and _release_second_set - takes the lock of the context's device for the call, as the entry points of
+ * include/ebcc_codec.h do for the engines they cache per (device, frame geometry); ebcc_hip_release_engines takes it device by
+ * device.  Calls on one device run one after the other, so threads may share a context, each with buffers of its own; calls on
+ * different devices do not wait for each other.  NOT serialised: ebcc_hip_create / _destroy and ebcc_hip_malloc / _free /
+ * _memcpy_h2d / _memcpy_d2h - safe beside any running call, and they leave the calling thread's current device as it was -, the
+ * unit hooks ebcc_hip_spiht_* and ebcc_hip_j2k_* - their context must not be in use by another thread - and
+ * ebcc_hip_timing_enable / _timing_read.  Destroying a context while a call on it is running or waiting is the caller's error.
+ * ebcc_hip_last_error is per thread.  (tests/test_threads_gpu.py)
  */
 #ifndef EBCC_HIP_H
 #define EBCC_HIP_H
