@@ -567,6 +567,98 @@ int ebcc_hip_spiht_decode_prefix(ebcc_hip_ctx *ctx, size_t n_frames, const size_
     EBCC_API_CATCH(1)
 }
 
+// The residual layer as BatchEncode::residual_layer queues it (batch_codec.hip, src/ebcc_codec.c:730-748), every frame active
+int ebcc_hip_residual_prepare(ebcc_hip_ctx *ctx, const float *d_data, const float *d_decoded, size_t n_frames, const size_t *budget_bits,
+                              float *rmin, float *rmax, int *dc, uint8_t **out_streams, size_t *out_sizes)
+{
+    EBCC_API_TRY
+    if (check_batch(ctx, n_frames, "ebcc_hip_residual_prepare")) return 1;
+    for (size_t f = 0; f < n_frames; f++) {
+        if (budget_bits[f] == 0 || (budget_bits[f] + 121 + 7) / 8 > ctx->rb.stream_words * 4 - 64) {
+            set_error("ebcc_hip_residual_prepare: a budget of %zu bits is zero or exceeds the stream slot", budget_bits[f]);
+            return 1;
+        }
+        ctx->h_active[f] = 1;
+        ctx->h_u64a[f] = (unsigned long long) budget_bits[f] + 128;       // bits0 = trunc_bits + 128
+    }
+    hipStream_t s = ctx->stream;
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_active, ctx->h_active, n_frames * sizeof(int), hipMemcpyHostToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_u64a, ctx->h_u64a, n_frames * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    launch_residual_minmax(d_data, d_decoded, (int) n_frames, ctx->n_pix, ctx->rb.fs, s);
+    launch_pad_and_dc(d_data, d_decoded, ctx->rb, (int) n_frames, ctx->d_active, s);
+    launch_analysis(ctx->rb, (int) n_frames, ctx->d_active, s);
+    launch_residual_budget(ctx->rb, (int) n_frames, ctx->d_u64a, ctx->d_active, s);
+    launch_spiht_encode(ctx->rb, (int) n_frames, ctx->d_u64a, ctx->d_active, s);
+    launch_whole_stream_cut(ctx->rb, (int) n_frames, ctx->d_u64b, ctx->d_active, s);
+    if (collect_streams(ctx, n_frames, out_streams, out_sizes)) return 1;
+    for (size_t f = 0; f < n_frames; f++) { rmin[f] = ctx->h_fs[f].rmin; rmax[f] = ctx->h_fs[f].rmax; dc[f] = (int) ctx->h_fs[f].dc; }
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
+// One round's probes of the truncation search (BatchEncode::truncation_search): the state a round's advance leaves
+// (search.hip: k_trunc_advance, k_trunc_advance_multi) is written by the host, the probes are the search's launchers
+int ebcc_hip_residual_probe(ebcc_hip_ctx *ctx, const float *d_data, const float *d_decoded, size_t n_frames, int slots, size_t n_probes,
+                            const int *frame_of, const size_t *cut_bits, const int *active, const float *exit_above,
+                            uint32_t *maxerr_bits, double *err_sum)
+{
+    EBCC_API_TRY
+    if (check_batch(ctx, n_frames, "ebcc_hip_residual_probe")) return 1;
+    if (n_probes < 1 || (slots ? n_probes * 8 > 65535 : n_probes != n_frames)) {     // (a launch of the slots takes 8 pieces a slot in grid y)
+        set_error("ebcc_hip_residual_probe: bad number of probes");
+        return 1;
+    }
+    for (size_t i = 0; i < n_probes; i++) {
+        if (cut_bits[i] <= 128) { set_error("ebcc_hip_residual_probe: a cut must exceed 128 bits"); return 1; }
+        if (frame_of[i] < 0 || (size_t) frame_of[i] >= n_frames || (!slots && (size_t) frame_of[i] != i)) {
+            set_error("ebcc_hip_residual_probe: probe %zu names frame %d", i, frame_of[i]);
+            return 1;
+        }
+    }
+    hipStream_t s = ctx->stream;
+    fetch_frame_states(ctx, n_frames);
+    if (!slots) {
+        for (size_t f = 0; f < n_frames; f++) {
+            ctx->h_u64b[f] = cut_bits[f];
+            ctx->h_active[f] = active[f] ? 1 : 0;
+            ctx->h_fs[f].exit_above = exit_above[f];
+            ctx->h_fs[f].maxerr_bits = maxerr_bits[f]; ctx->h_fs[f].err_sum = err_sum[f];      // (what an inactive frame must keep)
+        }
+        push_frame_states(ctx, n_frames);
+        EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_u64b, ctx->h_u64b, n_frames * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_active, ctx->h_active, n_frames * sizeof(int), hipMemcpyHostToDevice, s));
+        launch_prefix_synthesis_stats(d_data, d_decoded, ctx->rb, (int) n_frames, ctx->d_u64b, ctx->d_active, s);
+        fetch_frame_states(ctx, n_frames);
+        for (size_t f = 0; f < n_frames; f++) { maxerr_bits[f] = ctx->h_fs[f].maxerr_bits; err_sum[f] = ctx->h_fs[f].err_sum; }
+        // (the encoder's own probes of this context are exact again)
+        for (size_t f = 0; f < n_frames; f++) ctx->h_fs[f].exit_above = 0.0f;
+        push_frame_states(ctx, n_frames);
+        wait_stream(s);
+        return 0;
+    }
+    if (!ensure_cut_slots(ctx, (int) n_probes)) { set_error("ebcc_hip_residual_probe: no cut slots for %zu probes of this grid", n_probes); return 1; }
+    const CutSlots &cs = ctx->cut;
+    std::vector<FrameState> vfs(n_probes);
+    std::vector<unsigned long long> bits(n_probes);
+    std::vector<int> on(n_probes), of(n_probes);
+    for (size_t v = 0; v < n_probes; v++) {
+        bits[v] = cut_bits[v]; on[v] = active[v] ? 1 : 0; of[v] = frame_of[v];
+        vfs[v] = ctx->h_fs[frame_of[v]];                                     // (what a probe reads of the frame's state)
+        vfs[v].exit_above = exit_above[v];
+        vfs[v].maxerr_bits = maxerr_bits[v]; vfs[v].err_sum = err_sum[v];
+    }
+    EBCC_HIP_CHECK(hipMemcpyAsync(cs.fs, vfs.data(), n_probes * sizeof(FrameState), hipMemcpyHostToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(cs.bits, bits.data(), n_probes * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(cs.active, on.data(), n_probes * sizeof(int), hipMemcpyHostToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(cs.frame_of, of.data(), n_probes * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_prefix_synthesis_slots(d_data, d_decoded, ctx->rb, cs, (int) n_probes, s);
+    EBCC_HIP_CHECK(hipMemcpyAsync(vfs.data(), cs.fs, n_probes * sizeof(FrameState), hipMemcpyDeviceToHost, s));
+    wait_stream(s);
+    for (size_t v = 0; v < n_probes; v++) { maxerr_bits[v] = vfs[v].maxerr_bits; err_sum[v] = vfs[v].err_sum; }
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
 // parse + validate the 15-byte IMS header on the host (spiht_re.c:480-503)
 }  // extern "C"
 // header of a SPIHT stream against the context's grid, and a bit budget the decoder can work with (non-zero: reject)

@@ -7,6 +7,7 @@
 #include "../../include/ebcc_hip.h"
 #include "engine.hpp"
 #include "j2k.hpp"
+#include "search.hpp"
 
 namespace ebcc {
 
@@ -609,6 +610,41 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_emulated_decode(ebcc_hip
     EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
     wait_stream(s);
     for (size_t f = 0; f < n_frames; f++) { nbad[f] = jf[f].nbad; err_sum[f] = jf[f].err_sum; }
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
+// After ebcc_hip_j2k_encode: one round of a rate search for the active frames (batch_codec.hip: BatchEncode::rate_search,
+// enqueue_rounds), with the per-frame scalars the search's advance would have written (search.hip: k_search_advance)
+__attribute__((visibility("default"))) int ebcc_hip_j2k_probe(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const float *cr,
+                                                              const float *target, const uint32_t *bad_limit, const int *keep,
+                                                              const int *active, int keep_field, unsigned long long *nbad,
+                                                              double *err_sum, int *stream_bytes, float *d_field_out)
+{
+    EBCC_API_TRY
+    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames || keep_field < 0 || keep_field > 2) { set_error("ebcc_hip_j2k_probe: bad batch"); return 1; }
+    EBCC_HIP_CHECK(hipSetDevice(ctx->device));
+    J2kBuffers &jb = *static_cast<J2kBuffers *>(ctx->j2k);
+    hipStream_t s = ctx->stream;
+    std::vector<J2kFrame> jf(n_frames);
+    EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
+    wait_stream(s);
+    for (size_t f = 0; f < n_frames; f++) {
+        ctx->h_active[f] = active[f] ? 1 : 0;
+        if (!active[f]) continue;
+        jf[f].cr = cr[f]; jf[f].target = target[f]; jf[f].bad_limit = bad_limit[f]; jf[f].keep = keep[f] ? 1 : 0;
+    }
+    EBCC_HIP_CHECK(hipMemcpyAsync(jb.jf, jf.data(), sizeof(J2kFrame) * n_frames, hipMemcpyHostToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->d_active, ctx->h_active, sizeof(int) * n_frames, hipMemcpyHostToDevice, s));
+    launch_j2k_rate(jb, (int) n_frames, ctx->d_active, s, nullptr);
+    launch_j2k_probe_decode(d_frames, jb, (int) n_frames, ctx->d_active, s, keep_field);
+    if (d_field_out) EBCC_HIP_CHECK(hipMemcpyAsync(d_field_out, jb.DEC, n_frames * ctx->n_pix * sizeof(float), hipMemcpyDeviceToDevice, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
+    wait_stream(s);
+    for (size_t f = 0; f < n_frames; f++) {
+        if (!active[f]) continue;
+        nbad[f] = jf[f].nbad; err_sum[f] = jf[f].err_sum; stream_bytes[f] = probe_stream_bytes(1, jf[f].body_bytes);
+    }
     return 0;
     EBCC_API_CATCH(1)
 }

@@ -32,8 +32,7 @@ struct FrameState {
     // ---- probe statistics (:477-513)
     unsigned int maxerr_bits;               // float bits of max |x - (d + r)| (non-negative => monotone)
     double err_sum;
-    int err_sum_inexact;
-    unsigned long long nbad;                // count(|x - d| > target)
+    unsigned long long nbad;               // count(|x - d| > target)
     float exit_above;                       // > 0: a probe of the truncation search may stop once its running maximum exceeds
                                             // this (the search then only asks "max error > target?", search.hip); 0: exact
     // ---- decode

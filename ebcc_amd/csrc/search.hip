@@ -4,8 +4,6 @@
 namespace ebcc {
 namespace {
 
-constexpr int kMainHeaderBytes = 135;      // SOC, SIZ, COD, QCD, COM of every codestream the codec writes
-
 // ---- /root/reference/src/ebcc_codec.c:545-596, one probe per call --------------------------------------
 // returns true and sets `out` if a probe at rate `out` is needed next
 __device__ bool rs_next(DevRateSearch &r, float &out)
@@ -121,8 +119,8 @@ __global__ void k_search_advance(DevChunk *chunks, J2kFrame *jf, int *active, in
         DevProbe rec{jf[t0].cr, 0, 0ull, 0.0, 1, 0};
         int body = 0;
         for (int t = 0; t < tiles; t++) { rec.nbad += jf[t0 + t].nbad; rec.err_sum += jf[t0 + t].err_sum; body += jf[t0 + t].body_bytes; }
-        rec.stream_bytes = kMainHeaderBytes + tiles * 14 + body + 2;     // main header, SOT + SOD per tile, EOC
-        rec.complete = jf[t0].bad_limit == 0 || rec.nbad < jf[t0].bad_limit;   // (a count below the limit: no piece left early)
+        rec.stream_bytes = probe_stream_bytes(tiles, body);
+        rec.complete = probe_complete(jf[t0].bad_limit, rec.nbad);
         // search 0's probes change the layer assignment the codestream is written from; only those that also stored
         // their field leave the engine in the state of one rate (decode and assignment), the others in none
         if (k == 0) C.state_cr = keeps_field(k, R.phase) ? rec.cr : -1.0f;

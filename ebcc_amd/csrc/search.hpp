@@ -22,6 +22,16 @@ struct DevProbe {                  // outcome of the base layer coded at one rat
     int complete;                  // 0: the probe may have stopped counting early (J2kFrame::bad_limit): nbad is a lower bound that
     int pad;                       //    already settles "infeasible", err_sum is partial - a search's RESULT never rests on such a record
 };
+// The two early exits of the probes, as the searches rely on them (tests/test_probe_j2k_gpu.py, tests/test_probe_residual_gpu.py):
+//   * rate probe, J2kFrame::bad_limit = L > 0 (statistics-only probes alone: a probe that stores its field counts everything
+//     whatever L is).  N the exact count: N < L -> nbad == N and err_sum is the full sum (probe_complete below);
+//     otherwise L <= nbad <= N, err_sum partial.
+//   * truncation probe, FrameState::exit_above = T > 0.  M the exact maximum: M <= T -> maxerr_bits and err_sum are those of
+//     the exact probe (M == T included); otherwise T < maxerr <= M, err_sum unspecified.
+// length of the codestream a probe's layer assignment would be written as: main header, SOT + SOD per tile, EOC
+__host__ __device__ inline int probe_stream_bytes(int tiles, int body_bytes) { return 135 + tiles * 14 + body_bytes + 2; }
+// a count below the limit: no piece left early
+__host__ __device__ inline bool probe_complete(unsigned int bad_limit, unsigned long long nbad) { return bad_limit == 0 || nbad < bad_limit; }
 
 // :545-596 as a resumable state machine (phases 0-4 as in the reference's three loops and final encode)
 struct DevRateSearch {

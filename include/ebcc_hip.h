@@ -24,7 +24,7 @@
  * device.  Calls on one device run one after the other, so threads may share a context, each with buffers of its own; calls on
  * different devices do not wait for each other.  NOT serialised: ebcc_hip_create / _destroy and ebcc_hip_malloc / _free /
  * _memcpy_h2d / _memcpy_d2h - safe beside any running call, and they leave the calling thread's current device as it was -, the
- * unit hooks ebcc_hip_spiht_* and ebcc_hip_j2k_* - their context must not be in use by another thread - and
+ * unit hooks ebcc_hip_spiht_*, ebcc_hip_residual_* and ebcc_hip_j2k_* - their context must not be in use by another thread - and
  * ebcc_hip_timing_enable / _timing_read.  Destroying a context while a call on it is running or waiting is the caller's error.
  * ebcc_hip_last_error is per thread.  (tests/test_threads_gpu.py)
  */
@@ -89,6 +89,25 @@ int ebcc_hip_spiht_decode_prefix(ebcc_hip_ctx *ctx, size_t n_frames, const size_
 int ebcc_hip_spiht_coeffs(ebcc_hip_ctx *ctx, const float *d_images, size_t n_frames, int32_t *coeffs, int *dc);
 size_t ebcc_hip_padded_pixels(const ebcc_hip_ctx *ctx);
 
+/* Test entry points of the truncation search's probes (src/ebcc_codec.c:745-754, :777-795): they call the launchers the
+ * encoder calls, in its order, so that what the tests run is what the search runs (tests/test_probe_residual_gpu.py).
+ * _prepare: the residual layer of the encoder for r = d_data - d_decoded (both [n_frames][height][width], 4-byte aligned) with a
+ * SPIHT budget of budget_bits[f] bits (> 0; the encoder's is 8 x the base layer's bytes): residual range, padding and DC,
+ * analysis, budget, SPIHT.  rmin / rmax / dc (host, [n_frames]) and the streams (malloc'd, free_buffer) come back; the
+ * bookkeeping stays in the context for the probes. */
+int ebcc_hip_residual_prepare(ebcc_hip_ctx *ctx, const float *d_data, const float *d_decoded, size_t n_frames, const size_t *budget_bits,
+                              float *rmin, float *rmax, int *dc, uint8_t **out_streams, size_t *out_sizes);
+/* _probe, after _prepare on this context with the same d_data / d_decoded: n_probes probes, probe i = the cut of cut_bits[i] bits
+ * (> 128) of frame frame_of[i], counted where active[i] is set, with FrameState::exit_above = exit_above[i] (0: exact).
+ * slots == 0: one probe per frame through the one-cut-per-round launcher (n_probes == n_frames, frame_of[i] == i, active the
+ * mask); slots != 0: any number of probes a frame, at most 8191 a call, through the cut slots of the look-ahead, set up as the
+ * search's advance sets them up.  maxerr_bits[i] = float bits of max |x - (d + r)|, err_sum[i] = sum(x - (d + r)); both arrays are read first and what
+ * they hold is what an inactive probe's entry holds afterwards.  0 = ok, 1 = error (a cut of 128 bits or fewer, a frame out of
+ * range, a grid the cut slots do not take). */
+int ebcc_hip_residual_probe(ebcc_hip_ctx *ctx, const float *d_data, const float *d_decoded, size_t n_frames, int slots, size_t n_probes,
+                            const int *frame_of, const size_t *cut_bits, const int *active, const float *exit_above,
+                            uint32_t *maxerr_bits, double *err_sum);
+
 /* ---- JPEG 2000 base layer (unit level) ----------------------------------------------------------
  * Batch forms of j2k_encode_internal / j2k_decode_internal, /root/reference/src/ebcc_codec.c:105-180,
  * :1092-1136 (the reference reaches OpenJPEG there).  Frames are scaled to u16 with their own min/max as
@@ -99,6 +118,16 @@ int ebcc_hip_j2k_encode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frame
  * place from the encoder's code-block slots; nbad[f] = count(|x - d| > target[f]), err_sum[f] = sum(x - d). */
 int ebcc_hip_j2k_emulated_decode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const float *target,
                                  float *d_out, unsigned long long *nbad, double *err_sum);
+/* Test entry point of the rate search's probes (src/ebcc_codec.c:545-596), after ebcc_hip_j2k_encode on this context with the
+ * same d_frames, any number of times: one round's work - rate allocation, then the probe decode - through the launchers the
+ * search's rounds call (tests/test_probe_j2k_gpu.py).  Frames with active[f] set are probed at rate cr[f] against target[f]
+ * with J2kFrame::bad_limit = bad_limit[f] (0: count everything) and J2kFrame::keep = keep[f]; keep_field 0: statistics only,
+ * 1: every probed frame stores its field, 2: the frames with keep[f] do.  nbad / err_sum / stream_bytes (host, [n_frames]; the
+ * length is the search's own formula) are written for the probed frames only.  d_field_out (device, may be NULL) receives the
+ * engine's decoded fields [n_frames][height][width] as they lie after the probe. */
+int ebcc_hip_j2k_probe(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const float *cr, const float *target,
+                       const uint32_t *bad_limit, const int *keep, const int *active, int keep_field, unsigned long long *nbad,
+                       double *err_sum, int *stream_bytes, float *d_field_out);
 /* j2k_decode_internal for a batch of codestreams with (minval, maxval) pairs in minmax [n][2] */
 int ebcc_hip_j2k_decode(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                         const float *minmax, float *d_out);

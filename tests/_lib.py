@@ -247,6 +247,12 @@ def product():
                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
             lib.ebcc_hip_j2k_decode.argtypes = [ctypes.c_void_p, c_void_pp, c_size_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_void_p]
+        lib.ebcc_hip_j2k_probe.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + \
+            [ctypes.c_int] + [ctypes.c_void_p] * 4
+        lib.ebcc_hip_residual_prepare.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_size_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp, c_size_p]
+        lib.ebcc_hip_residual_probe.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+                                                ctypes.c_size_t] + [ctypes.c_void_p] * 6
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         if hasattr(lib, "ebcc_hip_encode_frames"):
             lib.ebcc_hip_encode_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -299,6 +305,11 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+def _dptr(d):
+    """a DeviceArray, or a raw device address (a frame inside a larger buffer)"""
+    return d.ptr if isinstance(d, DeviceArray) else int(d)
 
 
 class Context:
@@ -414,6 +425,63 @@ class Context:
         res = out.get(np.float32, (n, self.h, self.w))
         out.free()
         return res
+
+    # ---- probes of the two searches (test entry points over the encoder's own launchers)
+    PROBE_SENTINEL = (np.uint64(0xDEADBEEFCAFEF00D), np.float64(-1.25e300), np.int32(-77))
+    RESID_SENTINEL = (np.uint32(0x7FC0BEEF), np.float64(-2.5e300))
+
+    def j2k_probe(self, d_frames, n, cr, target, bad_limit=None, keep=None, active=None, keep_field=1, want_field=False):
+        """One round of a rate search after j2k_encode: (nbad, err_sum, stream_bytes, field or None); the entries of frames
+        that are not active hold PROBE_SENTINEL."""
+        crs = np.ascontiguousarray(np.broadcast_to(np.asarray(cr, np.float32), (n,)))
+        tg = np.ascontiguousarray(np.broadcast_to(np.asarray(target, np.float32), (n,)))
+        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if bad_limit is None else bad_limit, np.uint32), (n,)))
+        kp = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if keep is None else keep, np.int32), (n,)))
+        act = np.ascontiguousarray(np.broadcast_to(np.asarray(1 if active is None else active, np.int32), (n,)))
+        nbad = np.full(n, self.PROBE_SENTINEL[0], np.uint64)
+        esum = np.full(n, self.PROBE_SENTINEL[1], np.float64)
+        size = np.full(n, self.PROBE_SENTINEL[2], np.int32)
+        out = DeviceArray(nbytes=n * self.h * self.w * 4) if want_field else None
+        rc = self.lib.ebcc_hip_j2k_probe(self.ptr, d_frames.ptr, n, crs.ctypes.data, tg.ctypes.data, lim.ctypes.data, kp.ctypes.data,
+                                         act.ctypes.data, keep_field, nbad.ctypes.data, esum.ctypes.data, size.ctypes.data,
+                                         out.ptr if out else None)
+        assert rc == 0, self.lib.ebcc_hip_last_error()
+        field = None
+        if out:
+            field = out.get(np.float32, (n, self.h, self.w))
+            out.free()
+        return nbad, esum, size, field
+
+    def residual_prepare(self, d_x, d_d, n, budget_bits):
+        """The encoder's residual layer for r = x - d (device pointers): (rmin, rmax, dc, streams)."""
+        bb = (ctypes.c_size_t * n)(*[int(b) for b in budget_bits])
+        rmin, rmax, dc = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        outs = (ctypes.c_void_p * n)()
+        sizes = (ctypes.c_size_t * n)()
+        rc = self.lib.ebcc_hip_residual_prepare(self.ptr, _dptr(d_x), _dptr(d_d), n, bb, rmin.ctypes.data, rmax.ctypes.data,
+                                                dc.ctypes.data, outs, sizes)
+        assert rc == 0, self.lib.ebcc_hip_last_error()
+        streams = []
+        for f in range(n):
+            streams.append(ctypes.string_at(outs[f], sizes[f]))
+            self.lib.free_buffer(outs[f])
+        return rmin, rmax, dc, streams
+
+    def residual_probe(self, d_x, d_d, n, frame_of, cut_bits, active=None, exit_above=None, slots=False, rc_only=False):
+        """Probes of the truncation search: (maxerr_bits, err_sum) per probe; inactive probes hold RESID_SENTINEL."""
+        m = len(cut_bits)
+        fo = np.ascontiguousarray(frame_of, np.int32)
+        cb = np.ascontiguousarray(cut_bits, np.uint64)
+        act = np.ascontiguousarray(np.broadcast_to(np.asarray(1 if active is None else active, np.int32), (m,)))
+        ea = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if exit_above is None else exit_above, np.float32), (m,)))
+        bits = np.full(m, self.RESID_SENTINEL[0], np.uint32)
+        esum = np.full(m, self.RESID_SENTINEL[1], np.float64)
+        rc = self.lib.ebcc_hip_residual_probe(self.ptr, _dptr(d_x), _dptr(d_d), n, 1 if slots else 0, m, fo.ctypes.data,
+                                              cb.ctypes.data, act.ctypes.data, ea.ctypes.data, bits.ctypes.data, esum.ctypes.data)
+        if rc_only:
+            return rc
+        assert rc == 0, self.lib.ebcc_hip_last_error()
+        return bits, esum
 
     # ---- frame codec
     def encode_frames(self, frames, cfg):
