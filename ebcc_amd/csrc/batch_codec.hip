@@ -948,7 +948,7 @@ int decode_batch(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t 
             keep_row = (size_t) g.nblocks;
             keep.resize(n * keep_row);
             boxes_reserve(ctx, region.n, sizeof(J2kBoxEntry) + sizeof(J2kPlacement));
-            J2kBoxEntry *const h_table = static_cast<J2kBoxEntry *>(ctx->h_boxes), *const table = static_cast<J2kBoxEntry *>(ctx->d_boxes);
+            J2kBoxEntry *const h_table = static_cast<J2kBoxEntry *>(ctx->boxes.h), *const table = static_cast<J2kBoxEntry *>(ctx->boxes.d);
             dev.list = J2kBoxList{h_table, table, reinterpret_cast<J2kPlacement *>(h_table + region.n), reinterpret_cast<J2kPlacement *>(table + region.n), region.n, 0, 0};
             if (!j2k_list_check("list decode", g, n, local.data(), local.size(), region.out_floats, keep.data(), h_table, dev.list.h_place, j2k_first_fused(jb),
                                 &dev.list.rows, &dev.list.cols)) return 1;

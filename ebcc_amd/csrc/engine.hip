@@ -155,19 +155,34 @@ void stage_download(ebcc_hip_ctx *ctx, const uint8_t *src, size_t stride, const 
 
 void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m) { stage_layout(ctx, len, off, m); }
 
-void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes)
+void *DeviceBuffer::reserve(size_t bytes, bool mirrored, bool poisoned)
 {
-    if (n * bytes <= ctx->boxes_cap) return;
-    void *h_old = ctx->h_boxes, *d_old = ctx->d_boxes;
-    ctx->h_boxes = nullptr; ctx->d_boxes = nullptr; ctx->boxes_cap = 0;
+    if (cap >= bytes) return d;
+    release();
+    void *h_new = nullptr, *d_new = nullptr;
+    if (mirrored) EBCC_HIP_CHECK(hipHostMalloc(&h_new, bytes));
+    const hipError_t e = device_malloc(&d_new, bytes);
+    if (e != hipSuccess) {
+        if (h_new) hipHostFree(h_new);
+        char b[128];
+        snprintf(b, sizeof b, "device buffer of %zu bytes: %s", bytes, hipGetErrorString(e));
+        throw HipFailure(b);
+    }
+    h = h_new; d = d_new; cap = bytes;
+    if (poisoned) poison_alloc(d_new, bytes);
+    return d;
+}
+void DeviceBuffer::release()
+{
+    void *h_old = h, *d_old = d;
+    h = nullptr; d = nullptr; cap = 0;
     if (h_old) hipHostFree(h_old);
     if (d_old) hipFree(d_old);
-    const size_t cap = (n + n / 2 + 64) * bytes;
-    void *h_new = nullptr, *d_new = nullptr;
-    EBCC_HIP_CHECK(hipHostMalloc(&h_new, cap));
-    const hipError_t e = device_malloc(&d_new, cap);
-    if (e != hipSuccess) { hipHostFree(h_new); EBCC_HIP_CHECK(e); }
-    ctx->h_boxes = h_new; ctx->d_boxes = d_new; ctx->boxes_cap = cap;
+}
+
+void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes)
+{
+    if (n * bytes > ctx->boxes.cap) ctx->boxes.reserve((n + n / 2 + 64) * bytes, true, false);
 }
 
 void stage_send(ebcc_hip_ctx *ctx, size_t m, hipStream_t s)
@@ -434,14 +449,8 @@ void ebcc_hip_destroy(ebcc_hip_ctx *ctx)
     if (ctx->h_table) hipHostFree(ctx->h_table);
     if (ctx->h_stage) hipHostFree(ctx->h_stage);
     if (ctx->d_stage) hipFree(ctx->d_stage);
-    if (ctx->d_io) hipFree(ctx->d_io);
-    if (ctx->h_boxes) hipHostFree(ctx->h_boxes);
-    if (ctx->d_boxes) hipFree(ctx->d_boxes);
     if (ctx->h_bounce) hipHostFree(ctx->h_bounce);
-    if (ctx->d_audit) hipFree(ctx->d_audit);
-    if (ctx->d_offenders) hipFree(ctx->d_offenders);
-    if (ctx->d_errs) hipFree(ctx->d_errs);
-    if (ctx->h_errs) hipHostFree(ctx->h_errs);
+    for (DeviceBuffer *b : {&ctx->io, &ctx->boxes, &ctx->audit, &ctx->offenders, &ctx->errs}) b->release();
     if (ctx->ev_a) hipEventDestroy(ctx->ev_a);
     if (ctx->ev_b) hipEventDestroy(ctx->ev_b);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);

@@ -7,6 +7,21 @@
 
 #include "residual.hpp"
 
+namespace ebcc {
+
+// A device buffer that is made on first use and grown on demand, with a pinned host mirror of the same size where one is
+// asked for.  reserve keeps what is large enough; else it frees both and makes them anew (the contents are not kept).  The
+// context stays cached after a failed call: the buffer never keeps a freed pointer or a capacity it does not have.
+struct DeviceBuffer {
+    void *d = nullptr, *h = nullptr;
+    size_t cap = 0;                         // bytes
+    // -> d, with room for `bytes`; poisoned: a new buffer is filled by poison_alloc (common.hpp).  Throws HipFailure.
+    void *reserve(size_t bytes, bool mirrored, bool poisoned);
+    void release();
+};
+
+}  // namespace ebcc
+
 struct ebcc_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -43,22 +58,17 @@ struct ebcc_hip_ctx {
     uint8_t *h_stage = nullptr, *d_stage = nullptr;
     size_t stage_cap = 0;
     // device image of the host arrays the reference-compatible entry points are handed (kept between calls)
-    float *d_io = nullptr;
-    size_t io_cap = 0;                      // bytes
+    ebcc::DeviceBuffer io;
     uint8_t *h_bounce = nullptr;            // 2 x kBounceBytes pinned: pageable host arrays cross PCIe through it (host_codec.hip)
     unsigned long long *h_pack = nullptr, *d_pack = nullptr;   // [2 pieces per frame][offset, length]
-    void *h_boxes = nullptr, *d_boxes = nullptr;               // boxes_cap bytes: the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use); an encode of frame groups keeps the table and the result words of k_group_ranges there (host_codec.hip)
-    size_t boxes_cap = 0;
-    // Audit and hard-bound encode (host_codec.hip), all made on first use and freed with the engine set: the decoded frames of
-    // one batch, the originals of a round's offenders gathered side by side, and the records of k_frame_errors (one per
-    // workgroup, then one per frame, with the frames' bounds behind them) on the device and pinned.  The reduce decode decodes
-    // its batches into d_audit too (a context runs one call at a time) and keeps the fold's (item, bin) list in h_boxes / d_boxes;
-    // so does the area series, whose row weights and region table lie in h_boxes / d_boxes and whose records (per row of a
-    // region, then per region) lie in d_errs / h_errs.
-    float *d_audit = nullptr, *d_offenders = nullptr;
-    size_t audit_cap = 0, offenders_cap = 0;                    // bytes
-    void *d_errs = nullptr, *h_errs = nullptr;
-    size_t errs_cap = 0;                                        // bytes
+    ebcc::DeviceBuffer boxes;                                  // the entry table of a box-list decode (j2k.hpp: J2kBoxEntry, and the J2kPlacement table of placed boxes behind it), pinned and on the device (made on first use); an encode of frame groups keeps the table and the result words of k_group_ranges there (array_stats.hip)
+    // Audit and hard-bound encode (host_codec.hip, array_stats.hip), all made on first use and freed with the engine set: the
+    // decoded frames of one batch (audit), the originals of a round's offenders gathered side by side (offenders), and the
+    // records of k_frame_errors (errs: one per workgroup, then one per frame, with the frames' bounds behind them) on the device
+    // and pinned.  The reduce decode decodes its batches into `audit` too (a context runs one call at a time) and keeps the fold's
+    // (item, bin) list in `boxes`; so does the area series, whose row weights and region table lie in `boxes` and whose records
+    // (per row of a region, then per region) lie in `errs`.
+    ebcc::DeviceBuffer audit, offenders, errs;
     ebcc::CutSlots cut{};                 // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
     bool cut_failed = false;                // (no memory for it: the search probes one cut per round)
 };
@@ -83,7 +93,7 @@ void stage_download(ebcc_hip_ctx *ctx, const uint8_t *src, size_t stride, const 
 void stage_reserve(ebcc_hip_ctx *ctx, const size_t *len, size_t *off, size_t m);
 void stage_send(ebcc_hip_ctx *ctx, size_t m, hipStream_t s);
 void stage_scatter(ebcc_hip_ctx *ctx, uint8_t *dst, size_t stride, size_t first, size_t count, hipStream_t s);
-// room for n records of `bytes` each in ctx->h_boxes / d_boxes (grown rarely: sized by the largest table seen)
+// room for n records of `bytes` each in ctx->boxes, pinned and on the device (grown rarely: sized by the largest table seen)
 void boxes_reserve(ebcc_hip_ctx *ctx, size_t n, size_t bytes);
 
 // cut slots for `capacity` simultaneous probes (residual.hpp); false: not available (unsupported grid or no memory)

@@ -4,7 +4,10 @@
 //   batch_codec.hip  one device batch: the frame codec of /root/reference/src/ebcc_codec.c:607-918 (encode_batch) and
 //                    :1215-1320 (decode_batch) on an engine, with its three search loops
 //   host_codec.hip   engines per device and geometry, slices and alternating engine sets, host <-> device copies, the EBCK
-//                    container, and the C API of include/ebcc_codec.h / include/ebcc_hip.h
+//                    container, the driver of the consumers of decoded frames, and the C API of include/ebcc_codec.h /
+//                    include/ebcc_hip.h
+//   array_stats.hip  the statistics the entry points compute on device arrays, kernels and launchers (array_stats.hpp): chunk
+//                    gather, ranges, per-frame errors, the fold over time, regional statistics
 //   h5z_filter.hip   the HDF5 filter plugin (id 308) of /root/reference/src/h5z_ebcc.c
 #pragma once
 
@@ -86,6 +89,8 @@ static_assert(sizeof(FrameHeader) == 48, "EBCC header must be 48 bytes");
 static_assert(sizeof(ChunkHeader) == 80, "EBCK header must be 80 bytes");
 inline uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 inline float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+
+inline size_t cdiv(size_t a, size_t b) { return a / b + (a % b != 0); }
 
 inline bool dims_are_valid(const size_t d[3])
 {

@@ -414,7 +414,7 @@ typedef struct {
     float    x_max;
 } ebcc_hip_frame_error;
 /* The report is the same bytes from run to run and whatever the batch size, the slices, the engine sets and the alignment of
- * the arrays: no atomics, a fixed order of every sum (ebcc_amd/csrc/host_codec.hip: k_frame_errors).  `bound`: host, one float per
+ * the arrays: no atomics, a fixed order of every sum (ebcc_amd/csrc/array_stats.hip: k_frame_errors).  `bound`: host, one float per
  * frame, may be NULL.  Return 0 = ok, 1 = error (streams are refused exactly as ebcc_hip_decode_frames refuses them), 2 = NaN /
  * Inf in the originals (the frames without one are still reported).  One-frame chunks only.
  * unit level, the kernel alone: n_frames frames of height x width at d_x (originals) and d_d (decoded), each at any 4-byte
@@ -474,7 +474,7 @@ int ebcc_hip_encode_host_frames_hard(ebcc_hip_ctx *ctx, const float *h_frames, s
  * alignment of the arrays and the split of a series over several calls - the bytes of a plain loop over the decoded fields:
  *   sum += (double) x;  sum_sq += (double) x * (double) x (the product is exact, the sum rounds);  min / max in float, -0
  *   counts as +0 and +0 is written;  over += x > threshold, compared in float.
- * No atomics, and frames never meet in a reduction tree (ebcc_amd/csrc/host_codec.hip: k_time_fold).
+ * No atomics, and frames never meet in a reduction tree (ebcc_amd/csrc/array_stats.hip: k_time_fold).
  * Not covered: chunks of several frames, a slab of an EBCK container whose region crosses chunks, a host-pointer form, the
  * reference-compatible entry points and the filter callback.  (Statistics over an area per frame: the area series below.) */
 #define EBCC_HIP_NO_BIN UINT32_MAX
@@ -535,7 +535,7 @@ int ebcc_hip_reduce_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, cons
  *   Per region: fold64 of its row results with g = 1, rows counted from the region's first row.
  *   min / max take the same way (the order does not show in them) and leave with + 0.0f: -0 counts as +0.  A region whose
  *   weights are all zero gives sums of +0.0, min = +inf, max = -inf.  Products and sums are never contracted.
- * No atomics (ebcc_amd/csrc/host_codec.hip: k_area_rows, k_area_fold).
+ * No atomics (ebcc_amd/csrc/array_stats.hip: k_area_rows, k_area_fold).
  * Not covered: chunks of several frames, regions that are not boxes beyond what a d_w_pix mask expresses, a host-pointer
  * form, EBCK containers, the reference-compatible entry points and the filter callback. */
 typedef struct { size_t row0, col0, rows, cols; } ebcc_hip_region;     /* frame coordinates */

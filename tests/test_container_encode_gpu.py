@@ -189,25 +189,29 @@ def array_range(ctx, ptr, n):
 
 
 def test_array_range():
+    """One array is a group of one of the range kernel: 2047 / 2048 / 2049 floats lie around the one block of 256 lanes x 8 floats,
+    4097 is the first grid of two blocks.  The flag of a planted NaN / Inf comes from whichever wave meets it."""
     flat = array_a().ravel()
     with L.Context(2, 32, 48) as ctx:
         for base in (0, 1, 2, 3):
             src = Resident(flat, base)
-            for n in (1, 2, 3, 4, 5, 63, 64, 65, flat.size):
+            for n in (1, 2, 3, 4, 5, 63, 64, 65, 2047, 2048, 2049, 4097, flat.size):
                 rc, mm = array_range(ctx, src.ptr, n)
                 assert rc == 0, error()
                 assert mm[0] == flat[:n].min() and mm[1] == flat[:n].max(), (base, n)
+            assert src.unchanged()
             src.free()
-        for n in (1, 65, flat.size):                                       # the planted value is the last float: the 4-byte tail or a 16-byte load
-            for bad in (np.nan, np.inf, -np.inf):
-                x = flat[:n].copy()
-                x[-1] = bad
-                src = Resident(x, 1)
-                assert array_range(ctx, src.ptr, n)[0] == 2 and error()
-                if n > 1:
-                    rc, mm = array_range(ctx, src.ptr, n - 1)             # (and nothing behind the n floats is read)
-                    assert rc == 0 and mm[0] == x[:-1].min() and mm[1] == x[:-1].max()
-                src.free()
+        for n in (1, 65, 4097, flat.size):                                 # the last float is the 4-byte tail or in a 16-byte load
+            for at in sorted({0, n // 2, n - 1}):
+                for bad in (np.nan, np.inf, -np.inf):
+                    x = flat[:n].copy()
+                    x[at] = bad
+                    src = Resident(x, 1)
+                    assert array_range(ctx, src.ptr, n)[0] == 2 and error(), (n, at, bad)
+                    if n > 1 and at == n - 1:
+                        rc, mm = array_range(ctx, src.ptr, n - 1)         # (and nothing behind the n floats is read)
+                        assert rc == 0 and mm[0] == x[:-1].min() and mm[1] == x[:-1].max()
+                    src.free()
         assert lib().ebcc_hip_array_range(ctx.ptr, None, 5, np.zeros(2, np.float32).ctypes.data) == 1
         d = L.DeviceArray(flat[:8])
         assert lib().ebcc_hip_array_range(ctx.ptr, d.ptr, 0, np.zeros(2, np.float32).ctypes.data) == 1

@@ -310,6 +310,25 @@ def test_group_ranges():
             d.free()
         zeros = next(g for g, (at, n, _) in enumerate(groups) if n == 7 and at % 4 == 2)
         assert (groups[zeros][2] == 0).all() and np.signbit(groups[zeros][2]).any()
+        # one array through ebcc_hip_array_range and as a group of one: the same words, and the same flag on a planted NaN
+        array_range = lib().ebcc_hip_array_range
+        array_range.argtypes, array_range.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int
+        x = (rng.standard_normal(4099) * 100).astype(np.float32)
+        for base in (0, 1, 2, 3):
+            for planted in (None, 2050):
+                y = x.copy()
+                if planted is not None:
+                    y[planted] = np.nan
+                d = L.DeviceArray(np.concatenate([np.full(FRONT + base, SENT, np.uint32), y.view(np.uint32), np.full(BACK, SENT, np.uint32)]))
+                ptr = d.ptr + 4 * (FRONT + base)
+                one = np.array([-123.0, -456.0], np.float32)
+                rc_one = array_range(ctx.ptr, ptr, y.size, one.ctypes.data)
+                rc, mm, flags = group_ranges(ctx, [ptr], [y.size])
+                assert rc_one == rc == (2 if planted else 0) and flags.tolist() == [1 if planted else 0], (base, planted, error())
+                assert np.array_equal(one.view(np.uint32), mm[0].view(np.uint32)), (base, planted, one, mm)
+                if planted is None:
+                    assert bits(one[0]) == bits(x.min()) and bits(one[1]) == bits(x.max())
+                d.free()
         d = L.DeviceArray(clean)
         assert group_ranges(ctx, [d.ptr, None], [4, 4])[0] == 1 and error()
         assert group_ranges(ctx, [d.ptr, d.ptr], [4, 0])[0] == 1 and error()

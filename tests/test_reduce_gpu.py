@@ -428,16 +428,18 @@ def test_a_stream_damaged_inside_a_batch(monkeypatch):
         with L.Context(4, H, W) as ctx:
             return ctx.encode_frames(L.era5_like(H, W, 64)[None], L.make_config((1, H, W), base_cr=10, residual_type=L.NONE))[0][:40]
     damaged = HB.once("reduce damaged stream", make)
-    for at in (8, 1):                                               # in the last batch of three; in the first
+    # in batch 1 of three, in the first - and in batch 1 of four: batch 2, on the other set, is waiting for the turn of the batch that
+    # failed, and batch 3 only passes its turn on
+    for cap, at in ((5, 8), (5, 1), (3, 4)):
         bad = list(streams)
         bad[at] = damaged
-        with L.Context(5, H, W) as ctx:
+        with L.Context(cap, H, W) as ctx:
             st = Stats(3, H, W, base=1).init(ctx)
             assert reduce(ctx, bad, BINS12, st) == 1 and last_error()
             assert st.sentinels_intact()
             st.init(ctx)
             assert reduce(ctx, streams, BINS12, st) == 0, last_error()
-            same(st.get(), expected(fields, BINS12, 3), f"after the damaged stream at {at}")
+            same(st.get(), expected(fields, BINS12, 3), f"after the damaged stream at {at} of batches of {cap}")
             assert st.sentinels_intact()
 
 

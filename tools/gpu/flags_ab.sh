@@ -7,7 +7,7 @@ F=$1; shift
 BASE="--offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fvisibility=hidden -I../../include"
 S='import json,sys; d=json.loads(sys.stdin.read()); k=d["kernels"]; print(d["ms_per_step"], d["encode_GBps"], d["decode_GBps"], {n: v["ms_avg"] for n, v in k.items() if n in ("t1_mq","t1_symbols","t1_decode","t1_probe_decode","rate_alloc","spiht_decode","spiht_encode")})'
 OBJS=""
-for o in engine residual_dwt residual_spiht j2k j2k_analysis j2k_rate search host_pool batch_codec host_codec h5z_filter; do
+for o in engine residual_dwt residual_spiht j2k j2k_analysis j2k_rate search host_pool batch_codec array_stats host_codec h5z_filter; do
   if [ "$o.hip" == "$F" ]; then OBJS="$OBJS /tmp/flags_ab.o"; else OBJS="$OBJS $o.o"; fi
 done
 for V in "$@"; do

@@ -10,7 +10,7 @@ for C in $1; do
   grep -q "kRowChunk = $C;" j2k_analysis_chunk_ab.hip || { echo "kRowChunk not found"; rm -f j2k_analysis_chunk_ab.hip; exit 1; }
   /opt/rocm/bin/hipcc $FLAGS -c j2k_analysis_chunk_ab.hip -o /tmp/j2k_analysis_c$C.o || exit 1
   rm -f j2k_analysis_chunk_ab.hip
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libh5z_ebcc.so engine.o residual_dwt.o residual_spiht.o j2k.o /tmp/j2k_analysis_c$C.o j2k_rate.o search.o host_pool.o batch_codec.o host_codec.o h5z_filter.o -Wl,-rpath,/opt/rocm/lib -ldl -lpthread || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libh5z_ebcc.so engine.o residual_dwt.o residual_spiht.o j2k.o /tmp/j2k_analysis_c$C.o j2k_rate.o search.o host_pool.o batch_codec.o array_stats.o host_codec.o h5z_filter.o -Wl,-rpath,/opt/rocm/lib -ldl -lpthread || exit 1
   echo -n "[rows per barrier $C] "
   (cd ../.. && timeout -k 10 300 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "$S")
 done
