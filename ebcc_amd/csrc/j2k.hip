@@ -589,6 +589,96 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_encode(ebcc_hip_ctx *ctx
     EBCC_API_CATCH(1)
 }
 
+// Parity diagnostics (include/ebcc_hip.h): the rate-independent tables of the encoder in plain host arrays.  With d_frames
+// the launches are those of ebcc_hip_j2k_encode up to launch_j2k_rate, in its order; without, nothing is launched.  The
+// per-code-block arrays of J2kBuffers are indexed frame * stride + b with b in packet order (make_j2k_geom fills the
+// blocks resolution by resolution, J2kGeom::res_first), the pass tables in rows of kJ2kMaxPasses, the bytes in slots of
+// kJ2kCblkBytes (j2k.hpp); what leaves here is compact.
+__attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, float *coeffs,
+                                                               int32_t *q6, ebcc_hip_j2k_block *blocks, size_t blocks_per_frame,
+                                                               int *rates, double *disto, size_t passes_cap, uint8_t *bytes,
+                                                               size_t bytes_cap, int *const_field, int *retried)
+{
+    EBCC_API_TRY
+    if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_j2k_tables: bad batch"); return 1; }
+    if (ctx->tile_period != 1) { set_error("ebcc_hip_j2k_tables: the context is one for chunks of several frames"); return 1; }
+    if (!blocks || !rates || !disto || !bytes || !const_field) { set_error("ebcc_hip_j2k_tables: an output array is missing"); return 1; }
+    if (!d_frames && coeffs) { set_error("ebcc_hip_j2k_tables: the coefficients stand in the tile buffer only after the analysis of this call"); return 1; }
+    EBCC_HIP_CHECK(hipSetDevice(ctx->device));
+    J2kBuffers &jb = *static_cast<J2kBuffers *>(ctx->j2k);
+    const J2kGeom &g = jb.geom;
+    if (blocks_per_frame != (size_t) g.nblocks) {
+        set_error("ebcc_hip_j2k_tables: a frame of %d x %d has %d code-blocks, not %zu", g.H, g.W, g.nblocks, blocks_per_frame);
+        return 1;
+    }
+    hipStream_t s = ctx->stream;
+    const int n = (int) n_frames;
+    std::vector<J2kFrame> jf(n_frames);
+    bool again = false;
+    if (d_frames) {
+        launch_input_stats(d_frames, n, ctx->n_pix, ctx->rb.fs, s);
+        launch_j2k_analysis(d_frames, jb, n, s);
+        EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
+        wait_stream(s);
+        again = j2k_tier1_retry(jb, n, jf.data(), s);
+    }
+    if (retried) *retried = again ? 1 : 0;
+    EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
+    fetch_frame_states(ctx, n_frames);
+    const size_t n_pix = ctx->n_pix, stride = (size_t) g.stride, total = n_frames * stride;
+    std::vector<int> nbps(total), npass(total), len(total);
+    EBCC_HIP_CHECK(hipMemcpyAsync(nbps.data(), jb.numbps, sizeof(int) * total, hipMemcpyDeviceToHost, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(npass.data(), jb.totalpasses, sizeof(int) * total, hipMemcpyDeviceToHost, s));
+    EBCC_HIP_CHECK(hipMemcpyAsync(len.data(), jb.cblk_len, sizeof(int) * total, hipMemcpyDeviceToHost, s));
+    wait_stream(s);
+    std::vector<J2kBlock> blk;
+    make_j2k_geom(g.H, g.W, blk);
+    size_t pass_at = 0, byte_at = 0;
+    for (size_t f = 0; f < n_frames; f++) {
+        const bool is_const = ctx->h_fs[f].const_field != 0;
+        const_field[f] = is_const ? 1 : 0;
+        if (!is_const && jf[f].overflow) { set_error("ebcc_hip_j2k_tables: code-block byte slot overflow in frame %zu", f); return 1; }
+        if (is_const) {                                                  // (the analysis leaves a constant frame's arrays as they were)
+            if (coeffs) memset(coeffs + f * n_pix, 0, n_pix * sizeof(float));
+            if (q6) memset(q6 + f * n_pix, 0, n_pix * sizeof(int32_t));
+        } else {
+            if (coeffs) EBCC_HIP_CHECK(hipMemcpyAsync(coeffs + f * n_pix, jb.B + f * n_pix, n_pix * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (q6) EBCC_HIP_CHECK(hipMemcpyAsync(q6 + f * n_pix, jb.Q6 + f * n_pix, n_pix * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        for (int b = 0; b < g.nblocks; b++) {
+            const size_t gid = f * stride + (size_t) b;
+            const J2kBand &bd = g.bands[blk[(size_t) b].band];
+            ebcc_hip_j2k_block &o = blocks[f * blocks_per_frame + (size_t) b];
+            o.x = blk[(size_t) b].x; o.y = blk[(size_t) b].y; o.w = blk[(size_t) b].w; o.h = blk[(size_t) b].h;
+            o.orient = bd.orient; o.res = bd.res;
+            o.numbps = is_const ? 0 : nbps[gid];
+            o.totalpasses = is_const ? 0 : npass[gid];
+            o.len = is_const ? 0 : len[gid];
+            o.reserved = 0;
+            o.pass_at = pass_at; o.byte_at = byte_at;
+            if (o.totalpasses < 0 || o.totalpasses > kJ2kMaxPasses || o.len < 0 || o.len > kJ2kCblkBytes) {
+                set_error("ebcc_hip_j2k_tables: frame %zu code-block %d holds %d passes and %d bytes", f, b, o.totalpasses, o.len);
+                return 1;
+            }
+            if (pass_at + (size_t) o.totalpasses > passes_cap || byte_at + (size_t) o.len > bytes_cap) {
+                set_error("ebcc_hip_j2k_tables: the pass tables or the bytes outgrow the caller's arrays at frame %zu code-block %d", f, b);
+                return 1;
+            }
+            if (o.totalpasses > 0) {
+                EBCC_HIP_CHECK(hipMemcpyAsync(rates + pass_at, jb.rates + gid * kJ2kMaxPasses, sizeof(int) * (size_t) o.totalpasses, hipMemcpyDeviceToHost, s));
+                EBCC_HIP_CHECK(hipMemcpyAsync(disto + pass_at, jb.disto + gid * kJ2kMaxPasses, sizeof(double) * (size_t) o.totalpasses, hipMemcpyDeviceToHost, s));
+            }
+            if (o.len > 0)
+                EBCC_HIP_CHECK(hipMemcpyAsync(bytes + byte_at, jb.cblk_bytes + gid * kJ2kCblkBytes, (size_t) o.len, hipMemcpyDeviceToHost, s));
+            pass_at += (size_t) o.totalpasses;
+            byte_at += (size_t) o.len;
+        }
+    }
+    wait_stream(s);
+    return 0;
+    EBCC_API_CATCH(1)
+}
+
 // After ebcc_hip_j2k_encode: the field j2k_decode_internal (:1092-1136) would return for those streams,
 // decoded in place from the encoder's code-block slots; nbad[f] = count(|x - d| > target[f]).
 __attribute__((visibility("default"))) int ebcc_hip_j2k_emulated_decode(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames,

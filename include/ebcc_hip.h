@@ -128,6 +128,31 @@ int ebcc_hip_j2k_emulated_decode(ebcc_hip_ctx *ctx, const float *d_frames, size_
 int ebcc_hip_j2k_probe(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, const float *cr, const float *target,
                        const uint32_t *bad_limit, const int *keep, const int *active, int keep_field, unsigned long long *nbad,
                        double *err_sum, int *stream_bytes, float *d_field_out);
+/* Parity diagnostics of the rate-independent half of the encoder - forward 9/7, quantisation with six fractional bits,
+ * tier-1 with its per-pass byte counts, the distortion tables - in plain host arrays (tests/test_j2k_tables_gpu.py compares
+ * them with the oracle's analysis stage by stage).  Not on any product path.
+ * d_frames given: runs what ebcc_hip_j2k_encode runs before its rate allocation, through the same launchers in the same
+ * order (input statistics, analysis, the tier-1 retry; *retried, may be NULL, tells whether that retry ran).  d_frames NULL:
+ * launches nothing and returns what stands in the context for its first n_frames frames, e.g. after encodes and probes;
+ * coeffs must be NULL then (later decodes reuse the tile buffer).
+ * coeffs (may be NULL) / q6 (may be NULL): [n_frames][height][width], the tile buffer with the forward coefficients and the
+ * quantised coefficients.  blocks: [n_frames][blocks_per_frame] in packet order (resolution, band, raster);
+ * blocks_per_frame must be the frame's number of code-blocks (what ebcc_hip_window_plan returns).  A code-block's cumulative
+ * pass rates and distortions are rates / disto [pass_at, pass_at + totalpasses) and its bytes are bytes [byte_at, byte_at +
+ * len), packed one behind the other in the order of `blocks`; passes_cap / bytes_cap: room in those arrays (a call that
+ * needs more fails).  const_field: [n_frames]; a constant frame is not coded: its code-blocks come back with the
+ * geometry, zero passes and zero bytes, its coeffs and q6 zeroed.  0 = ok, 1 = error (bad batch, a context for chunks of
+ * several frames, arrays too small). */
+typedef struct {
+    int x, y, w, h;              /* rectangle in the tile buffer */
+    int orient, res;             /* 0 LL, 1 HL, 2 LH, 3 HH; resolution 0 (coarsest) .. 5 */
+    int numbps, totalpasses, len;
+    int reserved;
+    size_t pass_at, byte_at;
+} ebcc_hip_j2k_block;
+int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, float *coeffs, int32_t *q6,
+                        ebcc_hip_j2k_block *blocks, size_t blocks_per_frame, int *rates, double *disto, size_t passes_cap,
+                        uint8_t *bytes, size_t bytes_cap, int *const_field, int *retried);
 /* j2k_decode_internal for a batch of codestreams with (minval, maxval) pairs in minmax [n][2] */
 int ebcc_hip_j2k_decode(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                         const float *minmax, float *d_out);

@@ -1097,6 +1097,10 @@ static void make_layer(tile_t *t, double thresh)
 static void (*g_block_sink)(const int32_t *q, int w, int h, int orient, void *user) = NULL;
 static void *g_block_sink_user = NULL;
 void orc_j2k_set_block_sink(void (*fn)(const int32_t *, int, int, int, void *), void *user) { g_block_sink = fn; g_block_sink_user = user; }
+/* a second one: the float coefficients of the code-block as they stand just before quantisation, called before the first */
+static void (*g_coeff_sink)(const float *cf, int w, int h, int orient, void *user) = NULL;
+static void *g_coeff_sink_user = NULL;
+void orc_j2k_set_coeff_sink(void (*fn)(const float *, int, int, int, void *), void *user) { g_coeff_sink = fn; g_coeff_sink_user = user; }
 
 static void j2k_analyse_at(const uint16_t *img, int H, int W, int ty0, tile_t *tp, int *expn, int *mant)
 {
@@ -1139,13 +1143,16 @@ static void j2k_analyse_at(const uint16_t *img, int H, int W, int ty0, tile_t *t
                 int w = cb->x1 - cb->x0, h = cb->y1 - cb->y0;
                 t1_alloc(&e.t, w, h);
                 e.mag = (uint32_t *) malloc((size_t) w * h * sizeof(uint32_t));
+                float *cfs = g_coeff_sink ? (float *) malloc((size_t) w * h * sizeof(float)) : NULL;
                 for (int y = 0; y < h; y++)
                     for (int x = 0; x < w; x++) {
                         float cf = buf[(size_t) (bd->offy + cb->y0 - bd->y0 + y) * W + bd->offx + cb->x0 - bd->x0 + x];
+                        if (cfs) cfs[y * w + x] = cf;
                         int q = (int) lrintf((cf / bd->stepsize) * (float) (1 << NMSEDEC_FRACBITS));
                         e.t.data[y * w + x] = q;
                         e.mag[y * w + x] = (uint32_t) (q < 0 ? -q : q);
                     }
+                if (cfs) { g_coeff_sink(cfs, w, h, bd->orient, g_coeff_sink_user); free(cfs); }
                 if (g_block_sink) g_block_sink(e.t.data, w, h, bd->orient, g_block_sink_user);
                 t1_encode_cblk(&e, cb, bd->orient, bd->level, bd->stepsize);
                 free(e.mag);
@@ -1300,14 +1307,17 @@ void orc_j2k_t1_decode(const uint8_t *data, int len, int numbps, int npasses, in
     t1_free(&t);
 }
 
-/* per-code-block tier-1 results in packet order (resolution, band, raster): for pinning the device analysis */
-int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
-                     int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes)
+/* per-code-block tier-1 results in packet order (resolution, band, raster): for pinning the device analysis.
+ * _bytes: the same, and the code-blocks' bytes one behind the other (code-block b's lens[b] bytes start at the sum of the
+ * lengths before it); returns -1 where they need more than `cap` bytes. */
+static int analysis_tables(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
+                           int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes, uint8_t *bytes, size_t cap)
 {
     tile_t t;
     int expn[3 * J2K_NRES - 2], mant[3 * J2K_NRES - 2];
     j2k_analyse(img, (int) height, (int) width, &t, expn, mant);
     int nb = 0;
+    size_t at = 0;
     for (int r = 0; r < J2K_NRES; r++)
         for (int b = 0; b < t.res[r].nbands; b++) {
             band_t *bd = &t.res[r].bands[b];
@@ -1315,11 +1325,27 @@ int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numb
                 cblk_t *cb = &bd->cblks[ci];
                 numbps[nb] = cb->numbps; totalpasses[nb] = cb->totalpasses; lens[nb] = cb->len;
                 for (int p = 0; p < cb->totalpasses; p++) { rates[nb * 100 + p] = cb->rate[p]; disto[nb * 100 + p] = cb->disto[p]; }
-                unsigned hsh = 0;
-                for (int k = 0; k < cb->len; k++) hsh = hsh * 131 + cb->data[k];
-                hashes[nb] = hsh;
+                if (hashes) {
+                    unsigned hsh = 0;
+                    for (int k = 0; k < cb->len; k++) hsh = hsh * 131 + cb->data[k];
+                    hashes[nb] = hsh;
+                }
+                if (bytes && cb->len > 0 && at + (size_t) cb->len <= cap) memcpy(bytes + at, cb->data, (size_t) cb->len);
+                at += (size_t) cb->len;
             }
         }
     tile_free(&t);
-    return nb;
+    return bytes && at > cap ? -1 : nb;
+}
+
+int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
+                     int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes)
+{
+    return analysis_tables(img, height, width, numbps, totalpasses, lens, rates, disto, hashes, NULL, 0);
+}
+
+int orc_j2k_analysis_bytes(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
+                           int *rates /* [nb][100] */, double *disto /* [nb][100] */, uint8_t *bytes, size_t cap)
+{
+    return analysis_tables(img, height, width, numbps, totalpasses, lens, rates, disto, NULL, bytes, cap);
 }

@@ -126,10 +126,21 @@ size_t orc_j2k_encode(const uint16_t *img, size_t height, size_t width, float ba
 /* `tiles` frames of height x width stacked along y, one tile each (ebcc_codec.c:105-180 with n_tiles > 1) */
 size_t orc_j2k_encode_tiled(const uint16_t *img, size_t tiles, size_t height, size_t width, float base_cr, uint8_t **out);
 
-/* Decode a codestream to int32 samples as OpenJPEG's opj_decode does (src/ebcc_codec.c:1092-1136
- * reads image->comps[0].data).  samples malloc'd. Returns number of pixels or 0. */
 /* test hook: called with every code-block's quantised coefficients during orc_j2k_encode / orc_j2k_analysis */
 void orc_j2k_set_block_sink(void (*fn)(const int32_t *q, int w, int h, int orient, void *user), void *user);
+/* a second hook, called before the first: the code-block's float coefficients as they stand just before quantisation */
+void orc_j2k_set_coeff_sink(void (*fn)(const float *cf, int w, int h, int orient, void *user), void *user);
+/* Everything of the encoder that does not depend on the rate, per code-block in packet order (resolution, band, raster),
+ * for pinning the device analysis: numbps, totalpasses, length, and the per-pass cumulative rates and distortions in rows of
+ * 100.  hashes: a polynomial hash of each code-block's bytes.  Returns the number of code-blocks. */
+int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens, int *rates,
+                     double *disto, unsigned *hashes);
+/* the same with the bytes themselves, one code-block behind the other (b's lens[b] bytes start at the sum of the lengths
+ * before it); -1: they need more than `cap` bytes */
+int orc_j2k_analysis_bytes(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens, int *rates,
+                           double *disto, uint8_t *bytes, size_t cap);
+/* Decode a codestream to int32 samples as OpenJPEG's opj_decode does (src/ebcc_codec.c:1092-1136
+ * reads image->comps[0].data).  samples malloc'd. Returns number of pixels or 0. */
 size_t orc_j2k_decode(const uint8_t *cs, size_t cs_size, int32_t **samples, size_t *height, size_t *width);
 
 #ifdef __cplusplus

@@ -76,6 +76,11 @@ def oracle():
         lib.orc_j2k_encode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_float, c_void_pp]
         lib.orc_j2k_decode.restype = ctypes.c_size_t
         lib.orc_j2k_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, c_void_pp, c_size_p, c_size_p]
+        lib.orc_j2k_set_block_sink.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.orc_j2k_set_coeff_sink.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.orc_j2k_analysis.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t] + [ctypes.c_void_p] * 6
+        lib.orc_j2k_analysis_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t] + [ctypes.c_void_p] * 6 + \
+            [ctypes.c_size_t]
         if hasattr(lib, "orc_opj_encode"):
             lib.orc_opj_encode.restype = ctypes.c_size_t
             lib.orc_opj_encode.argtypes = lib.orc_j2k_encode.argtypes
@@ -312,6 +317,32 @@ def _dptr(d):
     return d.ptr if isinstance(d, DeviceArray) else int(d)
 
 
+# ebcc_hip_j2k_block (include/ebcc_hip.h), and the limits of a code-block's pass tables and byte slot (j2k.hpp)
+J2K_BLOCK = np.dtype([(k, np.int32) for k in ("x", "y", "w", "h", "orient", "res", "numbps", "totalpasses", "len", "reserved")] +
+                     [("pass_at", np.uint64), ("byte_at", np.uint64)])
+J2K_MAX_PASSES, J2K_CBLK_BYTES = 78, 16 * 1024
+
+
+class J2kTables:
+    """What ebcc_hip_j2k_tables returned: n, h, w, nblocks; coeffs (or None) and q6 [n][h][w]; blocks [n][nblocks] of
+    J2K_BLOCK; rates, disto and bytes packed in the order of blocks; const [n]; retried."""
+
+    def passes(self, f, b):
+        """(rates, disto) of code-block b of frame f"""
+        k = self.blocks[f, b]
+        at, np_ = int(k["pass_at"]), int(k["totalpasses"])
+        return self.rates[at:at + np_], self.disto[at:at + np_]
+
+    def block_bytes(self, f, b):
+        k = self.blocks[f, b]
+        return self.bytes[int(k["byte_at"]):int(k["byte_at"]) + int(k["len"])].tobytes()
+
+    def rect(self, a, f, b):
+        """the code-block's rectangle of a [n][h][w] array"""
+        k = self.blocks[f, b]
+        return a[f, k["y"]:k["y"] + k["h"], k["x"]:k["x"] + k["w"]]
+
+
 class Context:
     def __init__(self, max_frames, h, w, device=0):
         self.lib = product()
@@ -425,6 +456,41 @@ class Context:
         res = out.get(np.float32, (n, self.h, self.w))
         out.free()
         return res
+
+    def j2k_tables(self, frames=None, n=None, coeffs=True):
+        """ebcc_hip_j2k_tables: the analysis of `frames` (a host array, or a DeviceArray with n), or - frames None - what
+        stands in the context for its first n frames.  A J2kTables."""
+        lib = self.lib
+        lib.ebcc_hip_window_plan.argtypes = [ctypes.c_size_t] * 6 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        lib.ebcc_hip_j2k_tables.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + \
+            [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+             ctypes.c_void_p, ctypes.c_void_p]
+        d, own = None, False
+        if frames is not None and not isinstance(frames, DeviceArray):
+            frames = np.ascontiguousarray(frames, np.float32)
+            n, d, own = frames.shape[0], DeviceArray(frames), True
+        elif frames is not None:
+            d = frames
+        nb = lib.ebcc_hip_window_plan(self.h, self.w, 0, 0, 1, 1, None, None, 0)
+        assert nb > 0, lib.ebcc_hip_last_error()
+        t = J2kTables()
+        t.n, t.h, t.w, t.nblocks = n, self.h, self.w, nb
+        t.coeffs = np.full((n, self.h, self.w), np.nan, np.float32) if coeffs and d is not None else None
+        t.q6 = np.full((n, self.h, self.w), -(2 ** 31), np.int32)
+        t.blocks = np.zeros((n, nb), J2K_BLOCK)
+        t.rates = np.full(n * nb * J2K_MAX_PASSES, -1, np.int32)
+        t.disto = np.full(n * nb * J2K_MAX_PASSES, np.nan, np.float64)
+        t.bytes = np.zeros(n * nb * J2K_CBLK_BYTES, np.uint8)
+        t.const = np.full(n, -1, np.int32)
+        retried = ctypes.c_int(-1)
+        rc = lib.ebcc_hip_j2k_tables(self.ptr, d.ptr if d is not None else None, n, t.coeffs.ctypes.data if t.coeffs is not None else None,
+                                     t.q6.ctypes.data, t.blocks.ctypes.data, nb, t.rates.ctypes.data, t.disto.ctypes.data, t.rates.size,
+                                     t.bytes.ctypes.data, t.bytes.size, t.const.ctypes.data, ctypes.byref(retried))
+        if own:
+            d.free()
+        assert rc == 0, lib.ebcc_hip_last_error()
+        t.retried = retried.value
+        return t
 
     # ---- probes of the two searches (test entry points over the encoder's own launchers)
     PROBE_SENTINEL = (np.uint64(0xDEADBEEFCAFEF00D), np.float64(-1.25e300), np.int32(-77))
@@ -573,6 +639,53 @@ def orc_j2k_decode(stream):
     a = np.frombuffer(ctypes.string_at(out.value, 4 * n), np.int32).reshape(h.value, w.value).copy()
     lib.orc_free(out)
     return a
+
+
+ORC_PASS_ROW = 100                                                      # row length of orc_j2k_analysis' rates / disto
+BLOCK_SINK = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p)
+COEFF_SINK = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p)
+
+
+def orc_j2k_analysis(img_u16):
+    """The oracle's rate-independent half of the encoder for one u16 image (orc_j2k_analysis_bytes and the two sinks): a
+    list of code-blocks in packet order, each a dict of w, h, orient, cf (float32 [h][w], the coefficients just before
+    quantisation), q (int32 [h][w], six fractional bits), numbps, totalpasses, len, rates (int32 [totalpasses]), disto
+    (float64 [totalpasses]) and bytes."""
+    lib = oracle()
+    img = np.ascontiguousarray(img_u16, np.uint16)
+    h, w = img.shape
+    qs, cfs = [], []
+
+    def take_q(q, bw, bh, orient, _user):
+        qs.append((bw, bh, orient, np.ctypeslib.as_array(q, (bh, bw)).copy()))
+
+    def take_cf(cf, bw, bh, orient, _user):
+        cfs.append((bw, bh, orient, np.ctypeslib.as_array(cf, (bh, bw)).copy()))
+
+    cap_blocks = ((h + 63) // 64 + 6) * ((w + 63) // 64 + 6) * 16        # far above any partition of h x w
+    nbp, tp, ln = (np.zeros(cap_blocks, np.int32) for _ in range(3))
+    rates = np.zeros((cap_blocks, ORC_PASS_ROW), np.int32)
+    disto = np.zeros((cap_blocks, ORC_PASS_ROW), np.float64)
+    data = np.zeros(4 * h * w + 64 * cap_blocks, np.uint8)                # (the oracle's own bound per code-block: 4 w h + 64)
+    sink_q, sink_cf = BLOCK_SINK(take_q), COEFF_SINK(take_cf)
+    lib.orc_j2k_set_block_sink(ctypes.cast(sink_q, ctypes.c_void_p), None)
+    lib.orc_j2k_set_coeff_sink(ctypes.cast(sink_cf, ctypes.c_void_p), None)
+    try:
+        n = lib.orc_j2k_analysis_bytes(img.ctypes.data, h, w, nbp.ctypes.data, tp.ctypes.data, ln.ctypes.data, rates.ctypes.data,
+                                       disto.ctypes.data, data.ctypes.data, data.size)
+    finally:
+        lib.orc_j2k_set_block_sink(None, None)
+        lib.orc_j2k_set_coeff_sink(None, None)
+    assert 0 < n <= cap_blocks and n == len(qs) == len(cfs), (n, len(qs), len(cfs))
+    off = np.concatenate([[0], np.cumsum(ln[:n], dtype=np.int64)])
+    blocks = []
+    for b in range(n):
+        assert qs[b][:3] == cfs[b][:3]
+        k = int(tp[b])
+        blocks.append({"w": qs[b][0], "h": qs[b][1], "orient": qs[b][2], "q": qs[b][3], "cf": cfs[b][3], "numbps": int(nbp[b]),
+                       "totalpasses": k, "len": int(ln[b]), "rates": rates[b, :k].copy(), "disto": disto[b, :k].copy(),
+                       "bytes": data[off[b]:off[b + 1]].tobytes()})
+    return blocks
 
 
 def map_decoded(samples, mn, mx):
