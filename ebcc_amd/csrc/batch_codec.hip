@@ -442,19 +442,7 @@ int BatchEncode::analyse()
     ebcc_hip_ctx *ctx = b.ctx, *rc = b.rc;
     const size_t tiles = b.tiles, nt = b.nt;
     launch_input_stats(b.d_frames, (int) nt, ctx->n_pix, ctx->rb.fs, b.s);
-    if (tiles > 1) {
-        // the reference scales the whole chunk with one (min, max) (:686-689): combine the tiles' statistics before
-        // the transform reads them; a tile that happens to be constant inside a varying chunk is coded normally
-        fetch_frame_states(ctx, nt);
-        for (size_t c = 0; c < n; c++) {
-            FrameState *t0 = ctx->h_fs + c * tiles;
-            float mn = t0[0].minv, mx = t0[0].maxv;
-            int bad = 0;
-            for (size_t k = 0; k < tiles; k++) { mn = std::min(mn, t0[k].minv); mx = std::max(mx, t0[k].maxv); bad |= t0[k].has_nonfinite; }
-            for (size_t k = 0; k < tiles; k++) { t0[k].minv = mn; t0[k].maxv = mx; t0[k].has_nonfinite = bad; t0[k].const_field = mn == mx; }
-        }
-        push_frame_states(ctx, nt);
-    }
+    if (tiles > 1) combine_chunk_states(ctx, n, tiles);
     launch_j2k_analysis(b.d_frames, b.jb, (int) nt, b.s);
     next.release();                                                    // the next slice may start: this one's first stage is queued
     fetch_frame_states(ctx, nt);

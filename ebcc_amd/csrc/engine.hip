@@ -243,6 +243,20 @@ void push_frame_states(ebcc_hip_ctx *ctx, size_t n, hipStream_t s)
 {
     EBCC_HIP_CHECK(hipMemcpyAsync(ctx->rb.fs, ctx->h_fs, n * sizeof(FrameState), hipMemcpyHostToDevice, s ? s : ctx->stream));
 }
+void combine_chunk_states(ebcc_hip_ctx *ctx, size_t n_chunks, size_t tiles)
+{
+    // the reference scales the whole chunk with one (min, max) (:686-689): combine the tiles' statistics before
+    // the transform reads them; a tile that happens to be constant inside a varying chunk is coded normally
+    fetch_frame_states(ctx, n_chunks * tiles);
+    for (size_t c = 0; c < n_chunks; c++) {
+        FrameState *t0 = ctx->h_fs + c * tiles;
+        float mn = t0[0].minv, mx = t0[0].maxv;
+        int bad = 0;
+        for (size_t k = 0; k < tiles; k++) { mn = std::min(mn, t0[k].minv); mx = std::max(mx, t0[k].maxv); bad |= t0[k].has_nonfinite; }
+        for (size_t k = 0; k < tiles; k++) { t0[k].minv = mn; t0[k].maxv = mx; t0[k].has_nonfinite = bad; t0[k].const_field = mn == mx; }
+    }
+    push_frame_states(ctx, n_chunks * tiles);
+}
 
 // ---- optional kernel timing -------------------------------------------------------------------------
 struct TimedSpan { std::string name; hipEvent_t a, b; hipStream_t s; bool closed; };
@@ -334,6 +348,18 @@ ebcc_hip_ctx *ebcc_hip_create(int device, size_t max_frames, size_t height, size
 {
     CallerDevice restore;
     return ebcc::create_engine(device, max_frames, height, width, 1);
+}
+
+// Parity diagnostics (include/ebcc_hip.h): the engine the chunk path makes for chunks of `tiles` frames, for the unit-level
+// entry points that take one (ebcc_hip_j2k_tables)
+ebcc_hip_ctx *ebcc_hip_create_tiles(int device, size_t max_frames, size_t height, size_t width, size_t tiles)
+{
+    CallerDevice restore;
+    if (tiles < 1 || tiles > 2047 || (tiles > 1 && height < 32)) {      // (fewer than 32 rows: no six resolutions in a tile, as ebcc_encode refuses)
+        ebcc::set_error("ebcc_hip_create_tiles: %zu tiles of %zu rows are not supported", tiles, height);
+        return nullptr;
+    }
+    return ebcc::create_engine(device, max_frames, height, width, (int) tiles);
 }
 
 }  // extern "C"

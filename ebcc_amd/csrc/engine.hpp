@@ -105,5 +105,8 @@ int check_ims_header(ebcc_hip_ctx *ctx, const uint8_t *b, size_t n, size_t num_b
 // synchronous copy of the frame states to ctx->h_fs; and back, on ctx->stream unless `s` is given
 void fetch_frame_states(ebcc_hip_ctx *ctx, size_t n_frames);
 void push_frame_states(ebcc_hip_ctx *ctx, size_t n_frames, hipStream_t s = nullptr);
+// After launch_input_stats on n_chunks x tiles frames of a context for chunks of several frames: every tile takes the
+// statistics of its chunk, on the host and on the device (synchronous fetch, push on ctx->stream)
+void combine_chunk_states(ebcc_hip_ctx *ctx, size_t n_chunks, size_t tiles);
 
 }  // namespace ebcc

@@ -589,11 +589,20 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_encode(ebcc_hip_ctx *ctx
     EBCC_API_CATCH(1)
 }
 
+// The code-block slots a frame has in the per-code-block arrays of its context (include/ebcc_hip.h; host only)
+__attribute__((visibility("default"))) int ebcc_hip_j2k_blocks_per_frame(const ebcc_hip_ctx *ctx)
+{
+    if (!ctx || !ctx->j2k) return -1;
+    return static_cast<const J2kBuffers *>(ctx->j2k)->geom.stride;
+}
+
 // Parity diagnostics (include/ebcc_hip.h): the rate-independent tables of the encoder in plain host arrays.  With d_frames
 // the launches are those of ebcc_hip_j2k_encode up to launch_j2k_rate, in its order; without, nothing is launched.  The
 // per-code-block arrays of J2kBuffers are indexed frame * stride + b with b in packet order (make_j2k_geom fills the
 // blocks resolution by resolution, J2kGeom::res_first), the pass tables in rows of kJ2kMaxPasses, the bytes in slots of
-// kJ2kCblkBytes (j2k.hpp); what leaves here is compact.
+// kJ2kCblkBytes (j2k.hpp); what leaves here is compact.  On a context for chunks of several frames (ebcc_hip_create_tiles) frame
+// f is tile f % period of chunk f / period: scaled by its chunk as BatchEncode::analyse scales it, described with the geometry
+// of its tile position; the slots past a tile position's own code-blocks come back without a rectangle.
 __attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, float *coeffs,
                                                                int32_t *q6, ebcc_hip_j2k_block *blocks, size_t blocks_per_frame,
                                                                int *rates, double *disto, size_t passes_cap, uint8_t *bytes,
@@ -601,14 +610,15 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx
 {
     EBCC_API_TRY
     if (!ctx || n_frames < 1 || n_frames > ctx->max_frames) { set_error("ebcc_hip_j2k_tables: bad batch"); return 1; }
-    if (ctx->tile_period != 1) { set_error("ebcc_hip_j2k_tables: the context is one for chunks of several frames"); return 1; }
+    const size_t period = (size_t) ctx->tile_period;
+    if (n_frames % period) { set_error("ebcc_hip_j2k_tables: %zu frames are no whole chunks of %zu frames", n_frames, period); return 1; }
     if (!blocks || !rates || !disto || !bytes || !const_field) { set_error("ebcc_hip_j2k_tables: an output array is missing"); return 1; }
     if (!d_frames && coeffs) { set_error("ebcc_hip_j2k_tables: the coefficients stand in the tile buffer only after the analysis of this call"); return 1; }
     EBCC_HIP_CHECK(hipSetDevice(ctx->device));
     J2kBuffers &jb = *static_cast<J2kBuffers *>(ctx->j2k);
     const J2kGeom &g = jb.geom;
-    if (blocks_per_frame != (size_t) g.nblocks) {
-        set_error("ebcc_hip_j2k_tables: a frame of %d x %d has %d code-blocks, not %zu", g.H, g.W, g.nblocks, blocks_per_frame);
+    if (blocks_per_frame != (size_t) g.stride) {
+        set_error("ebcc_hip_j2k_tables: a frame of %d x %d has %d code-blocks, not %zu", g.H, g.W, g.stride, blocks_per_frame);
         return 1;
     }
     hipStream_t s = ctx->stream;
@@ -617,6 +627,7 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx
     bool again = false;
     if (d_frames) {
         launch_input_stats(d_frames, n, ctx->n_pix, ctx->rb.fs, s);
+        if (period > 1) combine_chunk_states(ctx, n_frames / period, period);
         launch_j2k_analysis(d_frames, jb, n, s);
         EBCC_HIP_CHECK(hipMemcpyAsync(jf.data(), jb.jf, sizeof(J2kFrame) * n_frames, hipMemcpyDeviceToHost, s));
         wait_stream(s);
@@ -631,10 +642,12 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx
     EBCC_HIP_CHECK(hipMemcpyAsync(npass.data(), jb.totalpasses, sizeof(int) * total, hipMemcpyDeviceToHost, s));
     EBCC_HIP_CHECK(hipMemcpyAsync(len.data(), jb.cblk_len, sizeof(int) * total, hipMemcpyDeviceToHost, s));
     wait_stream(s);
-    std::vector<J2kBlock> blk;
-    make_j2k_geom(g.H, g.W, blk);
+    std::vector<std::vector<J2kBlock>> tile_blk(period);                    // (the code-blocks of every tile position, as j2k_create lists them)
+    for (size_t k = 0; k < period; k++) make_j2k_geom(g.H, g.W, tile_blk[k], (int) k * g.H);
     size_t pass_at = 0, byte_at = 0;
     for (size_t f = 0; f < n_frames; f++) {
+        const J2kGeom &tg = jb.geoms[f % period];
+        const std::vector<J2kBlock> &blk = tile_blk[f % period];
         const bool is_const = ctx->h_fs[f].const_field != 0;
         const_field[f] = is_const ? 1 : 0;
         if (!is_const && jf[f].overflow) { set_error("ebcc_hip_j2k_tables: code-block byte slot overflow in frame %zu", f); return 1; }
@@ -645,12 +658,17 @@ __attribute__((visibility("default"))) int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx
             if (coeffs) EBCC_HIP_CHECK(hipMemcpyAsync(coeffs + f * n_pix, jb.B + f * n_pix, n_pix * sizeof(float), hipMemcpyDeviceToHost, s));
             if (q6) EBCC_HIP_CHECK(hipMemcpyAsync(q6 + f * n_pix, jb.Q6 + f * n_pix, n_pix * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
-        for (int b = 0; b < g.nblocks; b++) {
+        for (int b = 0; b < g.stride; b++) {
             const size_t gid = f * stride + (size_t) b;
-            const J2kBand &bd = g.bands[blk[(size_t) b].band];
             ebcc_hip_j2k_block &o = blocks[f * blocks_per_frame + (size_t) b];
-            o.x = blk[(size_t) b].x; o.y = blk[(size_t) b].y; o.w = blk[(size_t) b].w; o.h = blk[(size_t) b].h;
-            o.orient = bd.orient; o.res = bd.res;
+            if (b < tg.nblocks) {
+                const J2kBand &bd = tg.bands[blk[(size_t) b].band];
+                o.x = blk[(size_t) b].x; o.y = blk[(size_t) b].y; o.w = blk[(size_t) b].w; o.h = blk[(size_t) b].h;
+                o.orient = bd.orient; o.res = bd.res;
+            } else {                                                     // a slot this tile position does not use: what the device left in it follows
+                o.x = o.y = o.w = o.h = 0;
+                o.orient = o.res = 0;
+            }
             o.numbps = is_const ? 0 : nbps[gid];
             o.totalpasses = is_const ? 0 : npass[gid];
             o.len = is_const ? 0 : len[gid];

@@ -141,8 +141,13 @@ int ebcc_hip_j2k_probe(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames
  * pass rates and distortions are rates / disto [pass_at, pass_at + totalpasses) and its bytes are bytes [byte_at, byte_at +
  * len), packed one behind the other in the order of `blocks`; passes_cap / bytes_cap: room in those arrays (a call that
  * needs more fails).  const_field: [n_frames]; a constant frame is not coded: its code-blocks come back with the
- * geometry, zero passes and zero bytes, its coeffs and q6 zeroed.  0 = ok, 1 = error (bad batch, a context for chunks of
- * several frames, arrays too small). */
+ * geometry, zero passes and zero bytes, its coeffs and q6 zeroed.  0 = ok, 1 = error (bad batch, arrays too small).
+ * On a context of ebcc_hip_create_tiles (chunks of `tiles` frames, below): n_frames is a multiple of tiles, frame f is tile
+ * f % tiles of chunk f / tiles.  The frames of a chunk are scaled with the chunk's (min, max) and carry the chunk's constant
+ * flag, as ebcc_encode scales them, and a frame's rectangles, bands and resolutions are those of its tile position (first
+ * row (f % tiles) * height of the image: its own sub-band extents, parities and code-block partition).  blocks_per_frame is
+ * ebcc_hip_j2k_blocks_per_frame, the most code-blocks of any tile position; the slots past a tile position's own code-blocks
+ * come back with w = h = 0 and the passes and bytes the device holds for them, which must be none. */
 typedef struct {
     int x, y, w, h;              /* rectangle in the tile buffer */
     int orient, res;             /* 0 LL, 1 HL, 2 LH, 3 HH; resolution 0 (coarsest) .. 5 */
@@ -153,6 +158,17 @@ typedef struct {
 int ebcc_hip_j2k_tables(ebcc_hip_ctx *ctx, const float *d_frames, size_t n_frames, float *coeffs, int32_t *q6,
                         ebcc_hip_j2k_block *blocks, size_t blocks_per_frame, int *rates, double *disto, size_t passes_cap,
                         uint8_t *bytes, size_t bytes_cap, int *const_field, int *retried);
+/* the code-block slots of a frame in the context's per-code-block arrays: a frame's number of code-blocks (what
+ * ebcc_hip_window_plan returns), on a context of ebcc_hip_create_tiles the most of any tile position; -1: no context */
+int ebcc_hip_j2k_blocks_per_frame(const ebcc_hip_ctx *ctx);
+/* Parity diagnostics: the context ebcc_encode / ebcc_decode make for chunks of `tiles` frames - one JPEG 2000 image a chunk,
+ * one tile a frame, a geometry per tile position (frame f uses number f % tiles) - so that ebcc_hip_j2k_tables can be asked
+ * about a tile away from the image's origin (tests/test_tile_positions_gpu.py).  Not on any product path: ebcc_hip_j2k_tables is
+ * the only entry point that is defined on such a context (the frame, shard and window entry points refuse it).  tiles == 1 is
+ * ebcc_hip_create.  NULL: what
+ * ebcc_hip_create refuses, tiles * height above 2047, or tiles > 1 with fewer than 32 rows a tile (no six resolutions in a
+ * tile: ebcc_encode refuses such chunks too). */
+ebcc_hip_ctx *ebcc_hip_create_tiles(int device, size_t max_frames, size_t height, size_t width, size_t tiles);
 /* j2k_decode_internal for a batch of codestreams with (minval, maxval) pairs in minmax [n][2] */
 int ebcc_hip_j2k_decode(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                         const float *minmax, float *d_out);

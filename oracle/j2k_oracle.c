@@ -1163,8 +1163,6 @@ static void j2k_analyse_at(const uint16_t *img, int H, int W, int ty0, tile_t *t
 
 }
 
-static void j2k_analyse(const uint16_t *img, int H, int W, tile_t *tp, int *expn, int *mant) { j2k_analyse_at(img, H, W, 0, tp, expn, mant); }
-
 #define PUT16(v) do { *p++ = (uint8_t) ((v) >> 8); *p++ = (uint8_t) (v); } while (0)
 #define PUT32(v) do { PUT16((uint32_t) (v) >> 16); PUT16((uint32_t) (v) & 0xFFFF); } while (0)
 
@@ -1310,12 +1308,12 @@ void orc_j2k_t1_decode(const uint8_t *data, int len, int numbps, int npasses, in
 /* per-code-block tier-1 results in packet order (resolution, band, raster): for pinning the device analysis.
  * _bytes: the same, and the code-blocks' bytes one behind the other (code-block b's lens[b] bytes start at the sum of the
  * lengths before it); returns -1 where they need more than `cap` bytes. */
-static int analysis_tables(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
+static int analysis_tables(const uint16_t *img, size_t height, size_t width, int ty0, int *numbps, int *totalpasses, int *lens,
                            int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes, uint8_t *bytes, size_t cap)
 {
     tile_t t;
     int expn[3 * J2K_NRES - 2], mant[3 * J2K_NRES - 2];
-    j2k_analyse(img, (int) height, (int) width, &t, expn, mant);
+    j2k_analyse_at(img, (int) height, (int) width, ty0, &t, expn, mant);
     int nb = 0;
     size_t at = 0;
     for (int r = 0; r < J2K_NRES; r++)
@@ -1341,11 +1339,31 @@ static int analysis_tables(const uint16_t *img, size_t height, size_t width, int
 int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
                      int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes)
 {
-    return analysis_tables(img, height, width, numbps, totalpasses, lens, rates, disto, hashes, NULL, 0);
+    return analysis_tables(img, height, width, 0, numbps, totalpasses, lens, rates, disto, hashes, NULL, 0);
 }
 
 int orc_j2k_analysis_bytes(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens,
                            int *rates /* [nb][100] */, double *disto /* [nb][100] */, uint8_t *bytes, size_t cap)
 {
-    return analysis_tables(img, height, width, numbps, totalpasses, lens, rates, disto, NULL, bytes, cap);
+    return analysis_tables(img, height, width, 0, numbps, totalpasses, lens, rates, disto, NULL, bytes, cap);
+}
+
+/* the same for tile `tile` of `tiles` frames of height x width stacked along y, one tile each (orc_j2k_encode_tiled): the
+ * tile's rows of img at their place in the image, so with the sub-band extents, parities and code-block partition of a
+ * tile whose first row is tile * height.  The sinks fire for that tile's code-blocks only.  0: no such tile. */
+int orc_j2k_analysis_tiled(const uint16_t *img, size_t tiles, size_t height, size_t width, size_t tile, int *numbps,
+                           int *totalpasses, int *lens, int *rates /* [nb][100] */, double *disto /* [nb][100] */, unsigned *hashes)
+{
+    if (tile >= tiles) return 0;
+    return analysis_tables(img + tile * width * height, height, width, (int) (tile * height), numbps, totalpasses, lens, rates, disto,
+                           hashes, NULL, 0);
+}
+
+int orc_j2k_analysis_tiled_bytes(const uint16_t *img, size_t tiles, size_t height, size_t width, size_t tile, int *numbps,
+                                 int *totalpasses, int *lens, int *rates /* [nb][100] */, double *disto /* [nb][100] */,
+                                 uint8_t *bytes, size_t cap)
+{
+    if (tile >= tiles) return 0;
+    return analysis_tables(img + tile * width * height, height, width, (int) (tile * height), numbps, totalpasses, lens, rates, disto,
+                           NULL, bytes, cap);
 }

@@ -139,6 +139,13 @@ int orc_j2k_analysis(const uint16_t *img, size_t height, size_t width, int *numb
  * before it); -1: they need more than `cap` bytes */
 int orc_j2k_analysis_bytes(const uint16_t *img, size_t height, size_t width, int *numbps, int *totalpasses, int *lens, int *rates,
                            double *disto, uint8_t *bytes, size_t cap);
+/* Both for one tile of an image of `tiles` frames of height x width stacked along y (orc_j2k_encode_tiled): img is the whole
+ * stacked image, the tables and both sinks are those of tile `tile` alone, at its place in the image (first row tile * height,
+ * so its own sub-band extents, parities and code-block partition).  0: no such tile. */
+int orc_j2k_analysis_tiled(const uint16_t *img, size_t tiles, size_t height, size_t width, size_t tile, int *numbps,
+                           int *totalpasses, int *lens, int *rates, double *disto, unsigned *hashes);
+int orc_j2k_analysis_tiled_bytes(const uint16_t *img, size_t tiles, size_t height, size_t width, size_t tile, int *numbps,
+                                 int *totalpasses, int *lens, int *rates, double *disto, uint8_t *bytes, size_t cap);
 /* Decode a codestream to int32 samples as OpenJPEG's opj_decode does (src/ebcc_codec.c:1092-1136
  * reads image->comps[0].data).  samples malloc'd. Returns number of pixels or 0. */
 size_t orc_j2k_decode(const uint8_t *cs, size_t cs_size, int32_t **samples, size_t *height, size_t *width);

@@ -81,6 +81,7 @@ def oracle():
         lib.orc_j2k_analysis.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t] + [ctypes.c_void_p] * 6
         lib.orc_j2k_analysis_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t] + [ctypes.c_void_p] * 6 + \
             [ctypes.c_size_t]
+        lib.orc_j2k_analysis_tiled_bytes.argtypes = [ctypes.c_void_p] + [ctypes.c_size_t] * 4 + [ctypes.c_void_p] * 6 + [ctypes.c_size_t]
         if hasattr(lib, "orc_opj_encode"):
             lib.orc_opj_encode.restype = ctypes.c_size_t
             lib.orc_opj_encode.argtypes = lib.orc_j2k_encode.argtypes
@@ -325,7 +326,8 @@ J2K_MAX_PASSES, J2K_CBLK_BYTES = 78, 16 * 1024
 
 class J2kTables:
     """What ebcc_hip_j2k_tables returned: n, h, w, nblocks; coeffs (or None) and q6 [n][h][w]; blocks [n][nblocks] of
-    J2K_BLOCK; rates, disto and bytes packed in the order of blocks; const [n]; retried."""
+    J2K_BLOCK; rates, disto and bytes packed in the order of blocks; const [n]; retried.  From a context for chunks of several
+    frames nblocks is the most code-blocks of any tile position, and a frame's slots past its own hold w = h = 0."""
 
     def passes(self, f, b):
         """(rates, disto) of code-block b of frame f"""
@@ -344,10 +346,16 @@ class J2kTables:
 
 
 class Context:
-    def __init__(self, max_frames, h, w, device=0):
+    def __init__(self, max_frames, h, w, device=0, tiles=None):
+        """tiles: a context for chunks of that many frames (ebcc_hip_create_tiles; frame f is tile f % tiles of its chunk)"""
         self.lib = product()
-        self.h, self.w, self.max_frames = h, w, max_frames
-        self.ptr = self.lib.ebcc_hip_create(device, max_frames, h, w)
+        self.h, self.w, self.max_frames, self.tiles = h, w, max_frames, tiles or 1
+        if tiles is None:
+            self.ptr = self.lib.ebcc_hip_create(device, max_frames, h, w)
+        else:
+            self.lib.ebcc_hip_create_tiles.restype = ctypes.c_void_p
+            self.lib.ebcc_hip_create_tiles.argtypes = [ctypes.c_int] + [ctypes.c_size_t] * 4
+            self.ptr = self.lib.ebcc_hip_create_tiles(device, max_frames, h, w, tiles)
         assert self.ptr, self.lib.ebcc_hip_last_error()
 
     def close(self):
@@ -473,6 +481,10 @@ class Context:
             d = frames
         nb = lib.ebcc_hip_window_plan(self.h, self.w, 0, 0, 1, 1, None, None, 0)
         assert nb > 0, lib.ebcc_hip_last_error()
+        if self.tiles > 1:                                                # (the most code-blocks of any tile position)
+            lib.ebcc_hip_j2k_blocks_per_frame.argtypes = [ctypes.c_void_p]
+            nb = lib.ebcc_hip_j2k_blocks_per_frame(self.ptr)
+            assert nb > 0, nb
         t = J2kTables()
         t.n, t.h, t.w, t.nblocks = n, self.h, self.w, nb
         t.coeffs = np.full((n, self.h, self.w), np.nan, np.float32) if coeffs and d is not None else None
@@ -646,14 +658,17 @@ BLOCK_SINK = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_int32), ctypes.c_int
 COEFF_SINK = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p)
 
 
-def orc_j2k_analysis(img_u16):
+def orc_j2k_analysis(img_u16, tile=0):
     """The oracle's rate-independent half of the encoder for one u16 image (orc_j2k_analysis_bytes and the two sinks): a
     list of code-blocks in packet order, each a dict of w, h, orient, cf (float32 [h][w], the coefficients just before
     quantisation), q (int32 [h][w], six fractional bits), numbps, totalpasses, len, rates (int32 [totalpasses]), disto
-    (float64 [totalpasses]) and bytes."""
+    (float64 [totalpasses]) and bytes.  A [tiles][h][w] array is the stacked image of a chunk of several frames, scaled by
+    the chunk: the code-blocks are those of tile `tile` at its place in the image (orc_j2k_analysis_tiled_bytes)."""
     lib = oracle()
     img = np.ascontiguousarray(img_u16, np.uint16)
-    h, w = img.shape
+    tiles = img.shape[0] if img.ndim == 3 else 1
+    assert 0 <= tile < tiles, (tile, tiles)
+    h, w = img.shape[-2:]
     qs, cfs = [], []
 
     def take_q(q, bw, bh, orient, _user):
@@ -671,8 +686,12 @@ def orc_j2k_analysis(img_u16):
     lib.orc_j2k_set_block_sink(ctypes.cast(sink_q, ctypes.c_void_p), None)
     lib.orc_j2k_set_coeff_sink(ctypes.cast(sink_cf, ctypes.c_void_p), None)
     try:
-        n = lib.orc_j2k_analysis_bytes(img.ctypes.data, h, w, nbp.ctypes.data, tp.ctypes.data, ln.ctypes.data, rates.ctypes.data,
-                                       disto.ctypes.data, data.ctypes.data, data.size)
+        if img.ndim == 3:
+            n = lib.orc_j2k_analysis_tiled_bytes(img.ctypes.data, tiles, h, w, tile, nbp.ctypes.data, tp.ctypes.data, ln.ctypes.data,
+                                                 rates.ctypes.data, disto.ctypes.data, data.ctypes.data, data.size)
+        else:
+            n = lib.orc_j2k_analysis_bytes(img.ctypes.data, h, w, nbp.ctypes.data, tp.ctypes.data, ln.ctypes.data, rates.ctypes.data,
+                                           disto.ctypes.data, data.ctypes.data, data.size)
     finally:
         lib.orc_j2k_set_block_sink(None, None)
         lib.orc_j2k_set_coeff_sink(None, None)

@@ -154,6 +154,57 @@ def test_multi_frame_chunk_extremes(name):
     assert sha(L.orc_decode(s).tobytes()) == c["decoded_sha256"]
 
 
+_tiles = load("tile_positions.json")
+
+
+def _tile_chunks():
+    from tests import _j2k_tables as T
+    return T.fixture_chunks()
+
+
+@pytest.mark.parametrize("backend", [0, 1], ids=["restated-j2k", "openjpeg"])
+@pytest.mark.parametrize("shape,kinds", _tile_chunks(), ids=lambda v: "x".join(map(str, v)) if isinstance(v[0], int) else "+".join(v))
+def test_tile_position_chunk_streams(shape, kinds, backend, monkeypatch):
+    """Chunks whose tiles differ in geometry from position to position (sub-band parities, a first code-block row of 1 to 63
+    lines, more code-blocks at one position than at another) with hostile content in every tile, over the rate ladder and
+    in both bounded modes: streams and decoded fields of the reference build (oracle/make_golden_tiles.py)."""
+    from tests import _j2k_tables as T
+    from tests.test_j2k_gpu import RATES
+    if backend == 1 and (not hasattr(L.oracle(), "orc_opj_version") or not L.opj_version()):
+        pytest.skip("OpenJPEG backend not available on this machine")
+    x = T.chunk(kinds, *shape[1:])
+    assert sha(x.tobytes()) == _tiles["inputs"][T.chunk_id(shape, kinds)], "input differs"
+    jobs = [(T.rate_key(shape, kinds, cr), None, L.make_config(shape, base_cr=cr, error=0.0, residual_type=L.NONE)) for cr in RATES]
+    jobs += [(T.bounded_key(shape, kinds, mode), q, L.make_config(shape, base_cr=base_cr, error=err, residual_type=mode))
+             for mode, err, base_cr, q in T.bounded_modes(shape, kinds)]
+    L.oracle().orc_set_j2k_backend(backend)
+    try:
+        for key, quantile, cfg in jobs:
+            c = _tiles["cases"][key]
+            for k in T.BOUNDED_ENV:
+                monkeypatch.delenv(k, raising=False)
+            if quantile is not None:
+                monkeypatch.setenv("EBCC_INIT_BASE_ERROR_QUANTILE", quantile)
+                monkeypatch.setenv("EBCC_DISABLE_PURE_BASE_COMPRESSION_FALLBACK", "1")
+            s = L.orc_encode(x, cfg)
+            assert len(s) == c["n"] and sha(s) == c["stream_sha256"], key
+            assert sha(L.orc_decode(s).tobytes()) == c["decoded_sha256"], key
+            if "coeffs_size" in c:
+                assert int.from_bytes(s[16:24], "little") == c["coeffs_size"] > 0, key
+    finally:
+        L.oracle().orc_set_j2k_backend(0)
+
+
+def test_tile_position_fixture_holds_every_case():
+    from tests import _j2k_tables as T
+    from tests.test_j2k_gpu import RATES
+    want = {T.rate_key(s, k, cr) for s, k in T.fixture_chunks() for cr in RATES}
+    want |= {T.bounded_key(s, k, b[0]) for s, k in T.fixture_chunks() for b in T.bounded_modes(s, k)}
+    assert set(_tiles["cases"]) == want and len(want) == 38 * 6 + 8 * 2
+    assert set(_tiles["inputs"]) == {T.chunk_id(s, k) for s, k in T.fixture_chunks()}
+    assert _tiles["openjpeg"] == "2.4.0"
+
+
 _live = load("live_checks.json")
 _live_inputs = np.load(os.path.join(L.GOLDEN, "live_checks_inputs.npz"))
 
