@@ -84,8 +84,21 @@ bool j2k_create(ebcc_hip_ctx *ctx)
         ok &= (rc.mnmx = ctx_alloc<double>(ctx, F * 2)) != nullptr;
         ok &= (rc.mval = (short *) ctx_alloc<uint16_t>(ctx, F * (size_t) rc.nodes_cap)) != nullptr;
         ok &= (rc.off = (int *) ctx_alloc<int32_t>(ctx, F * (size_t) (stride + 1))) != nullptr;
-        ok &= (rc.crate = ctx_alloc<uint16_t>(ctx, F * (size_t) rc.cap)) != nullptr;
-        ok &= (rc.cdisto = ctx_alloc<double>(ctx, F * (size_t) rc.cap)) != nullptr;
+        const char *e = getenv("EBCC_HIP_RATE_WALK");
+        jb->rate_walk = e && atoi(e);
+        rc.crate = nullptr; rc.cdisto = nullptr; rc.wlim = nullptr; rc.wnp = nullptr; rc.wcnt = nullptr;
+        if (jb->rate_walk) {
+            ok &= (rc.crate = ctx_alloc<uint16_t>(ctx, F * (size_t) rc.cap)) != nullptr;
+            ok &= (rc.cdisto = ctx_alloc<double>(ctx, F * (size_t) rc.cap)) != nullptr;
+        } else {
+            // (two buffers, as in walk mode: the counts in front of the pass counts they index)
+            const size_t cnt_bytes = (F * (size_t) stride * sizeof(uint16_t) + 15) & ~(size_t) 15;
+            uint8_t *small = nullptr;
+            ok &= (rc.wlim = ctx_alloc<double>(ctx, F * (size_t) (rc.cap + stride))) != nullptr;
+            ok &= (small = ctx_alloc<uint8_t>(ctx, cnt_bytes + F * (size_t) (rc.cap + stride))) != nullptr;
+            rc.wcnt = (unsigned short *) small;
+            rc.wnp = small ? small + cnt_bytes : nullptr;
+        }
     }
     ok &= (jb->rates = (int *) ctx_alloc<int32_t>(ctx, groups * 64 * kJ2kMaxPasses)) != nullptr;
     ok &= (jb->disto = ctx_alloc<double>(ctx, groups * 64 * kJ2kMaxPasses)) != nullptr;

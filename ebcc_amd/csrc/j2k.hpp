@@ -155,10 +155,17 @@ struct J2kBuffers {
         double *mnmx;             // [frames][2]
         short *mval;              // [frames][nodes_cap]
         int *off;                 // [frames][stride + 1]
-        unsigned short *crate;    // [frames][cap] rates, code-block b's passes at off[b] ..
-        double *cdisto;           // [frames][cap]
+        unsigned short *crate;    // [frames][cap] rates, code-block b's passes at off[b] ..  (walk mode only)
+        double *cdisto;           // [frames][cap]                                            (walk mode only)
+        // walk tables (rate_walk.hpp), built behind the distortion tables by launch_j2k_rate_tables: code-block b's walks at
+        // off[b] + b .. (a code-block of tp passes has at most tp + 1).  Null in walk mode.
+        double *wlim;             // [frames][cap + stride] limits, falling
+        unsigned char *wnp;       // [frames][cap + stride] passes of the walk from its limit up to the one before
+        unsigned short *wcnt;     // [frames][stride] walks of each code-block (one allocation with wnp)
         int nodes_cap, cap;
     } rate_cache;
+    bool rate_walk;               // EBCC_HIP_RATE_WALK=1 (read when the context is made): k_rate walks the pass tables at every
+                                  // threshold instead of looking the walk up in the walk tables - the cross-check of the tables
     uint8_t *cblk_bytes;          // [frames*nblocks][kJ2kCblkBytes]
     uint8_t *stream;              // [frames][stream_cap] codestream
     size_t stream_cap;
@@ -274,6 +281,8 @@ void launch_j2k_tier1(const J2kBuffers &jb, int n_frames, hipStream_t s, bool si
 bool j2k_tier1_retry(const J2kBuffers &jb, int n_frames, const J2kFrame *host_jf, hipStream_t s);
 // rate allocation for jf[f].cr (opj_tcd_rateallocate) -> npass, jf.body_bytes/stream_bytes
 void launch_j2k_rate(const J2kBuffers &jb, int n_frames, const int *d_active, hipStream_t s, const int *have_rate = nullptr);
+// the walk tables of n_frames analysed frames (RateCache::wlim ..): behind every launch that writes rates / distortions
+void launch_j2k_rate_tables(const J2kBuffers &jb, int n_frames, hipStream_t s);
 void j2k_probe_hist_dump(const char *what);                          // EBCC_HIP_T1_STATS=1 diagnostics (j2k_rate.hip)
 // the same for the candidate rates jb.cand_cr (two per frame) into the candidate slots; launch_j2k_rate_publish makes
 // candidate jb.cand_sel[f] the frame's current layer and sets jb.have_rate

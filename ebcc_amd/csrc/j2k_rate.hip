@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "j2k.hpp"
+#include "rate_walk.hpp"
 #include "t1_core.hpp"
 #include "t1_device.hpp"
 
@@ -133,6 +134,8 @@ __device__ int packet_header(int r, const J2kGeom &g, const Trees &t, const shor
 // k_rate's own arrays behind the carve-up: the per-block table offsets, then three sets of path masks and a flag
 __host__ __device__ inline size_t rate_off_bytes(int nblocks) { return ((size_t) (nblocks + 1) * 4 + 15) & ~(size_t) 15; }
 __host__ __device__ inline size_t rate_path_bytes(int nblocks) { return (size_t) nblocks * 2 * 8 * 3 + (((size_t) nblocks + 7) & ~(size_t) 7); }
+// ... table mode: three sets of walk indices (16 bits) in place of the masks
+__host__ __device__ inline size_t rate_index_bytes(int nblocks) { return (((size_t) nblocks * 2 * 3 + 7) & ~(size_t) 7) + (((size_t) nblocks + 7) & ~(size_t) 7); }
 
 __host__ __device__ inline size_t rate_lds_bytes(int nblocks, int nodes)
 {
@@ -250,105 +253,17 @@ struct PassTab {
     template <bool LDS> __device__ int base_of(int b) const { if constexpr (LDS) return l_off[b]; else return b * kJ2kMaxPasses; }
 };
 
-// opj_tcd_makelayer for one quality layer
-// opj_tcd_makelayer's greedy walk over the passes of code-block b: passes taken (count returned, bit mask in m0 / m1)
-// `from` > 0: the walk is taken up at pass `from` with passes [0, from) decided already - their mask in m0 / m1 on entry,
-// the last pass taken among them `n_in` (count, 0: none) - see the tail of k_rate's bisection
+// The pass tables as rate_walk.hpp's functions read them (walk_block, walk_interval, walk_table_build)
 template <bool LDS>
-__device__ inline int walk_block(const PassTab &pt, const int *totalpasses, int gid0, int b, double thresh, unsigned long long &m0,
-                                 unsigned long long &m1, int from = 0, int n_in = 0)
-{
-    if (from == 0) m0 = m1 = 0;
-    int tp;
-    if constexpr (LDS) tp = pt.l_off[b + 1] - pt.l_off[b]; else tp = totalpasses[gid0 + b];
-    const int base = pt.base_of<LDS>(b);
-    int n = n_in;
-    if (thresh < 0) return tp;
-    int rbase = 0;                                                   // rate / distortion of the last pass taken
-    double dbase = 0;
-    if (n_in > 0) { rbase = pt.rate<LDS>(base, n_in - 1); dbase = pt.dist<LDS>(base, n_in - 1); }
-    for (int p = from; p < tp; p++) {
-        const int rp = pt.rate<LDS>(base, p);
-        const double dp = pt.dist<LDS>(base, p);
-        unsigned int dr;
-        double dd;
-        if (n == 0) { dr = (unsigned int) rp; dd = dp; }
-        else { dr = (unsigned int) (rp - rbase); dd = dp - dbase; }
-        // OpenJPEG's test is  thresh - fl(dd / dr) < DBL_EPSILON.  The outcome is already certain whenever dd and
-        // thresh * dr differ by more than rounding can bridge (1e-11 relative, against 2^-52 per operation); only the
-        // narrow band in between is divided.  (The reject shortcut also needs DBL_EPSILON to be negligible next to
-        // thresh.)
-        bool take;
-        if (!dr) take = dd != 0;
-        else {
-            const double tdr = thresh * (double) dr;
-            if (dd >= tdr * 1.00000000001) take = true;
-            else if (thresh >= 1e-4 && dd <= tdr * 0.99999999999) take = false;
-            else take = thresh - (dd / dr) < DBL_EPSILON;
-        }
-        if (take) {
-            n = p + 1; rbase = rp; dbase = dp;
-            if (p < 64) m0 |= 1ull << p; else m1 |= 1ull << (p - 64);
-        }
-    }
-    return n;
-}
-
-// The thresholds at which a given greedy walk IS the walk: a pass with slope s = fl(dd / dr) is taken iff fl(thresh - s) <
-// DBL_EPSILON, which holds up to a limit T(s) and fails from it on (the difference is monotone in thresh).  So the walk
-// that takes exactly the passes of (m0, m1) from pass `from` on (the passes below it are given: last one taken n_in) is
-// the walk at thresh iff A <= thresh < B, with B the smallest limit of a pass it takes and A the largest limit of a pass
-// it leaves - two numbers per walk instead of a walk per threshold (the tail of k_rate's bisection).
-__device__ inline double next_up(double x)       // the next double above a finite x
-{
-    long long u = __double_as_longlong(x);
-    if (x == 0.0) return __longlong_as_double(1ll);
-    u += x > 0.0 ? 1 : -1;
-    return __longlong_as_double(u);
-}
-__device__ inline double next_down(double x) { return -next_up(-x); }
-__device__ inline double take_limit(double s)
-{
-    double t = s + DBL_EPSILON;                                        // close to the limit; settle on it exactly
-    for (int k = 0; k < 8 && (t - s) < DBL_EPSILON; k++) t = next_up(t);
-    for (int k = 0; k < 8; k++) { const double d = next_down(t); if ((d - s) < DBL_EPSILON) break; t = d; }
-    return t;
-}
-// [tlo, thi]: the bracket the thresholds to come lie in.  A pass whose slope is clearly outside it (by 1e-9 relative; only
-// used when the bracket is far above DBL_EPSILON) either does not constrain them at all or rules the walk out for all of
-// them - its exact limit is not needed, nor the division that gives its slope.
-template <bool LDS>
-__device__ inline void walk_interval(const PassTab &pt, const int *totalpasses, int gid0, int b, unsigned long long m0, unsigned long long m1,
-                                     int from, int n_in, double tlo, double thi, double &A, double &B)
-{
-    int tp;
-    if constexpr (LDS) tp = pt.l_off[b + 1] - pt.l_off[b]; else tp = totalpasses[gid0 + b];
-    const int base = pt.base_of<LDS>(b);
-    int n = n_in, rbase = 0;
-    double dbase = 0;
-    if (n_in > 0) { rbase = pt.rate<LDS>(base, n_in - 1); dbase = pt.dist<LDS>(base, n_in - 1); }
-    A = -DBL_MAX; B = DBL_MAX;
-    const bool coarse = tlo >= 1e-4;
-    for (int p = from; p < tp; p++) {
-        const int rp = pt.rate<LDS>(base, p);
-        const double dp = pt.dist<LDS>(base, p);
-        const unsigned int dr = n == 0 ? (unsigned int) rp : (unsigned int) (rp - rbase);
-        const double dd = n == 0 ? dp : dp - dbase;
-        const bool taken = p < 64 ? (m0 >> p) & 1ull : (m1 >> (p - 64)) & 1ull;
-        if (dr) {
-            const double fdr = (double) dr;
-            if (coarse && dd > thi * fdr * 1.000000001) {                // limit above every threshold to come
-                if (!taken) A = DBL_MAX;
-            } else if (coarse && dd < tlo * fdr * 0.999999999) {         // limit below every threshold to come
-                if (taken) B = -DBL_MAX;
-            } else {
-                const double lim = take_limit(dd / fdr);
-                if (taken) B = lim < B ? lim : B; else A = lim > A ? lim : A;
-            }
-        } else if (taken != (dd != 0)) { A = DBL_MAX; B = -DBL_MAX; }    // (cannot happen for a walk that was walked: never matches)
-        if (taken) { n = p + 1; rbase = rp; dbase = dp; }
-    }
-}
+struct PassView {
+    const PassTab &pt;
+    const int *totalpasses;
+    int gid0;
+    __device__ int passes(int b) const { if constexpr (LDS) return pt.l_off[b + 1] - pt.l_off[b]; else return totalpasses[gid0 + b]; }
+    __device__ int base_of(int b) const { return pt.template base_of<LDS>(b); }
+    __device__ int rate(int base, int p) const { return pt.template rate<LDS>(base, p); }
+    __device__ double dist(int base, int p) const { return pt.template dist<LDS>(base, p); }
+};
 
 // `path` (optional): [2][nblocks] bit masks of the passes taken, i.e. the whole greedy walk and not just its end;
 // `frozen` (optional): code-blocks whose walk cannot change any more (k_rate) keep their assignment
@@ -359,7 +274,7 @@ __device__ void make_layer_impl(const J2kGeom &g, RateLds &L, const int *totalpa
     for (int b = lane; b < g.nblocks; b += NT) {
         if (frozen && frozen[b]) continue;
         unsigned long long m0, m1;
-        const int n = walk_block<LDS>(pt, totalpasses, gid0, b, thresh, m0, m1);
+        const int n = walk_block(PassView<LDS>{pt, totalpasses, gid0}, b, thresh, m0, m1);
         L.npass[b] = (short) n;
         if (path) { path[b] = m0; path[g.nblocks + b] = m1; }
     }
@@ -555,8 +470,71 @@ __device__ int layer_bytes_fast(const J2kGeom &g, RateLds &L, const int *rates, 
 }
 
 // ================================================================================================
-// rate allocation kernel: one workgroup (one wave) per frame
+// walk tables (rate_walk.hpp): one lane per code-block, a wave of 64 code-blocks per workgroup.  Every lane goes through
+// its code-block's passes once per walk - about passes x walks steps - so the wave first copies the pass tables of its 64
+// code-blocks into LDS, pass-major (pass p of lane l at p * 64 + l): the lanes are at the same pass at the same time, and
+// that way they read neighbouring words.  (From global memory the chain of loads was 2.1 ms per 85-frame launch; from LDS
+// it is 0.8 ms, in this layout or packed code-block by code-block - the rest is each lane's chain of double arithmetic.)
+// The tables pack at the prefix sums of the pass counts over the frame (the offsets k_rate works out for itself),
+// code-block b at off[b] + b.
 // ================================================================================================
+constexpr int kTableLanes = 64;
+constexpr size_t kTableLds = (size_t) kTableLanes * kJ2kMaxPasses * 10;
+
+struct PassColumn {                    // one lane's code-block in that layout, as rate_walk.hpp reads it
+    const __attribute__((address_space(3))) double *d;
+    const __attribute__((address_space(3))) unsigned short *r;
+    int tp;
+    __device__ int passes(int) const { return tp; }
+    __device__ int base_of(int) const { return 0; }
+    __device__ int rate(int, int p) const { return r[p * kTableLanes]; }
+    __device__ double dist(int, int p) const { return d[p * kTableLanes]; }
+};
+
+__global__ __launch_bounds__(kTableLanes) void k_rate_tables(const int *__restrict__ totalpasses, const int *__restrict__ rates,
+                                                              const double *__restrict__ disto, const J2kGeom *geom,
+                                                              const FrameState *fs, J2kBuffers::RateCache cache)
+{
+    extern __shared__ unsigned char lds_raw[];                           // (no static LDS: the doubles stay aligned)
+    const int frame = blockIdx.y, lane = threadIdx.x;
+    if (fs[frame].const_field) return;
+    const J2kGeom &g = j2k_frame_geom(geom, frame);
+    const int gid0 = frame * g.stride, b0 = blockIdx.x * kTableLanes;
+    if (b0 >= g.nblocks) return;
+    auto passes_of = [&](int b) { return b < g.nblocks ? min(max(totalpasses[gid0 + b], 0), kJ2kMaxPasses) : 0; };
+    // passes of the code-blocks before this wave's, then of those before this lane's
+    int before = 0;
+    for (int c = 0; c < b0; c += kTableLanes) before += passes_of(c + lane);
+    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d);
+    const int b = b0 + lane, tp = passes_of(b);
+    int x = tp;
+    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
+    before += x - tp;
+    double *l_disto = (double *) lds_raw;
+    unsigned short *l_rate = (unsigned short *) (l_disto + kTableLanes * kJ2kMaxPasses);
+    for (int i = 0; i < kTableLanes && b0 + i < g.nblocks; i++) {        // a code-block's row at a time, a pass per lane
+        const int n = __shfl(tp, i);
+        const size_t row = (size_t) (gid0 + b0 + i) * kJ2kMaxPasses;
+        for (int p = lane; p < n; p += kTableLanes) {
+            l_rate[p * kTableLanes + i] = (unsigned short) rates[row + p];
+            l_disto[p * kTableLanes + i] = disto[row + p];
+        }
+    }
+    __syncthreads();
+    if (b >= g.nblocks) return;
+    typedef __attribute__((address_space(3))) double lds_double;
+    typedef __attribute__((address_space(3))) unsigned short lds_ushort;
+    const PassColumn col{(const lds_double *) l_disto + lane, (const lds_ushort *) l_rate + lane, tp};
+    const size_t o = (size_t) frame * (size_t) (cache.cap + g.stride) + (size_t) (before + b);   // (off[b] + b: tp + 1 entries to itself)
+    cache.wcnt[gid0 + b] = (unsigned short) walk_table_build(col, 0, cache.wlim + o, cache.wnp + o, tp + 1);
+}
+
+// ================================================================================================
+// rate allocation kernel: one workgroup per frame.  TAB: the layer of a threshold is looked up in the frame's walk tables
+// (k_rate_tables) and a walk is known by its index there; otherwise (EBCC_HIP_RATE_WALK=1) the pass tables are staged in LDS
+// and walked at every threshold, and a walk is known by the mask of the passes it takes.
+// ================================================================================================
+template <bool TAB>
 __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ numbps, const int *__restrict__ totalpasses,
                                                         const int *__restrict__ rates, const double *__restrict__ disto,
                                                         int *__restrict__ npass_out, const J2kGeom *geom, J2kFrame *jf,
@@ -625,14 +603,21 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
     // and the code-blocks whose walk is settled
     unsigned long long *p_cur = (unsigned long long *) (extra + rate_off_bytes(g.nblocks));
     unsigned long long *p_lo = p_cur + 2 * g.nblocks, *p_hi = p_lo + 2 * g.nblocks;
-    unsigned char *frozen = (unsigned char *) (p_hi + 2 * g.nblocks);
+    // table mode: the same three walks as indices into the code-block's walk table (kNoWalk: a threshold the table does
+    // not hold - such a walk equals no other, so its code-block is never settled and its sizes are always worked out)
+    constexpr unsigned short kNoWalk = 0xFFFFu;
+    unsigned short *i_cur = (unsigned short *) p_cur, *i_lo = i_cur + g.nblocks, *i_hi = i_lo + g.nblocks;
+    unsigned char *frozen = TAB ? (unsigned char *) p_cur + (((size_t) g.nblocks * 2 * 3 + 7) & ~(size_t) 7) : (unsigned char *) (p_hi + 2 * g.nblocks);
     double *l_disto = (double *) (frozen + (((size_t) g.nblocks + 7) & ~(size_t) 7));
+    const double *const w_lim = TAB ? cache.wlim + (size_t) frame * (size_t) (cache.cap + g.stride) : nullptr;
+    const unsigned char *const w_np = TAB ? cache.wnp + (size_t) frame * (size_t) (cache.cap + g.stride) : nullptr;
+    const unsigned short *const w_cnt = TAB ? cache.wcnt + gid0 : nullptr;
     for (int b = lane; b < g.nblocks; b += kRateThreads) frozen[b] = 0;
     // table offsets: exclusive prefix sums of the pass counts (block scan: wave shuffles + one LDS round per 512 code-blocks;
     // a single lane walking the ~300 counts cost 8 us of every call)
     if (cached) {
         for (int b = lane; b <= g.nblocks; b += kRateThreads) l_off[b] = c_off[b];
-        if (lane == 0) { const int running = c_off[g.nblocks]; s_fit = running <= pass_capacity ? running : -1; }
+        if (lane == 0) { const int running = c_off[g.nblocks]; s_fit = !TAB && running <= pass_capacity ? running : -1; }
     } else {
         __shared__ int s_scan[kRateThreads / 64];
         int running = 0;
@@ -649,7 +634,7 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
             running += tot;
             __syncthreads();
         }
-        if (lane == 0) { l_off[g.nblocks] = running; s_fit = running <= pass_capacity ? running : -1; }
+        if (lane == 0) { l_off[g.nblocks] = running; s_fit = !TAB && running <= pass_capacity ? running : -1; }
         __syncthreads();
         if (record) for (int b = lane; b <= g.nblocks; b += kRateThreads) c_off[b] = l_off[b];
     }
@@ -691,6 +676,28 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
 #ifdef EBCC_RATE_PROFILE
     t_s[3] = wall_clock64() - t_start;
 #endif
+    // Table mode: the walk of every open code-block at `thresh`, from its walk table - its index into `idx`, its passes into
+    // L.npass when `set_npass`.  `bracket`: thresh lies between the bracket ends whose walks are known (hi_seen / lo_seen), so
+    // only the entries between theirs are searched - one or two once the bracket has shrunk.  A threshold the table does
+    // not hold (none should be: below zero is rate 0's "every pass", below the table's end a table cut short) is walked.
+    auto lookup_layer = [&](double thresh, unsigned short *idx, bool set_npass, bool skip_frozen, bool bracket, bool lo_known, bool hi_known) {
+        for (int b = lane; b < g.nblocks; b += kRateThreads) {
+            if (skip_frozen && frozen[b]) continue;
+            const int o = l_off[b] + b, cnt = w_cnt[b];
+            int a = 0, z = cnt - 1;
+            if (bracket && hi_known && i_hi[b] != kNoWalk) a = i_hi[b];
+            if (bracket && lo_known && i_lo[b] != kNoWalk) z = i_lo[b];
+            const int k = thresh < 0 ? -1 : walk_table_find(w_lim + o, a, z, thresh);
+            if (idx) idx[b] = k < 0 ? kNoWalk : (unsigned short) k;
+            if (set_npass) {
+                int n;
+                if (k >= 0) n = w_np[o + k];
+                else { unsigned long long m0, m1; n = walk_block(PassView<false>{pt, totalpasses, gid0}, b, thresh, m0, m1); }
+                L.npass[b] = (short) n;
+            }
+        }
+        __syncthreads();
+    };
     int prev_bytes = 0;
     // size of the current assignment; identical assignments (late bisection steps) reuse the previous result
     auto sized = [&]() -> int {
@@ -755,7 +762,7 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
         __syncthreads();
         if (lane == 0) {
             cache.mnmx[2 * frame] = mn; cache.mnmx[2 * frame + 1] = mx;
-            if (pt.lds) { __threadfence(); __hip_atomic_store(&cache.ok[frame], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+            if (TAB || pt.lds) { __threadfence(); __hip_atomic_store(&cache.ok[frame], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
         }
     }
     }
@@ -808,15 +815,26 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
             if (!t_replay_end) t_replay_end = wall_clock64();
 #endif
             // the walks at bracket ends that came from the record (needed to tell settled code-blocks)
+            if constexpr (TAB) {
+                if (hi_from_rec) { lookup_layer(hi, i_hi, false, false, false, false, false); hi_seen = true; hi_from_rec = false; }
+                if (lo_from_rec) { lookup_layer(lo, i_lo, false, false, false, false, false); lo_seen = true; lo_from_rec = false; }
+                { RP_T0; lookup_layer(thresh, i_cur, true, true, true, lo_seen, hi_seen); RP_ADD(t_ml); }
+            } else {
             if (hi_from_rec) { make_layer<kRateThreads>(g, L, totalpasses, pt, gid0, hi, lane, p_hi); hi_seen = true; hi_from_rec = false; }
             if (lo_from_rec) { make_layer<kRateThreads>(g, L, totalpasses, pt, gid0, lo, lane, p_lo); lo_seen = true; lo_from_rec = false; }
             { RP_T0; make_layer<kRateThreads>(g, L, totalpasses, pt, gid0, thresh, lane, p_cur, frozen); RP_ADD(t_ml); }
+            }
             if (lane == 0) s_nun = 0;       // (after the barrier make_layer ends with: every thread is done with the previous
                                             //  step's value; before the barriers below: ahead of this step's additions)
             // late iterations alternate between the assignments of the two bracket ends: their sizes are known
             int at_lo = lo_seen, at_hi = hi_seen;
             for (int b = lane; b < g.nblocks; b += kRateThreads) {
                 if (frozen[b]) continue;
+                if constexpr (TAB) {
+                    if (i_cur[b] == kNoWalk || i_cur[b] != i_lo[b]) at_lo = 0;
+                    if (i_cur[b] == kNoWalk || i_cur[b] != i_hi[b]) at_hi = 0;
+                    continue;
+                }
                 if (p_cur[b] != p_lo[b] || p_cur[g.nblocks + b] != p_lo[g.nblocks + b]) at_lo = 0;
                 if (p_cur[b] != p_hi[b] || p_cur[g.nblocks + b] != p_hi[g.nblocks + b]) at_hi = 0;
             }
@@ -848,11 +866,19 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
             // of them, all remaining iterations see this assignment and this size, and whichever end they settle on
             // (`stable` = hi when it does not fit, the limit point when it does) the layer is the current one.
             unsigned long long *end = fits ? p_hi : p_lo;
+            unsigned short *i_end = fits ? i_hi : i_lo;
             int same = lo_seen && hi_seen;
             for (int b = lane; b < g.nblocks; b += kRateThreads) {
                 if (frozen[b]) continue;
-                end[b] = p_cur[b]; end[g.nblocks + b] = p_cur[g.nblocks + b];
-                if (lo_seen && hi_seen && p_lo[b] == p_hi[b] && p_lo[g.nblocks + b] == p_hi[g.nblocks + b]) frozen[b] = 1;
+                bool settled;
+                if constexpr (TAB) {
+                    i_end[b] = i_cur[b];
+                    settled = lo_seen && hi_seen && i_lo[b] == i_hi[b] && i_lo[b] != kNoWalk;
+                } else {
+                    end[b] = p_cur[b]; end[g.nblocks + b] = p_cur[g.nblocks + b];
+                    settled = lo_seen && hi_seen && p_lo[b] == p_hi[b] && p_lo[g.nblocks + b] == p_hi[g.nblocks + b];
+                }
+                if (settled) frozen[b] = 1;
                 else {
                     same = 0;
                     const int k = atomicAdd(&s_nun, 1);              // the code-blocks still open, for the tail below
@@ -877,7 +903,7 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
                     // ~40 - with the common part's mask and its last taken pass as the start state.
                     int from = 0, n_in = 0;
                     unsigned long long c0 = 0, c1 = 0;
-                    if (b >= 0) {
+                    if (!TAB && b >= 0) {
                         const unsigned long long d0 = p_lo[b] ^ p_hi[b], d1 = p_lo[nb + b] ^ p_hi[nb + b];
                         from = d0 ? __builtin_ctzll(d0) : (d1 ? 64 + __builtin_ctzll(d1) : 0);
                         if (from > 0) {
@@ -889,13 +915,21 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
                     // ... and which thresholds give exactly the walk of the lower end, which exactly that of the upper
                     // end, is worked out once per code-block (walk_interval): a step is then two comparisons per lane.
                     double a_lo = -DBL_MAX, b_lo = DBL_MAX, a_hi = -DBL_MAX, b_hi = DBL_MAX;
-                    if (b >= 0) {
+                    if (TAB && b >= 0) {
+                        // (table mode: they are the entries of the two walks; a walk the table does not hold matches nothing)
+                        const double *wl = w_lim + l_off[b] + b;
+                        const int klo = i_lo[b], khi = i_hi[b];
+                        if (klo != kNoWalk) { a_lo = wl[klo]; b_lo = klo > 0 ? wl[klo - 1] : DBL_MAX; } else { a_lo = DBL_MAX; b_lo = -DBL_MAX; }
+                        if (khi != kNoWalk) { a_hi = wl[khi]; b_hi = khi > 0 ? wl[khi - 1] : DBL_MAX; } else { a_hi = DBL_MAX; b_hi = -DBL_MAX; }
+                    } else if (b >= 0) {
                         if (pt.lds) {
-                            walk_interval<true>(pt, totalpasses, gid0, b, p_lo[b], p_lo[nb + b], from, n_in, tlo, thi, a_lo, b_lo);
-                            walk_interval<true>(pt, totalpasses, gid0, b, p_hi[b], p_hi[nb + b], from, n_in, tlo, thi, a_hi, b_hi);
+                            const PassView<true> pv{pt, totalpasses, gid0};
+                            walk_interval(pv, b, p_lo[b], p_lo[nb + b], from, n_in, tlo, thi, a_lo, b_lo);
+                            walk_interval(pv, b, p_hi[b], p_hi[nb + b], from, n_in, tlo, thi, a_hi, b_hi);
                         } else {
-                            walk_interval<false>(pt, totalpasses, gid0, b, p_lo[b], p_lo[nb + b], from, n_in, tlo, thi, a_lo, b_lo);
-                            walk_interval<false>(pt, totalpasses, gid0, b, p_hi[b], p_hi[nb + b], from, n_in, tlo, thi, a_hi, b_hi);
+                            const PassView<false> pv{pt, totalpasses, gid0};
+                            walk_interval(pv, b, p_lo[b], p_lo[nb + b], from, n_in, tlo, thi, a_lo, b_lo);
+                            walk_interval(pv, b, p_hi[b], p_hi[nb + b], from, n_in, tlo, thi, a_hi, b_hi);
                         }
                     }
                     (void) c0; (void) c1;
@@ -942,7 +976,10 @@ __global__ __launch_bounds__(kRateThreads) void k_rate(const int *__restrict__ n
 #ifdef EBCC_RATE_PROFILE
     t_loop_end = wall_clock64();
 #endif
-    if (!converged) make_layer<kRateThreads>(g, L, totalpasses, pt, gid0, good, lane);
+    if (!converged) {
+        if constexpr (TAB) lookup_layer(good, nullptr, true, false, false, false, false);
+        else make_layer<kRateThreads>(g, L, totalpasses, pt, gid0, good, lane);
+    }
     const int body = sized();
     for (int b = lane; b < g.nblocks; b += kRateThreads) npass_out[gid0 + b] = L.npass[b];
     if (lane == 0 && candidate) {
@@ -1577,19 +1614,35 @@ size_t rate_lds(const J2kBuffers &jb)
 // ================================================================================================
 static void rate_launch(const J2kBuffers &jb, int n_frames, const int *d_active, hipStream_t s, bool candidates, const int *have_rate)
 {
-    // dynamic LDS: the carve-up, the per-block table offsets, then as many (rate, distortion) entries as fit
-    const size_t head = ((rate_lds(jb) + 15) & ~(size_t) 15) + rate_off_bytes(jb.geom.stride) + rate_path_bytes(jb.geom.stride);
+    // dynamic LDS: the carve-up, the per-block table offsets and the three walks per code-block; in walk mode then as many
+    // (rate, distortion) entries as fit.  Table mode stages nothing: a frame takes 15-25 KB instead of a whole CU's LDS.
+    const size_t carve = ((rate_lds(jb) + 15) & ~(size_t) 15) + rate_off_bytes(jb.geom.stride);
     const size_t budget = 150 * 1024;
-    size_t want = (size_t) jb.geom.stride * kJ2kMaxPasses;
-    if (head + want * 10 + 16 > budget) want = head + 16 < budget ? (budget - head - 16) / 10 : 0;
-    const size_t lds = head + want * 10 + 16;
     static std::once_flag once;
     std::call_once(once, [] {
-        EBCC_HIP_CHECK(hipFuncSetAttribute((const void *) k_rate, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        EBCC_HIP_CHECK(hipFuncSetAttribute((const void *) k_rate<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        EBCC_HIP_CHECK(hipFuncSetAttribute((const void *) k_rate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     });
-    hipLaunchKernelGGL(k_rate, dim3(n_frames, candidates ? 2 : 1), dim3(kRateThreads), lds, s, jb.numbps, jb.totalpasses, jb.rates,
-                       jb.disto, candidates ? jb.cand_npass : jb.npass, jb.d_geom, jb.jf, jb.fs, d_active, (int) want, jb.rate_path, jb.rate_path_n,
-                       candidates ? jb.cand_cr : nullptr, jb.cand_out, (size_t) jb.max_frames * (size_t) jb.geom.stride, have_rate, jb.rate_cache);
+    size_t want = 0, lds = carve + rate_index_bytes(jb.geom.stride) + 16;
+    if (jb.rate_walk) {
+        const size_t head = carve + rate_path_bytes(jb.geom.stride);
+        want = (size_t) jb.geom.stride * kJ2kMaxPasses;
+        if (head + want * 10 + 16 > budget) want = head + 16 < budget ? (budget - head - 16) / 10 : 0;
+        lds = head + want * 10 + 16;
+    }
+    hipLaunchKernelGGL(jb.rate_walk ? k_rate<false> : k_rate<true>, dim3(n_frames, candidates ? 2 : 1), dim3(kRateThreads), lds, s, jb.numbps,
+                       jb.totalpasses, jb.rates, jb.disto, candidates ? jb.cand_npass : jb.npass, jb.d_geom, jb.jf, jb.fs, d_active, (int) want,
+                       jb.rate_path, jb.rate_path_n, candidates ? jb.cand_cr : nullptr, jb.cand_out,
+                       (size_t) jb.max_frames * (size_t) jb.geom.stride, have_rate, jb.rate_cache);
+    EBCC_HIP_LAUNCH_CHECK();
+}
+
+void launch_j2k_rate_tables(const J2kBuffers &jb, int n_frames, hipStream_t s)
+{
+    if (jb.rate_walk) return;
+    ScopedTiming t("rate_alloc", s);                                     // (under the rate allocation's name: it is its set-up)
+    hipLaunchKernelGGL(k_rate_tables, dim3(ceil_div(jb.geom.stride, kTableLanes), n_frames), dim3(kTableLanes), kTableLds, s, jb.totalpasses,
+                       jb.rates, jb.disto, jb.d_geom, jb.fs, jb.rate_cache);
     EBCC_HIP_LAUNCH_CHECK();
 }
 
