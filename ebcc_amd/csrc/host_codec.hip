@@ -7,6 +7,7 @@
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include <climits>
 #include "array_stats.hpp"
+#include "regrid.hpp"
 
 using namespace ebcc;
 
@@ -1076,7 +1077,7 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
-// ---- consumers of decoded frames (audit, reduce decode, area series).  What one asks the driver for, its own arguments checked:
+// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode).  What one asks the driver for, its own arguments checked:
 struct DecodedAsk {
     const uint8_t *const *streams = nullptr;
     const size_t *sizes = nullptr, *names = nullptr;   // names[i]: the number stream i has in the caller's list, for a message (null: i)
@@ -1212,6 +1213,39 @@ int series_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
         area_fold(set, AreaItems{decoded, bb.rows * bb.cols, (unsigned) bb.cols, (unsigned) bb.row0, (unsigned) bb.col0}, k, (size_t) ctx->height, (size_t) ctx->width,
                   *spec, out + lo * spec->n_regions);
         pt.mark("series: fold");
+    });
+}
+
+// ---- regrid decode: the same fields on another grid (include/ebcc_hip.h: ebcc_hip_regrid_spec; k_regrid, regrid.hip)
+// The bounding box of the supports is what is decoded, and every batch is resampled where it was decoded and writes its own
+// frames of the output: batches never meet, so the two sets run free.  The tables go up once per engine set, ahead of the set's
+// first batch (the window and the full decode keep no table of their own in set->boxes).  host: the output is pageable host
+// memory - a batch is resampled into the set's device image (io) and only that crosses PCIe.
+int regrid_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_regrid_spec *spec,
+                 float *out, bool host)
+{
+    ebcc_hip_region bb{};
+    size_t out_pix = 0;
+    bool up[2] = {false, false};
+    return consume_decoded(who, ctx, false, false, [&](DecodedAsk &a) {
+        const long checked = regrid_checked(who, (size_t) ctx->height, (size_t) ctx->width, spec, &bb);
+        if (checked < 0) return false;
+        out_pix = (size_t) checked;
+        size_t bytes = 0;
+        if (!streams || !sizes || !out || ((uintptr_t) out & 3) || n_frames < 1) { set_error("%s: bad arguments", who); return false; }
+        if (__builtin_mul_overflow(n_frames, out_pix * sizeof(float), &bytes)) { set_error("%s: the size of the output overflows", who); return false; }
+        a.streams = streams; a.sizes = sizes; a.n = n_frames; a.out = out;
+        a.box = bb;
+        a.parsed_first = true;
+        a.decode_mark = "regrid: decode";
+        return true;
+    }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
+        bool &sent = up[set != ctx];
+        if (!sent) { regrid_upload(set, *spec, bb); sent = true; }
+        float *const d = host ? io_buffer(set, std::min(n_frames, ctx->max_frames) * out_pix * sizeof(float)) : out + lo * out_pix;
+        regrid_items(set, RegridItems{decoded, bb.rows * bb.cols, (unsigned) bb.cols, (unsigned) bb.row0, (unsigned) bb.col0}, k, (size_t) ctx->width, *spec, d);
+        if (host) copy_pageable(set, out + lo * out_pix, d, k * out_pix * sizeof(float), true);
+        pt.mark("regrid: map");
     });
 }
 
@@ -2024,6 +2058,48 @@ int ebcc_hip_series_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, cons
 {
     EBCC_API_TRY
     return series_shard("ebcc_hip_series_shard", ctx, streams, sizes, n_frames, spec, out);
+    EBCC_API_CATCH(1)
+}
+
+// ---- regrid decode (regrid_shard above): decoded frames resampled by a separable map, on the device
+long ebcc_hip_regrid_check(size_t height, size_t width, const ebcc_hip_regrid_spec *spec, ebcc_hip_region *bounding)
+{
+    EBCC_API_TRY
+    return regrid_checked("ebcc_hip_regrid_check", height, width, spec, bounding);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_regrid_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, size_t height, size_t width, const ebcc_hip_regrid_spec *spec,
+                          float *d_out)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_regrid_items";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || !d_out || ((uintptr_t) d_out & 3) || n_items < 1) { set_error("%s: bad arguments", who); return 1; }
+    const long out_pix = regrid_checked(who, height, width, spec, nullptr);
+    if (out_pix < 0) return 1;
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(n_items, (size_t) out_pix * sizeof(float), &bytes) || __builtin_mul_overflow(n_items, height * width * sizeof(float), &bytes)) {
+        set_error("%s: the size of the items or of the output overflows", who);
+        return 1;
+    }
+    return on_device(ctx->device, 1, [&] {
+        regrid_upload(ctx, *spec, ebcc_hip_region{0, 0, height, width});
+        regrid_items(ctx, RegridItems{d_items, height * width, (unsigned) width, 0u, 0u}, n_items, width, *spec, d_out);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_regrid_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_regrid_spec *spec,
+                          float *d_out)
+{
+    EBCC_API_TRY
+    return regrid_shard("ebcc_hip_regrid_shard", ctx, streams, sizes, n_frames, spec, d_out, false);
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_regrid_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_regrid_spec *spec,
+                                float *h_out)
+{
+    EBCC_API_TRY
+    return regrid_shard("ebcc_hip_regrid_host_frames", ctx, streams, sizes, n_frames, spec, h_out, true);
     EBCC_API_CATCH(1)
 }
 

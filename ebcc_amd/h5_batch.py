@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import load
+from . import regrid as _regrid
 from .filter_wrapper import EBCC_Filter, _MODES
 
 
@@ -327,6 +328,11 @@ class BatchCodec:
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeStats)]
         lib.ebcc_hip_series_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.POINTER(AreaSpec), ctypes.c_void_p]
+        for name in ("ebcc_hip_regrid_shard", "ebcc_hip_regrid_host_frames"):
+            getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                           ctypes.POINTER(_regrid.RegridSpec), ctypes.c_void_p]
+        lib.ebcc_hip_regrid_check.restype = ctypes.c_long
+        lib.ebcc_hip_regrid_check.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_regrid.RegridSpec), ctypes.c_void_p]
         lib.ebcc_hip_last_error.restype = ctypes.c_char_p
         lib.free_buffer.argtypes = [ctypes.c_void_p]
         self.h, self.w, self.max_frames = int(height), int(width), int(max_frames)
@@ -442,6 +448,33 @@ class BatchCodec:
             return SeriesResult(area.run(streams), area.weight())
         finally:
             area.close()
+
+    def regrid(self, streams, row_map, col_map, out=None):
+        """The same fields on another grid straight from the streams (ebcc_hip_regrid_host_frames): row_map and col_map are
+        regrid.AxisMap objects - identity_map, flip_map, block_mean_map, conservative_map, linear_map or hand-made - and every
+        frame is resampled on the device by the rule include/ebcc_hip.h states -> (n, row_map.n_out, col_map.n_out) float32.
+        Only the bounding box of the supports is decoded and only the resampled frames cross PCIe.  `out`: a C-contiguous
+        float32 array to fill, or an integer - a 4-byte aligned device pointer with room for the result, which is then
+        written there (ebcc_hip_regrid_shard) and returned as given.  ValueError for a map the engine refuses (checked here,
+        before the call), RuntimeError for what the call reports, such as a malformed stream."""
+        n = len(streams)
+        if n < 1:
+            raise ValueError("no streams")
+        spec = _regrid.regrid_spec(row_map, col_map)
+        if self.lib.ebcc_hip_regrid_check(self.h, self.w, ctypes.byref(spec), None) < 0:
+            raise ValueError((self.lib.ebcc_hip_last_error() or b"?").decode())
+        streams, ptrs, sizes = _stream_arrays(streams)
+        if isinstance(out, (int, np.integer)):
+            if self.lib.ebcc_hip_regrid_shard(self.ctx, ptrs, sizes, n, ctypes.byref(spec), int(out)):
+                self._fail("ebcc_hip_regrid_shard")
+            return out
+        shape = (n, row_map.n_out, col_map.n_out)
+        if out is None:
+            out = np.empty(shape, np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == n * shape[1] * shape[2]
+        if self.lib.ebcc_hip_regrid_host_frames(self.ctx, ptrs, sizes, n, ctypes.byref(spec), out.ctypes.data):
+            self._fail("ebcc_hip_regrid_host_frames")
+        return out
 
     def encode_groups(self, groups, hard=False, max_rounds=0):
         """Many variables in one device call: `groups` is a list of (frames, base_cr, residual_opt[, range_of_group]) - frames
@@ -935,6 +968,47 @@ def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=
                 if t:
                     t.join()
         return SeriesResult(np.concatenate(parts), area.weight())
+
+
+def read_regridded(dset, row_map, col_map, frames=None, batch=256, codec=None):
+    """The frames of an EBCC-filtered one-frame-per-chunk dataset on another grid (BatchCodec.regrid): `frames` names the frames
+    - counted in C order over the leading axes, in any order; None: all of them -, row_map and col_map are regrid.AxisMap
+    objects -> (len(frames), row_map.n_out, col_map.n_out) float32, frame k equal to the rule of include/ebcc_hip.h applied to
+    read_frames(dset) at frame k.  No decoded frame is downloaded.  The chunks are fetched as series_frames fetches them, the
+    next call's on a helper thread."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    named = np.arange(n) if frames is None else np.asarray(frames)
+    if named.ndim != 1 or len(named) < 1 or named.dtype.kind not in "iu" or named.min() < 0 or named.max() >= n:
+        raise ValueError(f"frames must be a non-empty list of integers in [0, {n})")
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
+        step = _SUPER * codec.max_frames
+
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, named[lo:lo + step]))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
+
+        out = np.empty((len(named), row_map.n_out, col_map.n_out), np.float32)
+        box = []
+        fetch(0, box)
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                codec.regrid(raw, row_map, col_map, out=out[lo:lo + len(raw)])
+            finally:
+                if t:
+                    t.join()
+        return out
 
 
 def read_boxes(dset, boxes, rows, cols, batch=256, codec=None):

@@ -610,6 +610,64 @@ int ebcc_hip_area_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, 
 int ebcc_hip_series_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const ebcc_hip_area_spec *spec,
                           ebcc_hip_area_stat *out);
 
+/* ---- regrid decode: the same fields on another grid, from the streams, on the device --------
+ * The fourth question an archive is asked: 0.25 degree fields conservatively coarsened to 1 degree, k x k block means for an
+ * overview, a north-south flip, a sub-sampled or bilinearly interpolated target grid, a centred difference along an axis.
+ * Streams go in, n_frames x n_out_rows x n_out_cols floats come out; the bounding box of the supports is decoded (only the
+ * code-blocks it needs) batch by batch into a buffer of the engine set and resampled there.  No decoded frame reaches the
+ * caller.  The reference has no counterpart.
+ * A regrid is a separable linear map with a contiguous support per output position along each axis (ebcc_hip_axis_map).
+ * The order is the contract.  For output (R, C) of a frame with decoded float samples x, wr[R][i] and wc[C][j] the packed
+ * weights of the row and the column map:
+ *   a = +0.0
+ *   for i = 0 .. rows.count[R), in increasing i:   r = rows.first[R] + i
+ *       t = +0.0;  for j = 0 .. cols.count[C), in increasing j:   t = t + (double) x[r][col(C, j)] * wc[C][j]
+ *       a = a + wr[R][i] * t
+ *   out[R][C] = (float) a        (round to nearest even; products and sums are never contracted)
+ *   col(C, j) = cols.first[C] + j, and (cols.first[C] + j) % width when cols.wrap is set.
+ * t depends on (r, C) alone: a two-pass separable form and a fused form that recomputes t where row supports overlap give the
+ * same bits (ebcc_amd/csrc/regrid.hip: k_regrid is the fused form).  Weights are used as given: the library does not normalise
+ * them.  Every tap takes part - there is no special case for a weight of 0: a term of +-0 never changes an accumulator, since
+ * one that starts at +0.0 never becomes -0.0 (so a restatement may pad every support to the longest with weights of 0).  A
+ * result depends on the map and on the samples inside its support, and on nothing else - not on the batch size, the slices, the
+ * engine sets, the alignment of any array, or whether the frame was decoded whole or as a window.  No atomics, no LDS.
+ * Not covered: chunks of several frames, EBCK containers, the reference-compatible entry points and the filter callback, maps
+ * that are not separable. */
+#define EBCC_HIP_REGRID_MAX_TAPS 256
+typedef struct {
+    size_t          n_out;    /* output positions along the axis, 1 .. 65535 */
+    const uint32_t *first;    /* host [n_out]: first source index of output i's support (any order: a flip is a map) */
+    const uint32_t *count;    /* host [n_out]: taps of output i, 1 .. EBCC_HIP_REGRID_MAX_TAPS */
+    const double   *weight;   /* host, packed: the weights of output 0, then of output 1, ...; finite, any sign */
+    int             wrap;     /* columns only: tap j reads source index (first + j) % width (a cell across the date line) */
+} ebcc_hip_axis_map;
+typedef struct { ebcc_hip_axis_map rows, cols; } ebcc_hip_regrid_spec;
+/* Host only, no device: n_out_rows * n_out_cols and (bounding, may be NULL) the box of the frame the map reads - the whole
+ * width when a column support wraps -, or -1 with a message and `bounding` untouched for what the calls below refuse before
+ * touching a device: a null spec or table, n_out of 0 or above 65535, a count of 0 or above EBCC_HIP_REGRID_MAX_TAPS, a
+ * first >= the extent, a support that leaves the axis (without wrap), wrap set on the row map, a NaN or Inf weight, a geometry
+ * ebcc_hip_create refuses, an output size that overflows. */
+long ebcc_hip_regrid_check(size_t height, size_t width, const ebcc_hip_regrid_spec *spec, ebcc_hip_region *bounding);
+/* unit level, the kernel alone: d_items [n_items][height][width] -> d_out [n_items][n_out_rows][n_out_cols], both on the
+ * device at any 4-byte alignment.  The items are never written.  ctx: any context of the device.  0 = ok, 1 = error with
+ * nothing written: what the check refuses, null or misaligned pointers, n_items == 0. */
+int ebcc_hip_regrid_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, size_t height, size_t width,
+                          const ebcc_hip_regrid_spec *spec, float *d_out);
+/* Any number of one-frame streams: the bounding box of the supports is decoded - by the window decode, by the full decode
+ * when it is the frame - in batches of the context's capacity on the two engine sets, each into its set's audit buffer (a
+ * context runs one call at a time), and every batch is resampled there into its own frames of d_out (device,
+ * [n_frames][n_out_rows][n_out_cols], any 4-byte alignment): batches take no turns.  Return 0 = ok, 1 = error
+ * (ebcc_hip_last_error).  Refused before anything is written: what the check refuses for the context's frames, null or
+ * misaligned pointers, n_frames == 0, a context for chunks of several frames, a frame without a stream or with one whose frame
+ * header does not parse.  A stream found damaged inside a batch (and so every stream, in a context of another geometry) is
+ * refused as ebcc_hip_decode_frames refuses it: the output is then unspecified within its bounds, and nothing outside it is
+ * written. */
+int ebcc_hip_regrid_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                          const ebcc_hip_regrid_spec *spec, float *d_out);
+/* The same into pageable host memory: only n_out_rows * n_out_cols floats a frame cross PCIe. */
+int ebcc_hip_regrid_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
+                                const ebcc_hip_regrid_spec *spec, float *h_out);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -649,7 +707,7 @@ int ebcc_hip_selfcheck(void);
 void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4]);
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
- * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold".  Process-wide switch. */
+ * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
