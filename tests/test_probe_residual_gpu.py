@@ -53,6 +53,11 @@ def input_names(h, w):
     return ["base", "noise", "checker"] + [f"spike-{k}" for k in spike_places(h, w)]
 
 
+def designed_budget(h, w):
+    """the SPIHT budget in bits of the designed residuals (also tests/test_geometry_sweep_gpu.py)"""
+    return 8 * min(1600, max(200, (h * w) // 5))
+
+
 @functools.lru_cache(maxsize=None)
 def make_input(h, w, name):
     """(x, d, budget in bits)"""
@@ -68,7 +73,7 @@ def make_input(h, w, name):
         r = (L.smooth_image(h, w, 5) * np.float32(0.01)).astype(np.float32)
         r[spike_places(h, w)[name[len("spike-"):]]] = 1.0
     d = (x - r).astype(np.float32)
-    return x, d, 8 * min(1600, max(200, (h * w) // 5))
+    return x, d, designed_budget(h, w)
 
 
 @functools.lru_cache(maxsize=None)
