@@ -476,7 +476,7 @@ void ebcc_hip_destroy(ebcc_hip_ctx *ctx)
     if (ctx->h_stage) hipHostFree(ctx->h_stage);
     if (ctx->d_stage) hipFree(ctx->d_stage);
     if (ctx->h_bounce) hipHostFree(ctx->h_bounce);
-    for (DeviceBuffer *b : {&ctx->io, &ctx->boxes, &ctx->audit, &ctx->offenders, &ctx->errs}) b->release();
+    for (DeviceBuffer *b : {&ctx->io, &ctx->boxes, &ctx->audit, &ctx->offenders, &ctx->errs, &ctx->ranks}) b->release();
     if (ctx->ev_a) hipEventDestroy(ctx->ev_a);
     if (ctx->ev_b) hipEventDestroy(ctx->ev_b);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);

@@ -69,6 +69,9 @@ struct ebcc_hip_ctx {
     // (item, bin) list in `boxes`; so does the area series, whose row weights and region table lie in `boxes` and whose records
     // (per row of a region, then per region) lie in `errs`.
     ebcc::DeviceBuffer audit, offenders, errs;
+    // Quantile decode (quantile.hip): the counters, prefixes and remaining ranks of a call's radix select, made on first use and
+    // freed with the engine set.  A call sets them anew before its first pass; both engine sets count into the primary context's.
+    ebcc::DeviceBuffer ranks;
     ebcc::CutSlots cut{};                 // look-ahead storage of the truncation search (made on first use: ensure_cut_slots)
     bool cut_failed = false;                // (no memory for it: the search probes one cut per round)
 };

@@ -8,6 +8,7 @@
 #include <climits>
 #include "array_stats.hpp"
 #include "regrid.hpp"
+#include "quantile.hpp"
 
 using namespace ebcc;
 
@@ -1006,7 +1007,9 @@ struct BoxCall {
 // The decode entry points: `region` as the caller states it, and the checks in their order - bad batch (`one_batch`, the _frames
 // forms: at most the context's capacity of frames), bad arguments, a window or a list that does not fit the context's frames
 // (nothing is written for one that is refused) - then run(region, streams, sizes, n) in the device prologue.
-// (decode_region: the checks of the region alone, which also turn a list into its BoxCall - for a caller that holds the device)
+// (decode_region: the checks of the region alone, which also turn a list into its BoxCall - for a caller that holds the device;
+// decode_call with `held`: the caller holds the device's lock and has made the device current - run() runs where it stands, and
+// what it throws is the caller's prologue's to catch)
 int decode_region(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *&streams, const size_t *&sizes, size_t &n_frames, DecodeRegion &region,
                   BoxCall &call)
 {
@@ -1032,12 +1035,13 @@ int decode_region(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *&str
 }
 template <class Run>
 int decode_call(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const void *out,
-                DecodeRegion region, bool one_batch, Run &&run)
+                DecodeRegion region, bool one_batch, Run &&run, bool held = false)
 {
     if (one_batch && (!ctx || n_frames < 1 || n_frames > ctx->max_frames)) { set_error("%s: bad batch", who); return 1; }
     if (!ctx || !streams || !sizes || !out || n_frames < 1) { set_error("%s: bad arguments", who); return 1; }
     BoxCall call;
     if (decode_region(who, ctx, streams, sizes, n_frames, region, call)) return 1;
+    if (held) return run(region, streams, sizes, n_frames);
     return on_codec(ctx->device, 1, [&] { return run(region, streams, sizes, n_frames); });
 }
 // device output: batches of the context's capacity on the two sets side by side, each as its slices
@@ -1077,7 +1081,7 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
-// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode).  What one asks the driver for, its own arguments checked:
+// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode).  What one asks the driver for, its own arguments checked:
 struct DecodedAsk {
     const uint8_t *const *streams = nullptr;
     const size_t *sizes = nullptr, *names = nullptr;   // names[i]: the number stream i has in the caller's list, for a message (null: i)
@@ -1092,8 +1096,9 @@ struct DecodedAsk {
 // set), the pre-parse, decode_call's checks and device prologue, then the batches of the context's capacity on the two sets
 // (decode_batches), each decoded into its set's audit buffer and handed to per_batch(set, decoded, first stream, count, timer) -
 // free-running, or `ordered`: in batch order and only while nothing has failed.  one_batch: at most the context's capacity.
+// held: the caller is inside on_codec for the context's device (a consumer of several passes keeps the lock over all of them).
 template <class Ask, class PerBatch>
-int consume_decoded(const char *who, ebcc_hip_ctx *ctx, bool one_batch, bool ordered, Ask ask, PerBatch per_batch)
+int consume_decoded(const char *who, ebcc_hip_ctx *ctx, bool one_batch, bool ordered, Ask ask, PerBatch per_batch, bool held = false)
 {
     if (!ctx) { set_error(one_batch ? "%s: bad batch" : "%s: bad arguments", who); return 1; }
     if (ctx->tile_period != 1) { set_error("%s: the context is one for chunks of several frames", who); return 1; }
@@ -1122,7 +1127,7 @@ int consume_decoded(const char *who, ebcc_hip_ctx *ctx, bool one_batch, bool ord
             hand(set, lo, k);
             return 0;
         });
-    });
+    }, held);
 }
 
 // ---- audit: the error of what the streams decode to, against the originals, measured on the device
@@ -1246,6 +1251,52 @@ int regrid_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
         regrid_items(set, RegridItems{decoded, bb.rows * bb.cols, (unsigned) bb.cols, (unsigned) bb.row0, (unsigned) bb.col0}, k, (size_t) ctx->width, *spec, d);
         if (host) copy_pageable(set, out + lo * out_pix, d, k * out_pix * sizeof(float), true);
         pt.mark("regrid: map");
+    });
+}
+
+// ---- quantile decode: order statistics over time per pixel (include/ebcc_hip.h: ebcc_hip_time_ranks; k_rank_count, quantile.hip)
+// A radix select over the series: kRankPasses passes, each one ordered consume_decoded call over the frames that are read - the
+// counters are shared between the batches, which count in their turns - and after each the advance on the calling thread.  The
+// state of the select lives in the context (ctx->ranks) from the first pass to the last, so the device's lock is taken once and
+// held over all of them (consume_decoded's `held`): calls of several threads on one context run one after the other, as every
+// other entry point's do.  The check, the compaction and the parse belong to the first pass, which also sets the workspace;
+// d_out and count are written after the last pass, so a refusal or a damaged stream in any pass leaves both untouched.  A frame
+// whose bin has no slot in use is counted and not read.
+int quantile_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                   size_t row0, size_t col0, const ebcc_hip_time_ranks *spec)
+{
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz, names;
+    std::vector<uint32_t> bn;
+    RankPlan plan;
+    return on_codec(ctx->device, 1, [&] {
+        for (int pass = 0; pass < kRankPasses; pass++) {
+            const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
+                if (pass == 0) {
+                    if (time_ranks_named(who, (size_t) ctx->height, (size_t) ctx->width, spec, bin, n_frames, row0, col0, &plan) < 0) return false;
+                    if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
+                    for (size_t f = 0; f < n_frames; f++) {
+                        const uint32_t b = bin ? bin[f] : 0u;
+                        if (b == EBCC_HIP_NO_BIN || !plan.mask[b]) continue;
+                        st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b); names.push_back(f);
+                    }
+                    a.parsed_first = true;
+                    a.ready = [&] { rank_begin(ctx, plan); return true; };
+                }
+                a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = spec;
+                a.box = ebcc_hip_region{row0, col0, spec->rows, spec->cols};
+                a.decode_mark = "quantile: decode";
+                return true;
+            }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
+                rank_count(set, plan, decoded, k, bn.data() + lo, pass);
+                pt.mark("quantile: count");
+            }, true);
+            if (rc) return rc;
+            rank_advance(ctx, plan, pass, spec->d_out);
+        }
+        std::copy(plan.count.begin(), plan.count.end(), spec->count);
+        return 0;
     });
 }
 
@@ -2100,6 +2151,41 @@ int ebcc_hip_regrid_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams
 {
     EBCC_API_TRY
     return regrid_shard("ebcc_hip_regrid_host_frames", ctx, streams, sizes, n_frames, spec, h_out, true);
+    EBCC_API_CATCH(1)
+}
+
+// ---- quantile decode (quantile_shard above): order statistics over time, selected on the device
+long ebcc_hip_time_ranks_check(size_t height, size_t width, const ebcc_hip_time_ranks *spec, const uint32_t *bin, size_t n_frames, size_t row0,
+                               size_t col0)
+{
+    EBCC_API_TRY
+    return time_ranks_named("ebcc_hip_time_ranks_check", height, width, spec, bin, n_frames, row0, col0);
+    EBCC_API_CATCH(-1)
+}
+size_t ebcc_hip_time_ranks_work_bytes(const ebcc_hip_time_ranks *spec) { return time_ranks_work_bytes(spec); }
+int ebcc_hip_rank_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const ebcc_hip_time_ranks *spec)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_rank_items";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
+    RankPlan plan;
+    if (time_ranks_named(who, spec ? spec->rows : 0, spec ? spec->cols : 0, spec, bin, n_items, 0, 0, &plan) < 0) return 1;
+    return on_device(ctx->device, 1, [&] {
+        rank_begin(ctx, plan);
+        for (int pass = 0; pass < kRankPasses; pass++) {
+            rank_count(ctx, plan, d_items, n_items, bin, pass);
+            rank_advance(ctx, plan, pass, spec->d_out);
+        }
+        std::copy(plan.count.begin(), plan.count.end(), spec->count);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_quantile_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin, size_t row0,
+                            size_t col0, const ebcc_hip_time_ranks *spec)
+{
+    EBCC_API_TRY
+    return quantile_shard("ebcc_hip_quantile_shard", ctx, streams, sizes, n_frames, bin, row0, col0, spec);
     EBCC_API_CATCH(1)
 }
 

@@ -139,6 +139,50 @@ class ReduceState:
         self.close()
 
 
+class TimeRanks(ctypes.Structure):
+    """ebcc_hip_time_ranks, include/ebcc_hip.h: the order statistics asked of every bin (host) and their planes
+    [n_bins][n_ranks][rows][cols] (device), count on the host."""
+    _fields_ = [("n_bins", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t), ("n_ranks", ctypes.c_size_t),
+                ("rank", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
+NO_RANK = 2 ** 64 - 1                                             # EBCC_HIP_NO_RANK
+MAX_RANKS = 16                                                    # EBCC_HIP_MAX_RANKS
+QUANTILE_METHODS = ("linear", "lower", "higher", "nearest")
+
+
+def quantile_rule(q, m, method="linear"):
+    """The rank rule of BatchCodec.quantiles for a bin of m >= 1 frames, in float64: h = q * (m - 1) -> (lo, hi, t), the
+    quantile being lo_value + (hi_value - lo_value) * t of the order statistics at the 0-based ranks lo and hi.  `lower`:
+    floor(h); `higher`: ceil(h); `nearest`: h rounded half to even; `linear`: floor(h), ceil(h) and t = h - floor(h).  All but
+    `linear` give lo == hi and t == 0."""
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f"method must be one of {QUANTILE_METHODS}, got {method!r}")
+    q = np.float64(q)
+    if not (q >= 0.0 and q <= 1.0):
+        raise ValueError(f"a quantile must lie in [0, 1], got {q}")
+    if m < 1:
+        raise ValueError("a bin without frames has no quantile")
+    h = q * np.float64(m - 1)
+    fl, ce = int(np.floor(h)), int(np.ceil(h))
+    if method == "lower":
+        return fl, fl, np.float64(0.0)
+    if method == "higher":
+        return ce, ce, np.float64(0.0)
+    if method == "nearest":
+        r = int(np.rint(h))
+        return r, r, np.float64(0.0)
+    return fl, ce, h - np.floor(h)
+
+
+class QuantileResult:
+    """Quantiles over time, per bin and pixel: values (n_bins, len(q), rows, cols) float32 and count (n_bins,) uint64 - the
+    frames of each bin.  A bin without frames gives NaN planes."""
+
+    def __init__(self, values, count):
+        self.values, self.count = values, count
+
+
 class Region(ctypes.Structure):
     """ebcc_hip_region, include/ebcc_hip.h: a box of a frame"""
     _fields_ = [("row0", ctypes.c_size_t), ("col0", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t)]
@@ -328,6 +372,8 @@ class BatchCodec:
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeStats)]
         lib.ebcc_hip_series_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.POINTER(AreaSpec), ctypes.c_void_p]
+        lib.ebcc_hip_quantile_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeRanks)]
         for name in ("ebcc_hip_regrid_shard", "ebcc_hip_regrid_host_frames"):
             getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                            ctypes.POINTER(_regrid.RegridSpec), ctypes.c_void_p]
@@ -435,6 +481,72 @@ class BatchCodec:
         finally:
             if own:
                 state.close()
+
+    def quantiles(self, streams, q, bins=None, n_bins=1, window=None, method="linear"):
+        """Quantiles over time straight from the streams (ebcc_hip_quantile_shard): for every bin - `bins` as in reduce: an
+        integer per stream, None: all bin 0, -1: the frame is skipped and not read - and every q of the sequence `q` (each in
+        [0, 1]) the quantile at every pixel of the frame or of its `window` = (row0, col0, rows, cols) -> a QuantileResult.
+        The device selects order statistics - samples that occur, by a radix select over eight decodes of the series, with
+        -0 as +0 and NaN last -; the rank rule runs here in float64 (quantile_rule): for a bin of m frames h = q (m - 1), and
+        `lower`, `higher`, `nearest` (half to even) return the order statistic at that rank, `linear` float32(lo + (hi - lo)
+        (h - floor(h))) computed in float64 from the two around h (the order statistic itself where h is whole).  The distinct
+        ranks a bin needs go to the device once, at most 16 per call: ValueError with the number above that, and for a q
+        outside [0, 1], an unknown method or bins the engine refuses; RuntimeError for what the call reports."""
+        n = len(streams)
+        qs = np.atleast_1d(np.asarray(q, np.float64))
+        if qs.ndim != 1 or qs.size < 1:
+            raise ValueError("q must be a number or a non-empty sequence of numbers")
+        if method not in QUANTILE_METHODS:
+            raise ValueError(f"method must be one of {QUANTILE_METHODS}, got {method!r}")
+        if not ((qs >= 0.0) & (qs <= 1.0)).all():
+            raise ValueError(f"every quantile must lie in [0, 1], got {qs.tolist()}")
+        n_bins = int(n_bins)
+        row0, col0, rows, cols = (0, 0, self.h, self.w) if window is None else tuple(int(v) for v in window)
+        if n_bins < 1 or min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > self.h or col0 + cols > self.w:
+            raise ValueError(f"n_bins {n_bins} or window {(row0, col0, rows, cols)} does not fit the {self.h} x {self.w} frame")
+        b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+        if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
+            raise ValueError(f"bins must be {n} integers, one per stream")
+        b = b.astype(np.int64)
+        if b.min() < -1 or b.max() >= n_bins:
+            raise ValueError(f"bins must lie in [-1, {n_bins})")
+        if not (b >= 0).any():
+            raise ValueError("no frame is named")
+        m = np.bincount(b[b >= 0], minlength=n_bins)
+        rules = [[quantile_rule(v, int(m[k]), method) for v in qs] if m[k] else None for k in range(n_bins)]
+        slots = [sorted({r for lo, hi, _ in rule for r in (lo, hi)}) if rule else [] for rule in rules]
+        n_ranks = max(len(s) for s in slots)
+        if n_ranks > MAX_RANKS:
+            raise ValueError(f"a bin needs {n_ranks} distinct ranks, more than the {MAX_RANKS} of one call")
+        rank = np.full((n_bins, n_ranks), NO_RANK, np.uint64)
+        for k, s in enumerate(slots):
+            rank[k, :len(s)] = s
+        count = np.zeros(n_bins, np.uint64)
+        planes = np.empty((n_bins, n_ranks, rows, cols), np.float32)
+        table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+        streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.nonzero(b >= 0)[0]))
+        d_out = self.lib.ebcc_hip_malloc(planes.nbytes)
+        if not d_out:
+            self._fail("ebcc_hip_malloc")
+        try:
+            spec = TimeRanks(n_bins, rows, cols, n_ranks, rank.ctypes.data, d_out, count.ctypes.data)
+            if self.lib.ebcc_hip_quantile_shard(self.ctx, ptrs, sizes, n, table.ctypes.data, row0, col0, ctypes.byref(spec)):
+                self._fail("ebcc_hip_quantile_shard")
+            if self.lib.ebcc_hip_memcpy_d2h(planes.ctypes.data, d_out, planes.nbytes):
+                self._fail("ebcc_hip_memcpy_d2h")
+        finally:
+            self.lib.ebcc_hip_free(d_out)
+        values = np.full((n_bins, len(qs), rows, cols), np.nan, np.float32)
+        for k, rule in enumerate(rules):
+            for i, (lo, hi, t) in enumerate(rule or ()):
+                low = planes[k, slots[k].index(lo)]
+                if hi == lo:
+                    values[k, i] = low
+                else:
+                    low64, high64 = low.astype(np.float64), planes[k, slots[k].index(hi)].astype(np.float64)
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        values[k, i] = (low64 + (high64 - low64) * t).astype(np.float32)
+        return QuantileResult(values, count)
 
     def series(self, streams, regions, w_row=None, w_pix=None, threshold=None):
         """Statistics over regions at every time step straight from the streams (ebcc_hip_series_shard): `regions` is an int
@@ -925,6 +1037,32 @@ def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=
                 if t:
                     t.join()
         return state.result()
+
+
+def quantile_frames(dset, q, bins=None, n_bins=None, rows=None, cols=None, method="linear", batch=256, codec=None):
+    """Quantiles over time of an EBCC-filtered one-frame-per-chunk dataset, selected on the device (BatchCodec.quantiles): `q`
+    a number or a sequence of numbers in [0, 1], `bins`, n_bins, `rows` / `cols` as in reduce_frames (a month per frame gives
+    a percentile climatology), `method` as in BatchCodec.quantiles -> a QuantileResult whose values (n_bins, len(q), rows,
+    cols) are those quantiles of read_frames(dset)[..., rows, cols] over the frames of each bin; no frame is downloaded.  The
+    chunks of the named frames are fetched once - the eight passes of the select run over the streams in host memory, which
+    therefore must hold them (not the decoded frames)."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
+        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
+    b = b.astype(np.int64).reshape(-1)
+    named = np.nonzero(b >= 0)[0]
+    if len(named) < 1 or b.min() < -1:
+        raise ValueError("bins must name at least one frame, and -1 is the only negative value")
+    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
+    if b.max() >= n_bins:
+        raise ValueError(f"a frame names bin {int(b.max())} of {n_bins}")
+    with held_codec(h, w, min(batch, len(named)), codec=codec) as codec:
+        raw = _read_chunks(dset, named)
+        return codec.quantiles(raw, q, bins=b[named], n_bins=n_bins, window=(row0, col0, nrows, ncols), method=method)
 
 
 def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=None, batch=256, codec=None):

@@ -18,7 +18,8 @@
  * where base and frame size allow them, and a decode output on a 256-byte boundary is written directly instead of through
  * one device-to-device copy of the batch.  (tests/test_caller_buffers_gpu.py)
  *
- * Threads: every entry point that codes, decodes, audits, reduces or folds on a context - and ebcc_hip_upload, _download,
+ * Threads: every entry point that codes, decodes, audits, reduces, folds or selects on a context (ebcc_hip_quantile_shard and
+ * ebcc_hip_rank_items among them: each holds the lock from its first pass to its last) - and ebcc_hip_upload, _download,
  * _prepare and _release_second_set - takes the lock of the context's device for the call, as the entry points of
  * include/ebcc_codec.h do for the engines they cache per (device, frame geometry); ebcc_hip_release_engines takes it device by
  * device.  Calls on one device run one after the other, so threads may share a context, each with buffers of its own; calls on
@@ -668,6 +669,63 @@ int ebcc_hip_regrid_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, cons
 int ebcc_hip_regrid_host_frames(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames,
                                 const ebcc_hip_regrid_spec *spec, float *h_out);
 
+/* ---- quantile decode: order statistics over time per pixel, from the streams, on the device --------
+ * The fifth question an archive is asked: how the values at a pixel are distributed over time - the median, the 5th, 90th or
+ * 95th percentile per calendar month (the thresholds of TX90p / R95p style indices), an ensemble's quartiles, a return level.
+ * Sums, extremes and one exceedance count (the reduce decode) cannot give a percentile, and a full decode of a multi-decade
+ * series does not fit a device.  Streams go in, for every bin and rank slot one plane [rows][cols] comes out; no decoded frame
+ * reaches the caller.  The reference has no counterpart.
+ * The rule is integers' work, so no order rule is needed.  For a bin b take the m frames f with bin[f] == b.  A sample x (float)
+ * has the order-preserving key of x + 0.0f:
+ *   u = bits(x + 0.0f);  key = (u >> 31) ? ~u : u ^ 0x80000000;  every NaN, whatever its sign and payload: key = 0xFFFFFFFF.
+ * So -0 counts as +0, and the order is -inf < negative < 0 < positive < +inf < NaN (that of a sort that puts NaN last).  For
+ * a pixel and a rank r (0-based, r < m) the result is the float whose key is the r-th smallest of the m keys, written as that
+ * float, +0.0f for a zero and 0x7FC00000 for a NaN: a sample that occurs at the pixel, the canonical zero and NaN aside.
+ * Nothing is interpolated here (ebcc_amd/h5_batch.py: BatchCodec.quantiles makes quantiles of the order statistics).
+ * The selection is a radix select on the key, most significant digit first, digits of 4 bits: eight passes over the series.
+ * In pass s, shift = 28 - 4 s: a sample of bin b counts for slot j if key >> (shift + 4) == prefix[b][j][p] (every sample in
+ * pass 0) and adds 1 to hist[b][j][(key >> shift) & 15][p]; then, per (bin, slot, pixel), the first digit d whose running total
+ * over the 16 counters exceeds rem is taken: rem -= (total before d), prefix = prefix << 4 | d, counters = 0.  After pass 7
+ * prefix is the key.  No atomics (ebcc_amd/csrc/quantile.hip: k_rank_count, k_rank_advance).  The workspace - (16 + 2) * 4
+ * bytes per (bin, slot, pixel) - is the context's, grown on demand, set anew by every call and freed with the context.
+ * Not covered: a series split over several calls, chunks of several frames, a host-pointer output, EBCK containers, weighted
+ * quantiles, quantiles over an area, the reference-compatible entry points and the filter callback. */
+#define EBCC_HIP_NO_RANK SIZE_MAX
+#define EBCC_HIP_MAX_RANKS 16
+typedef struct {
+    size_t n_bins, rows, cols, n_ranks;   /* n_ranks: 1 .. EBCC_HIP_MAX_RANKS slots per bin */
+    const size_t *rank;                   /* host [n_bins][n_ranks]: 0-based order statistic among the bin's frames; EBCC_HIP_NO_RANK: slot unused */
+    float    *d_out;                      /* device [n_bins][n_ranks][rows][cols], 4-byte aligned; an unused slot's plane is never written */
+    uint64_t *count;                      /* host [n_bins], written by a call that succeeds: frames of each bin */
+} ebcc_hip_time_ranks;
+/* Host only, no device: the number of frames `bin` names (bin: host [n_frames], NULL = every frame in bin 0, EBCC_HIP_NO_BIN =
+ * the frame is skipped), or -1 with a message for what the calls below refuse before touching a device: a null spec, rank,
+ * d_out or count, n_bins, rows or cols zero, n_ranks of 0 or above EBCC_HIP_MAX_RANKS, a d_out that is not 4-byte aligned, sizes
+ * that overflow, a geometry ebcc_hip_create refuses, a window [row0, row0 + rows) x [col0, col0 + cols) not inside the height x
+ * width frame, a bin >= n_bins, no frame named, a bin with 2^32 frames or more, a rank >= the number of frames its bin is given,
+ * every slot unused.  A bin without frames is legal if all its slots are unused. */
+long ebcc_hip_time_ranks_check(size_t height, size_t width, const ebcc_hip_time_ranks *spec, const uint32_t *bin, size_t n_frames,
+                               size_t row0, size_t col0);
+/* Host only: the bytes of workspace a call with this spec needs in its context, n_bins * n_ranks * rows * cols * 72; 0 =
+ * overflow or a bad spec. */
+size_t ebcc_hip_time_ranks_work_bytes(const ebcc_hip_time_ranks *spec);
+/* unit level, the kernels alone: all eight passes over d_items [n_items][rows][cols] at any 4-byte aligned device address; an
+ * item with EBCC_HIP_NO_BIN is not read.  The items are never written.  ctx: any context of the device.  0 = ok, 1 = error with
+ * nothing written: what the check refuses, null or misaligned items, no memory for the workspace. */
+int ebcc_hip_rank_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const ebcc_hip_time_ranks *spec);
+/* Any number of one-frame streams.  Every pass decodes the frames `bin` names - the window [row0, row0 + spec->rows) x [col0,
+ * col0 + spec->cols) by the window decode, the whole frame by the full decode when the window is the frame - in batches of the
+ * context's capacity on the two engine sets, each into its set's audit buffer, and counts
+ * them there (the call holds the device's lock over all eight passes: a context runs one call at a time): the decodes of two batches run side by side, the counts take turns in batch order and share the counters of the
+ * primary context.  A frame with EBCC_HIP_NO_BIN is not read at all: its streams[f] may be NULL with size 0; a frame of a bin
+ * whose slots are all unused is counted and not read either.  d_out and count
+ * are written once, after the last pass.  Return 0 = ok, 1 = error (ebcc_hip_last_error) with nothing written: what the check
+ * refuses for the context's frames, a context for chunks of several frames, a named frame without a stream or with one whose
+ * frame header does not parse, no memory for the workspace, a stream found damaged inside a batch of any pass (refused as
+ * ebcc_hip_decode_frames refuses it; so every stream in a context of another geometry). */
+int ebcc_hip_quantile_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                            size_t row0, size_t col0, const ebcc_hip_time_ranks *spec);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -707,7 +765,8 @@ int ebcc_hip_selfcheck(void);
 void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4]);
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
- * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid".  Process-wide switch. */
+ * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid", "rank_count",
+ * "rank_advance".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
