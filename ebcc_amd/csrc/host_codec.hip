@@ -9,6 +9,7 @@
 #include "array_stats.hpp"
 #include "regrid.hpp"
 #include "quantile.hpp"
+#include "time_map.hpp"
 
 using namespace ebcc;
 
@@ -1081,7 +1082,7 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
-// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode).  What one asks the driver for, its own arguments checked:
+// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode, time-map decode).  What one asks the driver for, its own arguments checked:
 struct DecodedAsk {
     const uint8_t *const *streams = nullptr;
     const size_t *sizes = nullptr, *names = nullptr;   // names[i]: the number stream i has in the caller's list, for a message (null: i)
@@ -1298,6 +1299,37 @@ int quantile_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *str
         std::copy(plan.count.begin(), plan.count.end(), spec->count);
         return 0;
     });
+}
+
+// ---- time-map decode: weighted sums over time per pixel (include/ebcc_hip.h: ebcc_hip_time_map; k_time_map, time_map.hip)
+// Built as reduce_shard is: the frames some term names are the call the decode sees, and the fold is ordered - an output's
+// additions are in frame order.  slot[f]: the place frame f has among the named ones; a batch is the frames names[lo] ..
+// names[lo + k - 1] and folds the terms whose frame lies among them.
+int project_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                  const ebcc_hip_time_map *map)
+{
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz, names;
+    std::vector<uint32_t> named, slot;
+    const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
+        if (time_map_named(who, (size_t) ctx->height, (size_t) ctx->width, map, n_frames, row0, col0, &named) < 0) return false;
+        if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
+        slot.assign((size_t) named.back() + 1, 0u);
+        for (const uint32_t f : named) {
+            slot[f] = (uint32_t) st.size();
+            st.push_back(streams[f]); sz.push_back(sizes[f]); names.push_back(f);
+        }
+        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = map;
+        a.box = ebcc_hip_region{row0, col0, map->rows, map->cols};
+        a.parsed_first = true;
+        a.decode_mark = "project: decode";
+        return true;
+    }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
+        time_map(set, decoded, map->rows * map->cols, *map, names[lo], names[lo + k - 1] + 1, slot.data(), lo);
+        pt.mark("project: fold");
+    });
+    if (!rc) for (size_t o = 0; o < map->n_out; o++) map->count[o] += map->start[o + 1] - map->start[o];
+    return rc;
 }
 
 // ---- EBCK chunk container (the reference's src/ebcc_codec.c:920-1052, :1322-1449) --------------------------------------------------
@@ -2186,6 +2218,51 @@ int ebcc_hip_quantile_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, co
 {
     EBCC_API_TRY
     return quantile_shard("ebcc_hip_quantile_shard", ctx, streams, sizes, n_frames, bin, row0, col0, spec);
+    EBCC_API_CATCH(1)
+}
+
+// ---- time-map decode (project_shard above): weighted sums over time, folded on the device
+long ebcc_hip_time_map_check(size_t height, size_t width, const ebcc_hip_time_map *map, size_t n_frames, size_t row0, size_t col0)
+{
+    EBCC_API_TRY
+    return time_map_named("ebcc_hip_time_map_check", height, width, map, n_frames, row0, col0);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_time_map_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_map *map)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_time_map_init";
+    size_t bytes = 0;
+    if (!ctx || !map || !map->d_acc || !map->count || ((uintptr_t) map->d_acc & 7)) { set_error("%s: bad arguments", who); return 1; }
+    if (map->n_out < 1 || map->rows < 1 || map->cols < 1) { set_error("%s: n_out, rows and cols must not be zero", who); return 1; }
+    if (__builtin_mul_overflow(map->rows, map->cols, &bytes) || __builtin_mul_overflow(bytes, map->n_out, &bytes) ||
+        __builtin_mul_overflow(bytes, sizeof(double), &bytes)) { set_error("%s: the size of the accumulators overflows", who); return 1; }
+    return on_device(ctx->device, 1, [&] {
+        EBCC_HIP_CHECK(hipMemsetAsync(map->d_acc, 0, bytes, ctx->stream));
+        wait_stream(ctx->stream);
+        std::fill_n(map->count, map->n_out, (uint64_t) 0);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_time_map_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const ebcc_hip_time_map *map)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_time_map_items";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
+    if (time_map_named(who, map ? map->rows : 0, map ? map->cols : 0, map, n_items, 0, 0) < 0) return 1;
+    return on_device(ctx->device, 1, [&] {
+        time_map(ctx, d_items, map->rows * map->cols, *map, 0, n_items, nullptr, 0);
+        for (size_t o = 0; o < map->n_out; o++) map->count[o] += map->start[o + 1] - map->start[o];
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_project_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                           const ebcc_hip_time_map *map)
+{
+    EBCC_API_TRY
+    return project_shard("ebcc_hip_project_shard", ctx, streams, sizes, n_frames, row0, col0, map);
     EBCC_API_CATCH(1)
 }
 

@@ -183,6 +183,151 @@ class QuantileResult:
         self.values, self.count = values, count
 
 
+class TimeMap(ctypes.Structure):
+    """ebcc_hip_time_map, include/ebcc_hip.h: the terms of every output as CSR arrays (host), the accumulators
+    [n_out][rows][cols] of doubles (device), count on the host."""
+    _fields_ = [("n_out", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t), ("start", ctypes.c_void_p),
+                ("frame", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("d_acc", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
+def time_map_terms(weights, n_frames=None):
+    """The CSR arrays of a time map -> (start uint64 (n_out + 1,), frame uint32 (n_terms,), weight float64 (n_terms,)): output
+    o owns the terms start[o] .. start[o + 1).  `weights`: a dense array [n_out][n_frames] of any real dtype, converted to
+    float64 - entries equal to 0 are dropped, the others become the terms of their row in increasing frame -, or a triple
+    (start, frame, weight), used as given.  n_frames: the length of the frame axis (a dense array's own).  ValueError for what
+    ebcc_hip_time_map_check would refuse of these arrays: start[0] != 0, a decreasing start, no term at all, a frame >=
+    n_frames, frames not strictly increasing within an output, a NaN or Inf weight."""
+    if isinstance(weights, tuple) and len(weights) == 3:
+        start, frame, weight = (np.asarray(v) for v in weights)
+        if start.ndim != 1 or start.size < 2 or start.dtype.kind not in "iu" or (start.astype(np.int64) < 0).any():
+            raise ValueError("start must be n_out + 1 integers that are not negative, n_out >= 1")
+        if frame.ndim != 1 or frame.dtype.kind not in "iu" or (frame.size and (frame.astype(np.int64).min() < 0 or frame.astype(np.int64).max() >= 2 ** 32)):
+            raise ValueError("frame must be integers that fit 32 bits")
+        if weight.ndim != 1 or weight.dtype.kind not in "fiu":
+            raise ValueError("weight must be real numbers")
+        start, frame, weight = start.astype(np.uint64), frame.astype(np.uint32), weight.astype(np.float64)
+    else:
+        dense = np.asarray(weights)
+        if dense.ndim != 2 or dense.shape[0] < 1 or dense.dtype.kind not in "fiu":
+            raise ValueError("weights must be a real array [n_out][n_frames] or a (start, frame, weight) triple")
+        dense = dense.astype(np.float64)
+        if n_frames is not None and int(n_frames) != dense.shape[1]:
+            raise ValueError(f"the frame axis of weights has {dense.shape[1]} entries, not {n_frames}")
+        n_frames = dense.shape[1]
+        out, at = np.nonzero(dense != 0.0)                          # (row-major: increasing frame within an output; NaN != 0)
+        start = np.concatenate([[0], np.cumsum(np.bincount(out, minlength=dense.shape[0]))]).astype(np.uint64)
+        frame, weight = at.astype(np.uint32), dense[out, at]
+    if start[0] != 0:
+        raise ValueError("start[0] must be 0")
+    if (np.diff(start.astype(np.int64)) < 0).any():
+        raise ValueError("start decreases")
+    n_terms = int(start[-1])
+    if n_terms < 1:
+        raise ValueError("no term at all")
+    if frame.size < n_terms or weight.size < n_terms:
+        raise ValueError(f"start names {n_terms} terms, frame has {frame.size} and weight {weight.size}")
+    frame, weight = np.ascontiguousarray(frame[:n_terms]), np.ascontiguousarray(weight[:n_terms])
+    if n_frames is not None and int(frame.max()) >= int(n_frames):
+        raise ValueError(f"a term names frame {int(frame.max())} of {int(n_frames)}")
+    inner = np.ones(n_terms, bool)                                  # terms that have a predecessor in their output
+    inner[start[:-1][start[:-1] < n_terms].astype(np.int64)] = False
+    if (np.diff(frame.astype(np.int64)) <= 0)[inner[1:]].any():
+        raise ValueError("the frames of an output must be strictly increasing")
+    if not np.isfinite(weight).all():
+        raise ValueError("every weight must be finite")
+    return np.ascontiguousarray(start), frame, weight
+
+
+def trend_weights(times):
+    """The 2 x n time map of the least-squares line through n >= 2 samples at `times` (float64): row 0 is 1 / n - the mean -,
+    row 1 is (t - mean(t)) / sum((t - mean(t))^2) - the slope per unit of `times`.  Plain float64 numpy."""
+    t = np.asarray(times, np.float64)
+    if t.ndim != 1 or t.size < 2 or not np.isfinite(t).all():
+        raise ValueError("times must be at least two finite numbers")
+    c = t - t.mean()
+    ss = (c * c).sum()
+    if not ss > 0.0:
+        raise ValueError("times must not all be equal")
+    return np.stack([np.full(t.size, 1.0 / t.size), c / ss])
+
+
+def running_mean_weights(n, width):
+    """The banded (n - width + 1) x n time map of the running mean over `width` consecutive frames: output o has the weight
+    1 / width at the frames o .. o + width - 1 and 0 elsewhere.  Plain float64 numpy."""
+    n, width = int(n), int(width)
+    if width < 1 or width > n:
+        raise ValueError("width must lie in [1, n]")
+    w = np.zeros((n - width + 1, n), np.float64)
+    for o in range(n - width + 1):
+        w[o, o:o + width] = 1.0 / width
+    return w
+
+
+class ProjectResult:
+    """Weighted sums over time, per output and pixel: values (n_out, rows, cols) float64 - for every output the bytes of a loop
+    over its terms in increasing frame, acc = acc + weight * float64(x) - and count (n_out,) uint64, the terms folded into
+    each output."""
+
+    def __init__(self, values, count):
+        self.values, self.count = values, count
+
+
+class MapState:
+    """The accumulators of BatchCodec.project, resident on the device from call to call (BatchCodec.map_state makes one):
+    result() downloads them, close() frees them."""
+
+    def __init__(self, codec, n_out, window):
+        self.codec, self.n_out = codec, int(n_out)
+        if self.n_out < 1:
+            raise ValueError("n_out must be at least 1")
+        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
+        row0, col0, rows, cols = self.window
+        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
+            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
+        self.shape = (self.n_out, rows, cols)
+        self.count = np.zeros(self.n_out, np.uint64)
+        self.d_acc = codec.lib.ebcc_hip_malloc(int(np.prod(self.shape)) * 8)
+        if not self.d_acc:
+            codec._fail("ebcc_hip_malloc")
+        try:
+            if codec.lib.ebcc_hip_time_map_init(codec.ctx, ctypes.byref(self.map(None, None, None))):
+                codec._fail("ebcc_hip_time_map_init")
+        except BaseException:
+            self.close()
+            raise
+
+    def map(self, start, frame, weight):
+        """the ebcc_hip_time_map of these accumulators with the terms of one call (arrays the caller keeps alive)"""
+        return TimeMap(self.n_out, self.shape[1], self.shape[2], *(None if a is None else a.ctypes.data for a in (start, frame, weight)),
+                       self.d_acc, self.count.ctypes.data)
+
+    def result(self):
+        a = np.empty(self.shape, np.float64)
+        if self.codec.lib.ebcc_hip_memcpy_d2h(a.ctypes.data, self.d_acc, a.nbytes):
+            self.codec._fail("ebcc_hip_memcpy_d2h")
+        return ProjectResult(a, self.count.copy())
+
+    def close(self):
+        if self.d_acc:
+            self.codec.lib.ebcc_hip_free(self.d_acc)
+            self.d_acc = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _terms_of_range(terms, lo, hi):
+    """the terms of the CSR triple whose frame lies in [lo, hi), frames rebased to lo -> a triple (n_terms may be 0)"""
+    start, frame, weight = terms
+    keep = (frame >= lo) & (frame < hi)
+    owner = np.repeat(np.arange(len(start) - 1), np.diff(start.astype(np.int64)))
+    part = np.concatenate([[0], np.cumsum(np.bincount(owner[keep], minlength=len(start) - 1))]).astype(np.uint64)
+    return part, (frame[keep].astype(np.int64) - lo).astype(np.uint32), np.ascontiguousarray(weight[keep])
+
+
 class Region(ctypes.Structure):
     """ebcc_hip_region, include/ebcc_hip.h: a box of a frame"""
     _fields_ = [("row0", ctypes.c_size_t), ("col0", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t)]
@@ -374,6 +519,9 @@ class BatchCodec:
                                               ctypes.POINTER(AreaSpec), ctypes.c_void_p]
         lib.ebcc_hip_quantile_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeRanks)]
+        lib.ebcc_hip_time_map_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(TimeMap)]
+        lib.ebcc_hip_project_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                               ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeMap)]
         for name in ("ebcc_hip_regrid_shard", "ebcc_hip_regrid_host_frames"):
             getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                            ctypes.POINTER(_regrid.RegridSpec), ctypes.c_void_p]
@@ -547,6 +695,45 @@ class BatchCodec:
                     with np.errstate(invalid="ignore", over="ignore"):
                         values[k, i] = (low64 + (high64 - low64) * t).astype(np.float32)
         return QuantileResult(values, count)
+
+    def map_state(self, n_out, window=None):
+        """Device-resident accumulators for project(state=...): n_out outputs of the window (row0, col0, rows, cols) - None:
+        the whole frame -, set to 0.  A MapState; close() it when done."""
+        return MapState(self, n_out, window)
+
+    def project(self, streams, weights, window=None, state=None, first=0):
+        """Weighted sums over time straight from the streams (ebcc_hip_project_shard): for every output o of the time map
+        `weights` - a dense [n_out][n_frames] array or a (start, frame, weight) triple, see time_map_terms - and every pixel of
+        the frame or of its `window` = (row0, col0, rows, cols) the sum of weight * x over the output's terms, folded on the
+        device in increasing frame: acc = acc + weight * float64(x), product and sum each rounded to float64 -> a
+        ProjectResult.  `first` is the index streams[0] has on the frame axis of `weights`; terms outside [first, first +
+        len(streams)) belong to other calls.  A stream no term names is not read and may be None.  No decoded frame leaves the
+        device, and the sums are the bytes of that loop whatever the engine's capacity.  `state`: a MapState (map_state) that
+        is added to and returned instead - the window is then the state's -, so that a series walked call by call in frame
+        order gives the bytes of one call; state.result() downloads the accumulators.  ValueError for a map the engine would
+        refuse or one without a term in this call, RuntimeError for what the call reports, such as a malformed stream (the
+        state must then be made anew)."""
+        n, first = len(streams), int(first)
+        terms = time_map_terms(weights)
+        if n < 1 or first < 0:
+            raise ValueError("streams must not be empty and first must not be negative")
+        start, frame, weight = _terms_of_range(terms, first, first + n)
+        if not len(frame):
+            raise ValueError(f"no term names a frame in [{first}, {first + n})")
+        own = state is None
+        if own:
+            state = MapState(self, len(start) - 1, window)
+        try:
+            if state.n_out != len(start) - 1:
+                raise ValueError(f"the map has {len(start) - 1} outputs, the state {state.n_out}")
+            streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.unique(frame)))
+            row0, col0 = state.window[:2]
+            if self.lib.ebcc_hip_project_shard(self.ctx, ptrs, sizes, n, row0, col0, ctypes.byref(state.map(start, frame, weight))):
+                self._fail("ebcc_hip_project_shard")
+            return state.result() if own else state
+        finally:
+            if own:
+                state.close()
 
     def series(self, streams, regions, w_row=None, w_pix=None, threshold=None):
         """Statistics over regions at every time step straight from the streams (ebcc_hip_series_shard): `regions` is an int
@@ -1063,6 +1250,52 @@ def quantile_frames(dset, q, bins=None, n_bins=None, rows=None, cols=None, metho
     with held_codec(h, w, min(batch, len(named)), codec=codec) as codec:
         raw = _read_chunks(dset, named)
         return codec.quantiles(raw, q, bins=b[named], n_bins=n_bins, window=(row0, col0, nrows, ncols), method=method)
+
+
+def project_frames(dset, weights, rows=None, cols=None, batch=256, codec=None):
+    """Weighted sums over time of an EBCC-filtered one-frame-per-chunk dataset, folded on the device (BatchCodec.project):
+    `weights` is a time map over the frames counted in C order of the leading axes - a dense [n_out][n_frames] array or a
+    (start, frame, weight) triple (time_map_terms; trend_weights and running_mean_weights make two) -, `rows` / `cols` are
+    slices (step 1) as in read_frames -> a ProjectResult whose values equal, for every output, a loop over its terms in
+    increasing frame, acc = acc + weight * float64(x), on read_frames(dset)[..., rows, cols]; no frame is downloaded.  Only the
+    chunks of frames that some term names are fetched, as read_frames fetches them, the next call's on a helper thread, and
+    folded call after call into one device-resident state, so the dataset need not fit into host memory."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    terms = time_map_terms(weights, n_frames=n)
+    named = np.unique(terms[1]).astype(np.int64)
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
+        step = _SUPER * codec.max_frames
+
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, named[lo:lo + step]))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
+
+        box = []
+        fetch(0, box)
+        state = stack.enter_context(codec.map_state(len(terms[0]) - 1, (row0, col0, nrows, ncols)))
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                # the call's streams are the named frames of this step alone: its terms, with their frames counted among them
+                start, frame, weight = _terms_of_range(terms, int(named[lo]), int(named[lo:lo + step][-1]) + 1)
+                at = np.searchsorted(named[lo:lo + step], frame.astype(np.int64) + int(named[lo])).astype(np.uint32)
+                codec.project(raw, (start, at, weight), state=state)
+            finally:
+                if t:
+                    t.join()
+        return state.result()
 
 
 def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=None, batch=256, codec=None):

@@ -726,6 +726,65 @@ int ebcc_hip_rank_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items,
 int ebcc_hip_quantile_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
                             size_t row0, size_t col0, const ebcc_hip_time_ranks *spec);
 
+/* ---- time-map decode: weighted sums over time per pixel, from the streams, on the device --------
+ * The sixth question an archive is asked: a linear functional over time with a weight per frame - the least-squares trend
+ * per pixel (the weight is the centred time), the regression of a field on an index series, a composite (weights +-1/m), the
+ * annual and semi-annual harmonics (cosine and sine weights), a running mean, a Lanczos filter or an interpolation to other
+ * time steps (many outputs, each reading a few neighbouring frames).  The reduce decode adds every frame with weight 1, and
+ * the regrid decode's axis maps weight rows and columns: this is the same sparse weighted map for the time axis.  Streams go
+ * in, one plane [rows][cols] of doubles per output comes out; no decoded frame reaches the caller.  The reference has no
+ * counterpart.
+ * The order is the contract, as for the reduce decode.  The map is a list of terms per output (CSR: output o owns the terms
+ * start[o] .. start[o + 1)), each a frame and a weight, the frames strictly increasing within an output.  For every output o and
+ * pixel p the terms of o are taken in the order of the list:
+ *   acc[o][p] = acc[o][p] + weight[t] * (double) x_frame[t][p]
+ * The product is rounded to double, then the sum is rounded to double; the two are never contracted into an FMA.  Every listed
+ * term takes part - a weight of 0 is no special case: a caller who wants a frame left out leaves the term out.  A frame no term
+ * names is not read at all: its streams[f] may be NULL with size 0, and it takes no slot of a batch.  An output without terms
+ * is legal and is never touched.  An accumulator that a NaN reaches (a NaN sample, or Inf - Inf) is a NaN, which one is not
+ * specified; everything else is specified to the bit.  No atomics, and frames never meet in a reduction tree
+ * (ebcc_amd/csrc/time_map.hip: k_time_map; consecutive outputs that name the same frames of a batch are folded together, up to
+ * four to a loaded sample, which changes no addition and no order).  So the accumulators are the same bytes whatever the batch
+ * size, the slices, the engine sets, the alignment of the arrays, whether the frame was decoded whole or as a window, and the
+ * split of a series over several calls made in frame order: a call adds to what d_acc and count hold, and the caller rebases
+ * `frame` per call.
+ * Not covered: chunks of several frames, EBCK containers, a host-pointer output, float32 accumulators, maps whose weights
+ * vary per pixel, the reference-compatible entry points and the filter callback. */
+typedef struct {
+    size_t          n_out, rows, cols;  /* the accumulators are [n_out][rows][cols] */
+    const size_t   *start;              /* host [n_out + 1]: output o owns terms start[o] .. start[o + 1); start[0] == 0 */
+    const uint32_t *frame;              /* host [n_terms]: index into the call's stream (item) list, strictly increasing within an output */
+    const double   *weight;             /* host [n_terms]: finite, any sign */
+    double         *d_acc;              /* device, 8-byte aligned */
+    uint64_t       *count;              /* host [n_out]: terms folded into each output */
+} ebcc_hip_time_map;
+/* Host only, no device: the number of distinct frames the map names, or -1 with a message for what the calls below refuse
+ * before touching a device: a null map, start, d_acc or count, a null frame or weight when there are terms, n_out, rows or cols
+ * zero, start[0] != 0 or a decreasing start, no term at all, a frame >= n_frames, frames not strictly increasing within an
+ * output, a NaN or Inf weight, a d_acc that is not 8-byte aligned, a window [row0, row0 + rows) x [col0, col0 + cols) not inside
+ * the height x width frame, sizes that overflow (n_out of 2^32 - 1 or more among them), a geometry ebcc_hip_create refuses. */
+long ebcc_hip_time_map_check(size_t height, size_t width, const ebcc_hip_time_map *map, size_t n_frames, size_t row0, size_t col0);
+/* d_acc = +0.0, count = 0.  ctx: any context of the device.  0 = ok, 1 = error. */
+int ebcc_hip_time_map_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_map *map);
+/* unit level, the kernel alone: d_items [n_items][rows][cols] at any 4-byte aligned device address, `frame` indexes the items.
+ * An item no term names is not read; the items are never written.  ctx: any context of the device.  Adds to what the map holds
+ * (count included).  0 = ok, 1 = error with nothing written: what the check refuses, null or misaligned items. */
+int ebcc_hip_time_map_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const ebcc_hip_time_map *map);
+/* Any number of one-frame streams: the frames the map names are decoded - the window [row0, row0 + map->rows) x [col0, col0 +
+ * map->cols) by the window decode, the whole frame by the full decode when the window is the frame - in batches of the
+ * context's capacity on the two engine sets, each into its set's audit buffer (the one ebcc_hip_audit_* use: a context runs
+ * one call at a time), and folded.  The decodes of two batches run side by side; the folds take turns in batch order.  The call
+ * adds to what the map holds: a series folded by several calls in frame order gives the bytes of one call.
+ * Return 0 = ok, 1 = error (ebcc_hip_last_error).  Refused before anything is written, accumulators and count included: what
+ * ebcc_hip_time_map_check refuses for the context's frames, a context for chunks of several frames, a named frame without a
+ * stream or with one whose frame header does not parse (truncated, sizes that do not add up).  A stream found damaged inside a
+ * batch - its codestream or its residual layer - is refused as ebcc_hip_decode_frames refuses it; a batch folds only after all
+ * of it has decoded, so streams that all fail (a context of another geometry) leave everything untouched, but after batches
+ * that succeeded the accumulators hold an unspecified mixture and must be initialised again (count is only advanced by a call
+ * that succeeds).  Nothing outside the accumulators is written in either case. */
+int ebcc_hip_project_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
+                           const ebcc_hip_time_map *map);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -766,7 +825,7 @@ void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4])
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
  * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid", "rank_count",
- * "rank_advance".  Process-wide switch. */
+ * "rank_advance", "time_map".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
