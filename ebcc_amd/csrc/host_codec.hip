@@ -10,6 +10,7 @@
 #include "regrid.hpp"
 #include "quantile.hpp"
 #include "time_map.hpp"
+#include "pair_stats.hpp"
 
 using namespace ebcc;
 
@@ -520,6 +521,8 @@ int encode_batches_alternating(ebcc_hip_ctx *ctx, size_t n_frames, const FrameCo
 // residual streams, its one-wave-per-frame SPIHT chains, which leave most of the chip idle) beside the other's kernels.
 //   decode_batches(ctx, n, each)          runs free: each(set, first frame, count) decodes one batch and puts its output where it belongs
 //   decode_batches(ctx, n, decode, fold)  ordered: decode(set, first frame, count) -> status, then - in batch order, and only while nothing has failed - fold(same)
+// granule: a batch is the context's capacity rounded down to a multiple of it (which must not be 0: the caller refuses a smaller
+// context), so the frames that belong together - the x and the y of a step of the pair decode - never fall into different batches.
 // Whose turn it is to fold: batch b folds after batch b - 1 has passed its turn on, while the two sets decode side by side.
 // A batch passes its turn on when its iteration of the batch loop ends, however it ends (decode_batches: a destructor), every
 // batch has an iteration - a loop that has seen a failure goes on and only passes -, and a thread that is left any other way
@@ -542,10 +545,10 @@ struct FoldTurn {
     void leave(int t) { { std::lock_guard<std::mutex> l(m); left[t] = true; } cv.notify_all(); }
 };
 template <class Decode, class Fold = std::nullptr_t>
-int decode_batches(ebcc_hip_ctx *ctx, size_t n, Decode decode, Fold fold = nullptr)
+int decode_batches(ebcc_hip_ctx *ctx, size_t n, Decode decode, Fold fold = nullptr, size_t granule = 1)
 {
     constexpr bool ordered = !std::is_same<Fold, std::nullptr_t>::value;
-    const size_t cap = ctx->max_frames, batches = (n + cap - 1) / cap;
+    const size_t cap = ctx->max_frames / granule * granule, batches = (n + cap - 1) / cap;
     if (batches == 1) {
         const int r = decode(ctx, (size_t) 0, n);
         if constexpr (ordered) { if (!r) fold(ctx, (size_t) 0, n); }
@@ -1082,7 +1085,7 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
-// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode, time-map decode).  What one asks the driver for, its own arguments checked:
+// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode, time-map decode, pair decode).  What one asks the driver for, its own arguments checked:
 struct DecodedAsk {
     const uint8_t *const *streams = nullptr;
     const size_t *sizes = nullptr, *names = nullptr;   // names[i]: the number stream i has in the caller's list, for a message (null: i)
@@ -1092,6 +1095,7 @@ struct DecodedAsk {
     bool parsed_first = false;              // every stream must parse as a frame stream before anything is written
     const char *decode_mark = "";           // EBCC_HIP_PHASE_TIMING label of a batch's decode
     std::function<bool()> ready;            // if set: runs in the device prologue before the first decode; false: refused, message set
+    size_t granule = 1;                     // streams that must share a batch: n is a multiple, the context's capacity at least one (decode_batches)
 };
 // The one driver: the refusals of the context, ask(DecodedAsk &) -> false when the consumer refuses its own arguments (message
 // set), the pre-parse, decode_call's checks and device prologue, then the batches of the context's capacity on the two sets
@@ -1122,12 +1126,12 @@ int consume_decoded(const char *who, ebcc_hip_ctx *ctx, bool one_batch, bool ord
             return r;
         };
         auto hand = [&](ebcc_hip_ctx *set, size_t lo, size_t k) { per_batch(set, (const float *) set->audit.d, lo, k, pt[set != ctx]); };
-        if (ordered) return decode_batches(ctx, n, decode, hand);
+        if (ordered) return decode_batches(ctx, n, decode, hand, a.granule);
         return decode_batches(ctx, n, [&](ebcc_hip_ctx *set, size_t lo, size_t k) {
             if (const int r = decode(set, lo, k)) return r;
             hand(set, lo, k);
             return 0;
-        });
+        }, nullptr, a.granule);
     }, held);
 }
 
@@ -1329,6 +1333,44 @@ int project_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *stre
         pt.mark("project: fold");
     });
     if (!rc) for (size_t o = 0; o < map->n_out; o++) map->count[o] += map->start[o + 1] - map->start[o];
+    return rc;
+}
+
+// ---- pair decode: co-moments and vector magnitude of two variables over time (include/ebcc_hip.h: ebcc_hip_pair_stats; k_pair_fold, pair_stats.hip)
+// Built as reduce_shard is, with two streams to a step: the decode sees the named steps' streams interleaved - item 2i is the x
+// and item 2i + 1 the y of the i-th named step - and asks for batches of an even number of frames (DecodedAsk::granule), so the
+// two frames of a step lie in the same batch, whose fold gets the audit buffer as both bases.  The fold is ordered: a bin's
+// additions are in step order.  The pre-parse is the call's own: its message names the step and says x or y.
+int pair_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, const size_t *x_sizes, const uint8_t *const *y_streams,
+               const size_t *y_sizes, size_t n_steps, const uint32_t *bin, size_t row0, size_t col0, const ebcc_hip_pair_stats *stats)
+{
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz;
+    std::vector<uint32_t> bn;
+    const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
+        if (pair_stats_named(who, (size_t) ctx->height, (size_t) ctx->width, stats, bin, n_steps, row0, col0) < 0) return false;
+        if (!x_streams || !x_sizes || !y_streams || !y_sizes) { set_error("%s: bad arguments", who); return false; }
+        if (ctx->max_frames < 2) { set_error("%s: a context of capacity 1 cannot hold the two frames of a step", who); return false; }
+        for (size_t t = 0; t < n_steps; t++) {
+            const uint32_t b = bin ? bin[t] : 0u;
+            if (b == EBCC_HIP_NO_BIN) continue;
+            ParsedFrame pf;
+            if (!x_streams[t] || !parse_frame(x_streams[t], x_sizes[t], pf)) { set_error("%s: step %zu: x is not a frame stream", who, t); return false; }
+            if (!y_streams[t] || !parse_frame(y_streams[t], y_sizes[t], pf)) { set_error("%s: step %zu: y is not a frame stream", who, t); return false; }
+            st.push_back(x_streams[t]); sz.push_back(x_sizes[t]);
+            st.push_back(y_streams[t]); sz.push_back(y_sizes[t]);
+            bn.push_back(b);
+        }
+        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.out = stats;
+        a.box = ebcc_hip_region{row0, col0, stats->rows, stats->cols};
+        a.granule = 2;
+        a.decode_mark = "pair: decode";
+        return true;
+    }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
+        pair_fold(set, decoded, decoded, true, k / 2, stats->rows * stats->cols, bn.data() + lo / 2, *stats);
+        pt.mark("pair: fold");
+    });
+    if (!rc) for (const uint32_t b : bn) stats->count[b]++;
     return rc;
 }
 
@@ -2218,6 +2260,58 @@ int ebcc_hip_quantile_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, co
 {
     EBCC_API_TRY
     return quantile_shard("ebcc_hip_quantile_shard", ctx, streams, sizes, n_frames, bin, row0, col0, spec);
+    EBCC_API_CATCH(1)
+}
+
+// ---- pair decode (pair_shard above): co-moments and vector magnitude of two variables over time, folded on the device
+long ebcc_hip_pair_stats_check(size_t height, size_t width, const ebcc_hip_pair_stats *stats, const uint32_t *bin, size_t n_steps, size_t row0,
+                               size_t col0)
+{
+    EBCC_API_TRY
+    return pair_stats_named("ebcc_hip_pair_stats_check", height, width, stats, bin, n_steps, row0, col0);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_pair_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_pair_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_pair_stats_init";
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    if (!pair_stats_shape(who, stats)) return 1;
+    return on_device(ctx->device, 1, [&] {
+        const size_t n = stats->n_bins * stats->rows * stats->cols;
+        for (double *p : {stats->d_sum_x, stats->d_sum_y, stats->d_sum_xx, stats->d_sum_yy, stats->d_sum_xy, stats->d_sum_mag})
+            if (p) EBCC_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(double), ctx->stream));
+        if (stats->d_over_mag) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_over_mag, 0, n * sizeof(uint32_t), ctx->stream));
+        if (stats->d_max_mag) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max_mag, (int) 0xFF800000u, n, ctx->stream));     // -inf
+        wait_stream(ctx->stream);
+        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_pair_fold(ebcc_hip_ctx *ctx, const float *d_x_items, const float *d_y_items, size_t n_items, const uint32_t *bin,
+                       const ebcc_hip_pair_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_pair_fold";
+    if (!ctx || !d_x_items || !d_y_items || ((uintptr_t) d_x_items & 3) || ((uintptr_t) d_y_items & 3) || n_items >= 0xFFFFFFFFu) {
+        set_error("%s: bad arguments", who);
+        return 1;
+    }
+    if (pair_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0) < 0) return 1;
+    return on_device(ctx->device, 1, [&] {
+        pair_fold(ctx, d_x_items, d_y_items, false, n_items, stats->rows * stats->cols, bin, *stats);
+        for (size_t k = 0; k < n_items; k++)
+            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_pair_shard(ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, const size_t *x_sizes, const uint8_t *const *y_streams,
+                        const size_t *y_sizes, size_t n_steps, const uint32_t *bin, size_t row0, size_t col0, const ebcc_hip_pair_stats *stats)
+{
+    EBCC_API_TRY
+    return pair_shard("ebcc_hip_pair_shard", ctx, x_streams, x_sizes, y_streams, y_sizes, n_steps, bin, row0, col0, stats);
     EBCC_API_CATCH(1)
 }
 

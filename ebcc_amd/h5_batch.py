@@ -139,6 +139,118 @@ class ReduceState:
         self.close()
 
 
+class PairStats(ctypes.Structure):
+    """ebcc_hip_pair_stats, include/ebcc_hip.h: per-pixel accumulators [n_bins][rows][cols] of two variables on the device, count on the host."""
+    _fields_ = [("n_bins", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t),
+                ("d_sum_x", ctypes.c_void_p), ("d_sum_y", ctypes.c_void_p), ("d_sum_xx", ctypes.c_void_p), ("d_sum_yy", ctypes.c_void_p),
+                ("d_sum_xy", ctypes.c_void_p), ("d_sum_mag", ctypes.c_void_p), ("d_max_mag", ctypes.c_void_p), ("d_over_mag", ctypes.c_void_p),
+                ("threshold", ctypes.c_float), ("count", ctypes.c_void_p)]
+
+
+class PairResult:
+    """Co-moments and vector magnitude of two variables over time, per bin and pixel: count (n_bins,) uint64 - the steps folded
+    into each bin -, sum_x, sum_y, sum_xx, sum_yy, sum_xy (n_bins, rows, cols) float64, and of m = sqrt(x^2 + y^2) in float32:
+    sum_mag float64, max_mag float32, over_mag uint32 (the steps with m > threshold).  The magnitude arrays are None when they
+    were not asked for, over_mag is None without a threshold.  The sums are those of a loop over the steps in increasing
+    index, acc = acc + term in float64.  mean_x, mean_y, cov (sum_xy / n - mean_x * mean_y), corr and mean_mag are float64;
+    NaN where a bin has no steps, corr also where a variance is 0."""
+
+    def __init__(self, count, sum_x, sum_y, sum_xx, sum_yy, sum_xy, sum_mag, max_mag, over_mag):
+        self.count, self.sum_x, self.sum_y, self.sum_xx, self.sum_yy, self.sum_xy = count, sum_x, sum_y, sum_xx, sum_yy, sum_xy
+        self.sum_mag, self.max_mag, self.over_mag = sum_mag, max_mag, over_mag
+
+    def _over_n(self, a):
+        n = self.count.astype(np.float64)[:, None, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, a / n, np.nan)
+
+    @property
+    def mean_x(self):
+        return self._over_n(self.sum_x)
+
+    @property
+    def mean_y(self):
+        return self._over_n(self.sum_y)
+
+    @property
+    def cov(self):
+        with np.errstate(invalid="ignore"):
+            return self._over_n(self.sum_xy) - self.mean_x * self.mean_y
+
+    @property
+    def corr(self):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mx, my = self.mean_x, self.mean_y
+            vx, vy = self._over_n(self.sum_xx) - mx * mx, self._over_n(self.sum_yy) - my * my
+            r = self.cov / np.sqrt(vx * vy)
+        r[~((vx > 0) & (vy > 0))] = np.nan
+        return r
+
+    @property
+    def mean_mag(self):
+        return None if self.sum_mag is None else self._over_n(self.sum_mag)
+
+
+class PairState:
+    """The accumulators of BatchCodec.pair, resident on the device from call to call (BatchCodec.pair_state makes one):
+    result() downloads them, close() frees them."""
+
+    def __init__(self, codec, n_bins, window, threshold, magnitude):
+        self.codec, self.n_bins = codec, int(n_bins)
+        if self.n_bins < 1:
+            raise ValueError("n_bins must be at least 1")
+        if threshold is not None and (not magnitude or np.isnan(float(threshold))):
+            raise ValueError("a threshold needs magnitude=True and must not be a NaN")
+        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
+        row0, col0, rows, cols = self.window
+        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
+            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
+        self.shape = (self.n_bins, rows, cols)
+        self.count = np.zeros(self.n_bins, np.uint64)
+        self.stats = PairStats(self.n_bins, rows, cols, None, None, None, None, None, None, None, None, 0.0 if threshold is None else float(threshold),
+                               self.count.ctypes.data)
+        self.fields = [(name, np.float64) for name in ("d_sum_x", "d_sum_y", "d_sum_xx", "d_sum_yy", "d_sum_xy")]
+        if magnitude:
+            self.fields += [("d_sum_mag", np.float64), ("d_max_mag", np.float32)]
+        if threshold is not None:
+            self.fields.append(("d_over_mag", np.uint32))
+        lib = codec.lib
+        try:
+            for name, dtype in self.fields:
+                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
+                if not p:
+                    codec._fail("ebcc_hip_malloc")
+                setattr(self.stats, name, p)
+            if lib.ebcc_hip_pair_stats_init(codec.ctx, ctypes.byref(self.stats)):
+                codec._fail("ebcc_hip_pair_stats_init")
+        except BaseException:
+            self.close()
+            raise
+
+    def result(self):
+        lib, got = self.codec.lib, {}
+        for name, dtype in self.fields:
+            a = np.empty(self.shape, dtype)
+            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, name), a.nbytes):
+                self.codec._fail("ebcc_hip_memcpy_d2h")
+            got[name] = a
+        return PairResult(self.count.copy(), got["d_sum_x"], got["d_sum_y"], got["d_sum_xx"], got["d_sum_yy"], got["d_sum_xy"], got.get("d_sum_mag"),
+                          got.get("d_max_mag"), got.get("d_over_mag"))
+
+    def close(self):
+        for name, _ in self.fields:
+            p = getattr(self.stats, name)
+            if p:
+                self.codec.lib.ebcc_hip_free(p)
+                setattr(self.stats, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class TimeRanks(ctypes.Structure):
     """ebcc_hip_time_ranks, include/ebcc_hip.h: the order statistics asked of every bin (host) and their planes
     [n_bins][n_ranks][rows][cols] (device), count on the host."""
@@ -515,6 +627,10 @@ class BatchCodec:
         lib.ebcc_hip_time_stats_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(TimeStats)]
         lib.ebcc_hip_reduce_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(TimeStats)]
+        lib.ebcc_hip_pair_stats_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(PairStats)]
+        lib.ebcc_hip_pair_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                            ctypes.POINTER(PairStats)]
         lib.ebcc_hip_series_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.POINTER(AreaSpec), ctypes.c_void_p]
         lib.ebcc_hip_quantile_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
@@ -625,6 +741,49 @@ class BatchCodec:
             row0, col0 = state.window[:2]
             if self.lib.ebcc_hip_reduce_shard(self.ctx, ptrs, sizes, n, table.ctypes.data, row0, col0, ctypes.byref(state.stats)):
                 self._fail("ebcc_hip_reduce_shard")
+            return state.result() if own else state
+        finally:
+            if own:
+                state.close()
+
+    def pair_state(self, n_bins=1, window=None, threshold=None, magnitude=True):
+        """Device-resident accumulators for pair(state=...): n_bins bins of the window (row0, col0, rows, cols) - None: the
+        whole frame -, the magnitude's sum and maximum unless magnitude=False, its exceedance count when a threshold is given.
+        A PairState; close() it when done."""
+        return PairState(self, n_bins, window, threshold, magnitude)
+
+    def pair(self, streams_x, streams_y, bins=None, n_bins=1, window=None, threshold=None, magnitude=True, state=None):
+        """Co-moments and vector magnitude of two variables over time straight from the streams (ebcc_hip_pair_shard): step t
+        pairs streams_x[t] with streams_y[t] - frames of the engine's geometry, or their `window` = (row0, col0, rows, cols) -,
+        and every step is folded on the device into the accumulators of the bin `bins` names for it (an integer per step,
+        None: all bin 0, -1: the step is skipped and not read - its entries may be None) -> a PairResult.  No decoded frame
+        leaves the device; the sums are the bytes of a loop over the steps in order, whatever the engine's capacity (2 at the
+        least).  streams_x may be streams_y.  `state`: a PairState (pair_state) that is added to and returned instead - n_bins,
+        window, threshold and magnitude are then the state's -, so that a series walked call by call in step order gives the
+        bytes of one call.  ValueError for bins the engine refuses, RuntimeError for what the call reports, such as a
+        malformed stream (the state must then be made anew)."""
+        n = len(streams_x)
+        if len(streams_y) != n:
+            raise ValueError(f"{n} streams of x and {len(streams_y)} of y")
+        own = state is None
+        if own:
+            state = PairState(self, n_bins, window, threshold, magnitude)
+        try:
+            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
+                raise ValueError(f"bins must be {n} integers, one per step")
+            b = b.astype(np.int64)
+            if b.min() < -1 or b.max() >= state.n_bins:
+                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
+            if not (b >= 0).any():
+                raise ValueError("no step is named")
+            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            named = set(int(f) for f in np.nonzero(b >= 0)[0])
+            keep_x, ptrs_x, sizes_x = _stream_arrays(streams_x, named=named)
+            keep_y, ptrs_y, sizes_y = (keep_x, ptrs_x, sizes_x) if streams_y is streams_x else _stream_arrays(streams_y, named=named)
+            row0, col0 = state.window[:2]
+            if self.lib.ebcc_hip_pair_shard(self.ctx, ptrs_x, sizes_x, ptrs_y, sizes_y, n, table.ctypes.data, row0, col0, ctypes.byref(state.stats)):
+                self._fail("ebcc_hip_pair_shard")
             return state.result() if own else state
         finally:
             if own:
@@ -1220,6 +1379,59 @@ def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=
                 t.start()
             try:
                 codec.reduce(raw, bins=b[named[lo:lo + step]], state=state)
+            finally:
+                if t:
+                    t.join()
+        return state.result()
+
+
+def pair_frames(dset_x, dset_y, bins=None, n_bins=None, rows=None, cols=None, threshold=None, magnitude=True, batch=256, codec=None):
+    """Co-moments and vector magnitude over time of two EBCC-filtered one-frame-per-chunk datasets of the same shape, folded on
+    the device (BatchCodec.pair): frame f of dset_x is paired with frame f of dset_y - u10 and v10, or a variable and itself
+    shifted.  `bins`, n_bins, `rows` / `cols` as in reduce_frames (-1: the step is skipped, its chunks are not fetched);
+    `threshold`: count the steps whose magnitude is above it; magnitude=False: co-moments only.  -> a PairResult whose every
+    array equals the same loop, step after step in C order of the leading axes, over read_frames of both datasets; no frame is
+    downloaded.  The chunks of both are fetched as reduce_frames fetches them, the next call's on a helper thread, and folded
+    call after call into one device-resident state.  ValueError for datasets of different shape."""
+    if tuple(dset_x.shape) != tuple(dset_y.shape):
+        raise ValueError(f"the datasets have the shapes {tuple(dset_x.shape)} and {tuple(dset_y.shape)}")
+    h, w = dset_x.shape[-2:]
+    lead = dset_x.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
+        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
+    b = b.astype(np.int64).reshape(-1)
+    named = np.nonzero(b >= 0)[0]
+    if len(named) < 1 or b.min() < -1:
+        raise ValueError("bins must name at least one step, and -1 is the only negative value")
+    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
+    if b.max() >= n_bins:
+        raise ValueError(f"a step names bin {int(b.max())} of {n_bins}")
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, max(2, min(batch, 2 * len(named))), codec=codec))
+        step = _SUPER * max(1, codec.max_frames // 2)                   # (steps a call: two frames each)
+
+        def fetch(lo, box):
+            try:
+                box.append((_read_chunks(dset_x, named[lo:lo + step]), _read_chunks(dset_y, named[lo:lo + step])))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
+
+        box = []
+        fetch(0, box)
+        state = stack.enter_context(codec.pair_state(n_bins, (row0, col0, nrows, ncols), threshold, magnitude))
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                codec.pair(raw[0], raw[1], bins=b[named[lo:lo + step]], state=state)
             finally:
                 if t:
                     t.join()

@@ -785,6 +785,72 @@ int ebcc_hip_time_map_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_it
 int ebcc_hip_project_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, size_t row0, size_t col0,
                            const ebcc_hip_time_map *map);
 
+/* ---- pair decode: co-moments and vector magnitude of two variables over time, from the streams, on the device ----
+ * The first question that needs two variables: the correlation of two fields per pixel, a covariance or eddy flux u'v', a
+ * lagged auto-covariance (y is x shifted), the mean, maximum and "days above 15 m/s" of the wind speed from u10 / v10.  Two
+ * lists of streams go in, per-pixel accumulators come out; no decoded frame reaches the caller.  The reference has no
+ * counterpart.
+ * The order is the contract, as for the reduce decode.  Two lists of one-frame streams of the same geometry, x and y, have
+ * n_steps entries each; step t pairs x[t] with y[t].  For every bin and pixel the steps of that bin are folded in increasing
+ * step index, one after the other, with a = (double) x and b = (double) y:
+ *   sum_x  = sum_x  + a          sum_y  = sum_y  + b
+ *   sum_xx = sum_xx + a * a      sum_yy = sum_yy + b * b      sum_xy = sum_xy + a * b
+ *   m      = sqrtf((float)(a * a + b * b))
+ *   sum_mag = sum_mag + (double) m;   max_mag = fmaxf(max_mag, m);   over_mag += m > threshold   (compared in float)
+ * Every product of two widened floats is exact in double; the sum a * a + b * b rounds once, to double; the result rounds to
+ * float (nearest even) and m is the correctly rounded float square root of that float (the library is built with
+ * -fhip-fp32-correctly-rounded-divide-sqrt, and the rule relies on that flag and nothing else).  sum_x and sum_xx are
+ * therefore the bytes ebcc_hip_reduce_shard gives as sum and sum_sq for x alone.  Not specified: an accumulator a NaN reaches
+ * (a NaN sample, Inf - Inf, an Inf magnitude's partner), and the magnitude of a sample pair whose (float)(a * a + b * b) is
+ * subnormal; everything else is specified to the bit.  No atomics, and steps never meet in a reduction tree
+ * (ebcc_amd/csrc/pair_stats.hip: k_pair_fold).  So the accumulators are the same bytes whatever the batch size, the engine
+ * sets, the slices, the alignment of any array, whether the frames were decoded whole or as a window, and the split of a
+ * series over several calls made in step order.
+ * Not covered: chunks of several frames, EBCK containers, a host-pointer form, x and y of different geometry, the
+ * reference-compatible entry points and the filter callback. */
+typedef struct {
+    size_t    n_bins, rows, cols;                               /* accumulators are [n_bins][rows][cols] */
+    double   *d_sum_x, *d_sum_y, *d_sum_xx, *d_sum_yy, *d_sum_xy; /* device, 8-byte aligned; each may be NULL */
+    double   *d_sum_mag;                                        /* device, 8-byte aligned; may be NULL */
+    float    *d_max_mag;                                        /* device, 4-byte aligned; may be NULL */
+    uint32_t *d_over_mag; float threshold;                      /* device, may be NULL: steps with m > threshold */
+    uint64_t *count;                                            /* host [n_bins]: steps folded into each bin */
+} ebcc_hip_pair_stats;
+/* Host only, no device (no device pointer is followed): the number of steps `bin` names (bin: host [n_steps], NULL = every
+ * step in bin 0, EBCC_HIP_NO_BIN = the step is skipped), or -1 with a message for what the calls below refuse before touching
+ * a device: a null stats or a null count, every device array NULL, n_bins, rows or cols zero, a window [row0, row0 + rows) x
+ * [col0, col0 + cols) not inside the height x width frame, a double array that is not 8-byte aligned or another array that is
+ * not 4-byte aligned, a NaN threshold when d_over_mag is set, a bin >= n_bins, no step named, a geometry ebcc_hip_create
+ * refuses. */
+long ebcc_hip_pair_stats_check(size_t height, size_t width, const ebcc_hip_pair_stats *stats, const uint32_t *bin, size_t n_steps,
+                               size_t row0, size_t col0);
+/* sums and over = 0, max_mag = -inf, count = 0.  ctx: any context of the device.  0 = ok, 1 = error. */
+int ebcc_hip_pair_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_pair_stats *stats);
+/* unit level, the kernel alone: d_x_items and d_y_items are [n_items][rows][cols], each at any 4-byte aligned device address;
+ * they may be the same array.  Item k of one is paired with item k of the other, in index order, into the bin it names; an item
+ * with EBCC_HIP_NO_BIN is not read, a bin no item names is not touched.  The items are never written.  A call that asks for
+ * co-moments alone executes no square root, one that asks for the magnitude alone holds no co-moment.  ctx: any context of
+ * the device.  Adds to what stats holds (count included).  0 = ok, 1 = error, nothing written. */
+int ebcc_hip_pair_fold(ebcc_hip_ctx *ctx, const float *d_x_items, const float *d_y_items, size_t n_items, const uint32_t *bin,
+                       const ebcc_hip_pair_stats *stats);
+/* Two lists of n_steps one-frame streams: the two frames of every step `bin` names are decoded - the window [row0, row0 +
+ * stats->rows) x [col0, col0 + stats->cols) by the window decode, the whole frame by the full decode when the window is the
+ * frame - side by side in the same batch (x, y, x, y, ..: a batch holds the context's capacity rounded down to an even number
+ * of frames, so an odd capacity works and a capacity of 3 gives one step per batch) on the two engine sets, each into its
+ * set's audit buffer, and folded.  The decodes of two batches run side by side; the folds take turns in batch order.  A
+ * skipped step is not read at all: both of its stream pointers may be NULL with size 0, and it takes no room in a batch.
+ * x_streams == y_streams is legal: sum_xy then carries the bytes of sum_xx.  The call adds to what stats holds: a series folded
+ * by several calls in step order gives the bytes of one call.
+ * Return 0 = ok, 1 = error (ebcc_hip_last_error).  Refused before anything is written, accumulators and count included: what
+ * ebcc_hip_pair_stats_check refuses for the context's frames, null stream or size arrays, a context for chunks of several
+ * frames, a context of capacity 1, a named step where either stream is missing or does not parse as a frame stream (the
+ * message names the step and says x or y).  A stream found damaged inside a batch behaves as ebcc_hip_reduce_shard documents:
+ * the batch is refused as ebcc_hip_decode_frames refuses it, earlier batches may have folded - the accumulators then hold an
+ * unspecified mixture and must be initialised again -, and count is only advanced by a call that succeeds. */
+int ebcc_hip_pair_shard(ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, const size_t *x_sizes, const uint8_t *const *y_streams,
+                        const size_t *y_sizes, size_t n_steps, const uint32_t *bin, size_t row0, size_t col0,
+                        const ebcc_hip_pair_stats *stats);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -825,7 +891,7 @@ void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4])
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
  * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid", "rank_count",
- * "rank_advance", "time_map".  Process-wide switch. */
+ * "rank_advance", "time_map", "pair_fold".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 
