@@ -11,6 +11,7 @@
 #include "quantile.hpp"
 #include "time_map.hpp"
 #include "pair_stats.hpp"
+#include "spell_stats.hpp"
 
 using namespace ebcc;
 
@@ -1085,7 +1086,7 @@ int decode_boxes(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *strea
     return host ? decode_host(who, ctx, streams, sizes, n_frames, out, region) : decode_resident(who, ctx, streams, sizes, n_frames, out, region, one_batch);
 }
 
-// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode, time-map decode, pair decode).  What one asks the driver for, its own arguments checked:
+// ---- consumers of decoded frames (audit, reduce decode, area series, regrid decode, quantile decode, time-map decode, pair decode, spell decode).  What one asks the driver for, its own arguments checked:
 struct DecodedAsk {
     const uint8_t *const *streams = nullptr;
     const size_t *sizes = nullptr, *names = nullptr;   // names[i]: the number stream i has in the caller's list, for a message (null: i)
@@ -1369,6 +1370,39 @@ int pair_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *x_strea
     }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
         pair_fold(set, decoded, decoded, true, k / 2, stats->rows * stats->cols, bn.data() + lo / 2, *stats);
         pt.mark("pair: fold");
+    });
+    if (!rc) for (const uint32_t b : bn) stats->count[b]++;
+    return rc;
+}
+
+// ---- spell decode: run lengths and event timing over time (include/ebcc_hip.h: ebcc_hip_spell_stats; k_spell_fold, spell_stats.hip)
+// Built as reduce_shard is: the named steps are the call the decode sees, with their labels (a step's index in the caller's
+// list where there is no `when`) and flags; the fold is ordered: a bin's steps are in step order, and the run a batch ends with
+// is in d_run when the next batch begins.
+int spell_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                const uint32_t *when, const uint8_t *fresh, size_t row0, size_t col0, const ebcc_hip_spell_stats *stats)
+{
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz, names;
+    std::vector<uint32_t> bn, wh;
+    std::vector<uint8_t> fr;
+    const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
+        if (spell_stats_named(who, (size_t) ctx->height, (size_t) ctx->width, stats, bin, when, n_frames, row0, col0) < 0) return false;
+        if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
+        for (size_t f = 0; f < n_frames; f++) {
+            const uint32_t b = bin ? bin[f] : 0u;
+            if (b == EBCC_HIP_NO_BIN) continue;
+            st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b); names.push_back(f);
+            wh.push_back(when ? when[f] : (uint32_t) f); fr.push_back(fresh && fresh[f] ? 1 : 0);
+        }
+        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = stats;
+        a.box = ebcc_hip_region{row0, col0, stats->rows, stats->cols};
+        a.parsed_first = true;
+        a.decode_mark = "spell: decode";
+        return true;
+    }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
+        spell_fold(set, decoded, k, stats->rows * stats->cols, bn.data() + lo, wh.data() + lo, fr.data() + lo, *stats);
+        pt.mark("spell: fold");
     });
     if (!rc) for (const uint32_t b : bn) stats->count[b]++;
     return rc;
@@ -2312,6 +2346,57 @@ int ebcc_hip_pair_shard(ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, cons
 {
     EBCC_API_TRY
     return pair_shard("ebcc_hip_pair_shard", ctx, x_streams, x_sizes, y_streams, y_sizes, n_steps, bin, row0, col0, stats);
+    EBCC_API_CATCH(1)
+}
+
+// ---- spell decode (spell_shard above): run lengths and event timing over time, folded on the device
+long ebcc_hip_spell_stats_check(size_t height, size_t width, const ebcc_hip_spell_stats *stats, const uint32_t *bin, const uint32_t *when,
+                                size_t n_frames, size_t row0, size_t col0)
+{
+    EBCC_API_TRY
+    return spell_stats_named("ebcc_hip_spell_stats_check", height, width, stats, bin, when, n_frames, row0, col0);
+    EBCC_API_CATCH(-1)
+}
+int ebcc_hip_spell_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_spell_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_spell_stats_init";
+    if (!ctx) { set_error("%s: bad arguments", who); return 1; }
+    if (!spell_stats_shape(who, stats)) return 1;
+    return on_device(ctx->device, 1, [&] {
+        const size_t n = stats->n_bins * stats->rows * stats->cols;
+        for (uint32_t *p : {stats->d_run, stats->d_longest, stats->d_spells, stats->d_spell_steps, stats->d_events})
+            if (p) EBCC_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(uint32_t), ctx->stream));
+        for (uint32_t *p : {stats->d_longest_end, stats->d_first, stats->d_last, stats->d_when_min, stats->d_when_max})
+            if (p) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) p, (int) EBCC_HIP_NO_STEP, n, ctx->stream));
+        if (stats->d_min) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_min, (int) 0x7F800000u, n, ctx->stream));     // +inf
+        if (stats->d_max) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max, (int) 0xFF800000u, n, ctx->stream));     // -inf
+        wait_stream(ctx->stream);
+        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_spell_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const uint32_t *when, const uint8_t *fresh,
+                        const ebcc_hip_spell_stats *stats)
+{
+    EBCC_API_TRY
+    const char *const who = "ebcc_hip_spell_fold";
+    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
+    if (spell_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, when, n_items, 0, 0) < 0) return 1;
+    return on_device(ctx->device, 1, [&] {
+        spell_fold(ctx, d_items, n_items, stats->rows * stats->cols, bin, when, fresh, *stats);
+        for (size_t k = 0; k < n_items; k++)
+            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
+        return 0;
+    });
+    EBCC_API_CATCH(1)
+}
+int ebcc_hip_spell_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                         const uint32_t *when, const uint8_t *fresh, size_t row0, size_t col0, const ebcc_hip_spell_stats *stats)
+{
+    EBCC_API_TRY
+    return spell_shard("ebcc_hip_spell_shard", ctx, streams, sizes, n_frames, bin, when, fresh, row0, col0, stats);
     EBCC_API_CATCH(1)
 }
 

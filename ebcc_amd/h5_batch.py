@@ -251,6 +251,108 @@ class PairState:
         self.close()
 
 
+class SpellStats(ctypes.Structure):
+    """ebcc_hip_spell_stats, include/ebcc_hip.h: per-pixel run, event and extreme state [n_bins][rows][cols] on the device, count on the host."""
+    _fields_ = [("n_bins", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t),
+                ("threshold", ctypes.c_float), ("below", ctypes.c_int), ("min_len", ctypes.c_uint32),
+                ("d_run", ctypes.c_void_p), ("d_longest", ctypes.c_void_p), ("d_longest_end", ctypes.c_void_p), ("d_spells", ctypes.c_void_p),
+                ("d_spell_steps", ctypes.c_void_p), ("d_events", ctypes.c_void_p), ("d_first", ctypes.c_void_p), ("d_last", ctypes.c_void_p),
+                ("d_min", ctypes.c_void_p), ("d_max", ctypes.c_void_p), ("d_when_min", ctypes.c_void_p), ("d_when_max", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
+NO_STEP = 0xFFFFFFFF                                              # EBCC_HIP_NO_STEP
+SPELL_FAMILIES = {"runs": ("run", "longest", "longest_end", "spells", "spell_steps"), "events": ("events", "first", "last"),
+                  "extremes": ("min", "max", "when_min", "when_max")}
+SPELL_LABELS = ("longest_end", "first", "last", "when_min", "when_max")
+
+
+class SpellResult:
+    """Run lengths and event timing over time, per bin and pixel, all (n_bins, rows, cols): an event is x > threshold (below:
+    x < threshold); run - the run still open after the last step -, longest - the longest run - and longest_end - the label of
+    its last step, the earliest of equal runs -, spells and spell_steps - the runs of at least min_len steps and the steps that
+    lie in them -; events, first and last - the count of events and the labels of the first and the last one -; min, max
+    (float32), when_min and when_max - the labels of the steps that first reached them.  Everything else is uint32; a label
+    nothing has set is NO_STEP.  An array that was not asked for is None.  count (n_bins,) uint64: the steps folded into each
+    bin.  masked(name): a label array as a numpy masked array, masked where it is NO_STEP."""
+    NAMES = SPELL_FAMILIES["runs"] + SPELL_FAMILIES["events"] + SPELL_FAMILIES["extremes"]
+
+    def __init__(self, count, **arrays):
+        self.count = count
+        for name in self.NAMES:
+            setattr(self, name, arrays.get(name))
+
+    def masked(self, name):
+        if name not in SPELL_LABELS:
+            raise ValueError(f"{name} is not one of the label arrays {SPELL_LABELS}")
+        a = getattr(self, name)
+        return None if a is None else np.ma.masked_equal(a, NO_STEP)
+
+
+class SpellState:
+    """The accumulators of BatchCodec.spells, resident on the device from call to call (BatchCodec.spell_state makes one): the
+    open run of every pixel is part of them.  result() downloads them, close() frees them."""
+
+    def __init__(self, codec, threshold, below, min_len, n_bins, window, what):
+        self.codec, self.n_bins, self.min_len = codec, int(n_bins), int(min_len)
+        if self.n_bins < 1:
+            raise ValueError("n_bins must be at least 1")
+        what = (what,) if isinstance(what, str) else tuple(what)
+        if not what or any(f not in SPELL_FAMILIES for f in what):
+            raise ValueError(f"what must name some of {tuple(SPELL_FAMILIES)}")
+        if np.isnan(float(threshold)) and ("runs" in what or "events" in what):
+            raise ValueError("the threshold must not be a NaN")
+        if not 0 <= self.min_len < NO_STEP:
+            raise ValueError("min_len must be a uint32")
+        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
+        row0, col0, rows, cols = self.window
+        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
+            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
+        self.shape = (self.n_bins, rows, cols)
+        self.count = np.zeros(self.n_bins, np.uint64)
+        self.stats = SpellStats(self.n_bins, rows, cols, float(threshold), 1 if below else 0, self.min_len)
+        self.stats.count = self.count.ctypes.data
+        self.fields = []
+        for family in SPELL_FAMILIES:                                   # (min_len 0: there is no spell to count)
+            if family in what:
+                self.fields += [(name, np.float32 if name in ("min", "max") else np.uint32) for name in SPELL_FAMILIES[family]
+                                if self.min_len or name not in ("spells", "spell_steps")]
+        lib = codec.lib
+        try:
+            for name, dtype in self.fields:
+                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
+                if not p:
+                    codec._fail("ebcc_hip_malloc")
+                setattr(self.stats, "d_" + name, p)
+            if lib.ebcc_hip_spell_stats_init(codec.ctx, ctypes.byref(self.stats)):
+                codec._fail("ebcc_hip_spell_stats_init")
+        except BaseException:
+            self.close()
+            raise
+
+    def result(self):
+        lib, got = self.codec.lib, {}
+        for name, dtype in self.fields:
+            a = np.empty(self.shape, dtype)
+            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, "d_" + name), a.nbytes):
+                self.codec._fail("ebcc_hip_memcpy_d2h")
+            got[name] = a
+        return SpellResult(self.count.copy(), **got)
+
+    def close(self):
+        for name, _ in self.fields:
+            p = getattr(self.stats, "d_" + name)
+            if p:
+                self.codec.lib.ebcc_hip_free(p)
+                setattr(self.stats, "d_" + name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class TimeRanks(ctypes.Structure):
     """ebcc_hip_time_ranks, include/ebcc_hip.h: the order statistics asked of every bin (host) and their planes
     [n_bins][n_ranks][rows][cols] (device), count on the host."""
@@ -631,6 +733,9 @@ class BatchCodec:
         lib.ebcc_hip_pair_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                             ctypes.POINTER(PairStats)]
+        lib.ebcc_hip_spell_stats_init.argtypes = [ctypes.c_void_p, ctypes.POINTER(SpellStats)]
+        lib.ebcc_hip_spell_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(SpellStats)]
         lib.ebcc_hip_series_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
                                               ctypes.POINTER(AreaSpec), ctypes.c_void_p]
         lib.ebcc_hip_quantile_shard.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
@@ -784,6 +889,60 @@ class BatchCodec:
             row0, col0 = state.window[:2]
             if self.lib.ebcc_hip_pair_shard(self.ctx, ptrs_x, sizes_x, ptrs_y, sizes_y, n, table.ctypes.data, row0, col0, ctypes.byref(state.stats)):
                 self._fail("ebcc_hip_pair_shard")
+            return state.result() if own else state
+        finally:
+            if own:
+                state.close()
+
+    def spell_state(self, threshold, below=False, min_len=1, n_bins=1, window=None, what=("runs", "events", "extremes")):
+        """Device-resident accumulators for spells(state=...): n_bins bins of the window (row0, col0, rows, cols) - None: the
+        whole frame - with the arrays of the families `what` names.  A SpellState; close() it when done."""
+        return SpellState(self, threshold, below, min_len, n_bins, window, what)
+
+    def spells(self, streams, threshold, below=False, min_len=1, bins=None, when=None, fresh=None, n_bins=1, window=None,
+               what=("runs", "events", "extremes"), state=None):
+        """Run lengths and event timing over time straight from the streams (ebcc_hip_spell_shard): every frame - or its
+        `window` = (row0, col0, rows, cols) - is a step, folded on the device in step order into the state of the bin `bins`
+        names for it (an integer per stream, None: all bin 0, -1: the step is skipped and not read - its entry of `streams` may
+        be None) -> a SpellResult.  A sample is an event where x > threshold (below=True: x < threshold); `when`: the label of
+        every step, a uint32 below NO_STEP (None: its index in `streams`); `fresh`: true at the first step of every visit to a
+        bin that recurs - the run does not continue from the visit before; min_len: the length from which a run is a spell (0:
+        spells are not counted); `what`: the families to compute, of "runs", "events", "extremes".  No decoded frame leaves the
+        device; the arrays are the bytes of a loop over the steps in order, whatever the engine's capacity.  `state`: a
+        SpellState (spell_state) that is continued and returned instead - threshold, below, min_len, n_bins, window and what
+        are then the state's -, so that a series walked call by call in step order gives the bytes of one call, runs that cross
+        the calls included (give `when`: the default labels start at 0 in every call).  ValueError for bins or labels the engine
+        refuses, RuntimeError for what the call reports, such as a malformed stream (the state must then be made anew)."""
+        n = len(streams)
+        own = state is None
+        if own:
+            state = SpellState(self, threshold, below, min_len, n_bins, window, what)
+        try:
+            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
+                raise ValueError(f"bins must be {n} integers, one per stream")
+            b = b.astype(np.int64)
+            if b.min() < -1 or b.max() >= state.n_bins:
+                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
+            if not (b >= 0).any():
+                raise ValueError("no step is named")
+            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            labels = None
+            if when is not None:
+                labels = np.asarray(when)
+                if labels.shape != (n,) or labels.dtype.kind not in "iu" or labels.min() < 0 or labels[b >= 0].max() >= NO_STEP or labels.max() > NO_STEP:
+                    raise ValueError(f"when must be {n} integers in [0, {NO_STEP}), one per stream")
+                labels = np.ascontiguousarray(labels, np.uint32)
+            flags = None
+            if fresh is not None:
+                flags = np.ascontiguousarray(np.asarray(fresh).astype(bool), np.uint8)
+                if flags.shape != (n,):
+                    raise ValueError(f"fresh must be {n} flags, one per stream")
+            streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.nonzero(b >= 0)[0]))
+            row0, col0 = state.window[:2]
+            if self.lib.ebcc_hip_spell_shard(self.ctx, ptrs, sizes, n, table.ctypes.data, None if labels is None else labels.ctypes.data,
+                                             None if flags is None else flags.ctypes.data, row0, col0, ctypes.byref(state.stats)):
+                self._fail("ebcc_hip_spell_shard")
             return state.result() if own else state
         finally:
             if own:
@@ -1432,6 +1591,67 @@ def pair_frames(dset_x, dset_y, bins=None, n_bins=None, rows=None, cols=None, th
                 t.start()
             try:
                 codec.pair(raw[0], raw[1], bins=b[named[lo:lo + step]], state=state)
+            finally:
+                if t:
+                    t.join()
+        return state.result()
+
+
+def spell_frames(dset, threshold, below=False, min_len=1, bins=None, when=None, fresh=None, n_bins=None, rows=None, cols=None,
+                 what=("runs", "events", "extremes"), batch=256, codec=None):
+    """Run lengths and event timing over time of an EBCC-filtered one-frame-per-chunk dataset, folded on the device
+    (BatchCodec.spells): every frame is a step, in C order of the leading axes.  `bins`, n_bins, `rows` / `cols` as in
+    reduce_frames (-1: the step is skipped, its chunk is not fetched); `when` and `fresh` are arrays shaped like the leading
+    axes - the label of every step (None: its index in C order) and the flag that begins a new visit to its bin -; threshold,
+    below, min_len and what as in BatchCodec.spells.  -> a SpellResult whose every array equals the same loop, step after step,
+    over read_frames(dset)[..., rows, cols]; no frame is downloaded.  The chunks are fetched as reduce_frames fetches them, the
+    next call's on a helper thread, and folded call after call into one device-resident state, which carries the open runs."""
+    h, w = dset.shape[-2:]
+    lead = dset.shape[:-2]
+    n = int(np.prod(lead)) if lead else 1
+    (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
+        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
+    b = b.astype(np.int64).reshape(-1)
+    named = np.nonzero(b >= 0)[0]
+    if len(named) < 1 or b.min() < -1:
+        raise ValueError("bins must name at least one step, and -1 is the only negative value")
+    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
+    if b.max() >= n_bins:
+        raise ValueError(f"a step names bin {int(b.max())} of {n_bins}")
+    labels = np.arange(n, dtype=np.int64) if when is None else np.asarray(when)
+    if labels.dtype.kind not in "iu" or labels.size != n or (when is not None and tuple(labels.shape) != tuple(lead)):
+        raise ValueError(f"when must be an integer array of shape {tuple(lead)}")
+    labels = labels.astype(np.int64).reshape(-1)
+    flags = np.zeros(n, bool) if fresh is None else np.asarray(fresh).astype(bool)
+    if flags.size != n or (fresh is not None and tuple(flags.shape) != tuple(lead)):
+        raise ValueError(f"fresh must be an array of shape {tuple(lead)}")
+    flags = flags.reshape(-1)
+    with contextlib.ExitStack() as stack:
+        codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
+        step = _SUPER * codec.max_frames
+
+        def fetch(lo, box):
+            try:
+                box.append(_read_chunks(dset, named[lo:lo + step]))
+            except BaseException as e:                              # (handed to the caller's thread)
+                box.append(e)
+
+        box = []
+        fetch(0, box)
+        state = stack.enter_context(codec.spell_state(threshold, below, min_len, n_bins, (row0, col0, nrows, ncols), what))
+        for lo in range(0, len(named), step):
+            raw = box[0]
+            if isinstance(raw, BaseException):
+                raise raw
+            box, t = [], None
+            if lo + step < len(named):
+                t = threading.Thread(target=fetch, args=(lo + step, box))
+                t.start()
+            try:
+                part = named[lo:lo + step]
+                codec.spells(raw, None, bins=b[part], when=labels[part], fresh=flags[part], state=state)
             finally:
                 if t:
                     t.join()

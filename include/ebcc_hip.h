@@ -851,6 +851,76 @@ int ebcc_hip_pair_shard(ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, cons
                         const size_t *y_sizes, size_t n_steps, const uint32_t *bin, size_t row0, size_t col0,
                         const ebcc_hip_pair_stats *stats);
 
+/* ---- spell decode: run lengths and event timing over time per pixel, from the streams, on the device ----
+ * When an event happened and how long it lasted: consecutive dry or wet days, the days that lie in warm or cold spells of at
+ * least six days, first and last frost, the onset of the growing season, the date of the annual maximum.  Streams go in,
+ * per-pixel accumulators come out; no decoded frame reaches the caller.  The reference has no counterpart.
+ * The order is the contract, as for the reduce decode.  A step carries a sample x (float), a bin, a label `when` (the caller's:
+ * a day of the year, an hour index) and a flag `fresh`.  For every bin and pixel the named steps of that bin are folded one
+ * after the other in increasing step index:
+ *   event     e = below ? (x < threshold) : (x > threshold), compared in float: a NaN sample is never an event and ends a run
+ *   runs      if (fresh) run = 0;  then run = e ? run + 1 : 0
+ *             if (run > longest) { longest = run; longest_end = when; }      strictly: among equal runs the earliest stays
+ *             if (run == min_len) { spells += 1; spell_steps += min_len; }  else if (run > min_len) spell_steps += 1
+ *   events    if (e) { events += 1;  if (first == EBCC_HIP_NO_STEP) first = when;  last = when; }
+ *   extremes  if (x > max) { max = x; when_max = when; }   if (x < min) { min = x; when_min = when; }   strictly, in float
+ * max and min start at -inf / +inf, the labels at EBCC_HIP_NO_STEP, the counters and run at 0.  -0 compares equal to +0 and +0
+ * is written, as the reduce decode does: d_min and d_max are the bytes ebcc_hip_reduce_shard gives over the same frames, and
+ * with below == 0 d_events is the bytes of its d_over.  spell_steps counts the steps that lie in runs of at least min_len; a
+ * run still open at the end of the series counts as far as it got.  `fresh` is for bins that recur - a month-of-year bin over
+ * many years -: the caller marks the first step of each visit to the bin, and the run does not continue from the visit before.
+ * The flag of a skipped step is not looked at.
+ * The state lives in the accumulators, run included: nothing else is carried from one batch or call to the next.  So the
+ * accumulators are the same bytes whatever the batch size, the engine sets, the slices, the alignment of any array, whether
+ * the frames were decoded whole or as a window, and the split of a series over several calls made in step order
+ * (ebcc_amd/csrc/spell_stats.hip: k_spell_fold; no atomics, and steps never meet in a reduction tree).
+ * Not covered: chunks of several frames, EBCK containers, a host-pointer form, events defined on two variables, the
+ * reference-compatible entry points and the filter callback. */
+#define EBCC_HIP_NO_STEP UINT32_MAX
+typedef struct {
+    size_t    n_bins, rows, cols;                 /* accumulators [n_bins][rows][cols], device, 4-byte aligned, each may be NULL */
+    float     threshold; int below; uint32_t min_len;
+    uint32_t *d_run, *d_longest, *d_longest_end, *d_spells, *d_spell_steps;   /* runs */
+    uint32_t *d_events, *d_first, *d_last;                                    /* events */
+    float    *d_min, *d_max; uint32_t *d_when_min, *d_when_max;               /* extremes */
+    uint64_t *count;                              /* host [n_bins]: steps folded into each bin */
+} ebcc_hip_spell_stats;
+/* Host only, no device (no device pointer is followed): the number of steps `bin` names (bin: host [n_frames], NULL = every
+ * step in bin 0, EBCC_HIP_NO_BIN = the step is skipped; when: host [n_frames], NULL = step f has the label f), or -1 with a
+ * message for what the calls below refuse before touching a device: what ebcc_hip_time_stats_check refuses - a null stats or a
+ * null count, every device array NULL, n_bins, rows or cols zero, a window [row0, row0 + rows) x [col0, col0 + cols) not inside
+ * the height x width frame, an array that is not 4-byte aligned, a bin >= n_bins, no step named, a geometry ebcc_hip_create
+ * refuses -, and d_longest, d_longest_end, d_spells or d_spell_steps without d_run, d_longest_end without d_longest, d_spells
+ * or d_spell_steps with min_len == 0, d_when_max without d_max or d_when_min without d_min, a NaN threshold with any runs or
+ * events array, a named step whose label is EBCC_HIP_NO_STEP. */
+long ebcc_hip_spell_stats_check(size_t height, size_t width, const ebcc_hip_spell_stats *stats, const uint32_t *bin, const uint32_t *when,
+                                size_t n_frames, size_t row0, size_t col0);
+/* counters and run = 0, the four labels, first and last = EBCC_HIP_NO_STEP, min = +inf, max = -inf, count = 0.  ctx: any
+ * context of the device.  0 = ok, 1 = error. */
+int ebcc_hip_spell_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_spell_stats *stats);
+/* unit level, the kernel alone: d_items [n_items][rows][cols] at any 4-byte aligned device address are folded in index order
+ * into the bins they name; bin, when (NULL: item k has the label k) and fresh (NULL: no item is fresh) are host arrays of
+ * n_items entries.  An item with EBCC_HIP_NO_BIN is not read, a bin no item names is not touched.  The items are never written.
+ * A call holds and executes only the families - runs, events, extremes - it has an array of.  ctx: any context of the device.
+ * Continues from what stats holds (count included).  0 = ok, 1 = error, nothing written. */
+int ebcc_hip_spell_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const uint32_t *when,
+                        const uint8_t *fresh, const ebcc_hip_spell_stats *stats);
+/* Any number of one-frame streams: the steps `bin` names are decoded - the window [row0, row0 + stats->rows) x [col0, col0 +
+ * stats->cols) by the window decode, the whole frame by the full decode when the window is the frame - in batches of the
+ * context's capacity on the two engine sets, each into its set's audit buffer, and folded.  The decodes of two batches run
+ * side by side; the folds take turns in batch order.  A skipped step is not read at all: its streams[f] may be NULL with size
+ * 0, and it takes no slot of a batch.  when == NULL: step f has the label f, its index in `streams`.  The call continues from
+ * what stats holds: a series folded by several calls in step order gives the bytes of one call, a run that crosses the cut
+ * included.
+ * Return 0 = ok, 1 = error (ebcc_hip_last_error).  Refused before anything is written, accumulators and count included: what
+ * ebcc_hip_spell_stats_check refuses for the context's frames, null stream or size arrays, a context for chunks of several
+ * frames, a named step without a stream or with one whose frame header does not parse (the message names the frame).  A stream
+ * found damaged inside a batch behaves as ebcc_hip_reduce_shard documents: the batch is refused as ebcc_hip_decode_frames
+ * refuses it, earlier batches may have folded - the accumulators then hold an unspecified mixture and must be initialised
+ * again -, and count is only advanced by a call that succeeds. */
+int ebcc_hip_spell_shard(ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
+                         const uint32_t *when, const uint8_t *fresh, size_t row0, size_t col0, const ebcc_hip_spell_stats *stats);
+
 /* Direct-chunk batch path for C callers (netCDF-C / CDO-style pipelines; ebcc_amd/h5_batch.py is the Python form): a dataset
  * whose chunks are single frames - chunk dims (1, ..., 1, H, W), filter 308 as /root/reference/src/h5z_ebcc.c:38-93 reads it -
  * is written / read in device batches instead of one filter callback per chunk (/root/reference/src/h5z_ebcc.c:124-148 is
@@ -891,7 +961,7 @@ void ebcc_hip_plan_decode_lanes(const int *table, int n_code_blocks, int out[4])
 
 /* Per-kernel timing with HIP events on the engine's stream (bench.py roofline leg).  Names: "t1_encode",
  * "t1_probe_decode", "t1_decode", "rate_alloc", "j2k_dwt_fwd", "spiht_encode", "frame_errors", "time_fold", "regrid", "rank_count",
- * "rank_advance", "time_map", "pair_fold".  Process-wide switch. */
+ * "rank_advance", "time_map", "pair_fold", "spell_fold".  Process-wide switch. */
 void ebcc_hip_timing_enable(ebcc_hip_ctx *ctx, int on);
 int ebcc_hip_timing_read(ebcc_hip_ctx *ctx, const char *name, double *total_ms, long *launches);
 

@@ -10,6 +10,7 @@
 #   tools/vgpr.sh 'rank'                                   the count and the advance of the quantile decode's radix select (quantile.hip)
 #   tools/vgpr.sh 'time_map'                               the two instances of the time-map decode's kernel (time_map.hip)
 #   tools/vgpr.sh 'pair_fold'                              the three instances of the pair decode's kernel (pair_stats.hip)
+#   tools/vgpr.sh 'spell_fold'                             the seven instances of the spell decode's kernel (spell_stats.hip)
 # Compiled with the Makefile's code-generation flags; run it at two commits to compare their register use.
 pat="${1:-t1_}"
 cd "$(dirname "$0")/../ebcc_amd/csrc"
@@ -18,7 +19,7 @@ filt="$(dirname "$HIPCC")/../llvm/bin/llvm-cxxfilt"
 [ -x "$filt" ] || filt=c++filt
 tmp=$(mktemp -d)
 trap 'rm -rf "$tmp"' EXIT
-for f in j2k_analysis j2k_rate residual_dwt array_stats regrid quantile time_map pair_stats; do
+for f in j2k_analysis j2k_rate residual_dwt array_stats regrid quantile time_map pair_stats spell_stats; do
   "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -I../../include -S --cuda-device-only -o "$tmp/$f.s" $f.hip 2>/dev/null
   awk '/\.name:/{n=$2} /\.vgpr_count:/{v=$2} /\.sgpr_count:/{s=$2} /\.private_segment_fixed_size:/{p=$2} /\.vgpr_spill_count:/{print n, v, s, p, $2}' "$tmp/$f.s" |
   while read -r n v s p sp; do
