@@ -5,6 +5,7 @@
 // chain.  The comments that state an order rule are the specification the tests check.
 #include <climits>
 #include "array_stats.hpp"
+#include "time_walk.hpp"
 
 namespace ebcc {
 
@@ -308,108 +309,61 @@ int frame_errors(ebcc_hip_ctx *ctx, const float *d_x, const float *d_d, size_t n
 // folded into the accumulators [n_bins][n_pix] of their bins.  A lane owns pixels and walks the list from its first entry to its
 // last, one item after the other: acc = acc + x, nothing else ever adds to a sample's accumulators, so for every bin and pixel
 // the order of the additions is the order of the list - frames never meet in a reduction tree, and there are no atomics.  The
-// lane keeps the current bin's accumulators in registers, writes them back and loads the other bin's only when the bin
-// changes; time_fold hands over the list grouped by bin (a stable sort: within a bin still in increasing item index, which is
-// all the order rule fixes), so a batch costs one load and one store of every bin it names.
-// A lane takes a quad (pixels 4q .. 4q + 3): one 16-byte load from an item that begins on a 16-byte boundary, four 4-byte loads
-// from one that does not, four items in flight; the accumulators of a bin the same way, each array on its own.  Quads count
-// from the item's first pixel, not from an address, and the last n_pix % 4 pixels go one to a lane - but which lane adds a
-// sample does not matter here: the additions of a pixel are one lane's, in list order, wherever the arrays lie.
+// walk is time_walk.hpp's: the lane keeps the current bin's accumulators in registers, writes them back and loads the other
+// bin's only when the bin changes; time_fold hands over the list grouped by bin (a stable sort: within a bin still in
+// increasing item index, which is all the order rule fixes), so a batch costs one load and one store of every bin it names.
+// A quad is one 16-byte load from an item that begins on a 16-byte boundary, four 4-byte loads from one that does not, four
+// items in flight; the accumulators of a bin the same way, each array on its own.  Which lane adds a sample does not matter
+// here: the additions of a pixel are one lane's, in list order, wherever the arrays lie.  An accumulator that is NULL is neither
+// loaded nor stored; min and max then start at 0, and -0 leaves as +0 in every store.
 namespace {
 struct FoldAcc { double *sum, *sum_sq; float *mn, *mx; unsigned *over; float threshold; };
 struct FoldEntry { unsigned item, bin; };
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <class T> struct Vec16;                                   // the 16-byte vector of T
-template <> struct Vec16<double> { typedef f64x2 type; };
-template <> struct Vec16<float> { typedef f32x4 type; };
-template <> struct Vec16<unsigned> { typedef u32x4 type; };
-// W samples at p: as 16-byte accesses where W == 4 and p is on a 16-byte boundary (the same answer in every lane of a
-// workgroup's quads: they lie whole quads apart), else one by one
-template <class T, int W> __device__ inline void fold_get(const T *p, T (&r)[W])
-{
-    typedef typename Vec16<T>::type V;
-    constexpr int per = 16 / sizeof(T);
-    if constexpr (W == 4) {
-        if (((uintptr_t) p & 15) == 0) {
+struct TimeFold {
+    typedef FoldEntry Entry;
+    template <int W> struct Lane {
+        typedef FoldEntry Entry;
+        struct Items { float x[W]; };
+        const size_t n_pix, p0;
+        const float *__restrict__ items;
+        const FoldAcc &a;
+        double s[W], s2[W];
+        float lo[W], hi[W];
+        unsigned ov[W], cur = walk::kNone;
+        __device__ __forceinline__ Lane(size_t n_pix_, size_t p0_, const float *items_, const FoldAcc &a_) : n_pix(n_pix_), p0(p0_), items(items_), a(a_)
+        {
 #pragma unroll
-            for (int v = 0; v < W / per; v++) {
-                const V q = reinterpret_cast<const V *>(p)[v];
-#pragma unroll
-                for (int i = 0; i < per; i++) r[v * per + i] = q[i];
-            }
-            return;
+            for (int i = 0; i < W; i++) { s[i] = 0.0; s2[i] = 0.0; lo[i] = 0.0f; hi[i] = 0.0f; ov[i] = 0u; }
         }
-    }
-#pragma unroll
-    for (int i = 0; i < W; i++) r[i] = p[i];
-}
-template <class T, int W> __device__ inline void fold_put(T *p, const T (&r)[W])
-{
-    typedef typename Vec16<T>::type V;
-    constexpr int per = 16 / sizeof(T);
-    if constexpr (W == 4) {
-        if (((uintptr_t) p & 15) == 0) {
-#pragma unroll
-            for (int v = 0; v < W / per; v++) {
-                V q;
-#pragma unroll
-                for (int i = 0; i < per; i++) q[i] = r[v * per + i];
-                reinterpret_cast<V *>(p)[v] = q;
-            }
-            return;
+        __device__ __forceinline__ void load(const Entry &e, Items &it) const { walk::get<float, W>(items + (size_t) e.item * n_pix + p0, it.x); }
+        __device__ __forceinline__ bool changed(const Entry &e) const { return e.bin != cur; }
+        __device__ __forceinline__ bool held() const { return cur != walk::kNone; }
+        __device__ __forceinline__ void get(const Entry &e)
+        {
+            const size_t at = (size_t) e.bin * n_pix + p0;
+            if (a.sum) walk::get<double, W>(a.sum + at, s);
+            if (a.sum_sq) walk::get<double, W>(a.sum_sq + at, s2);
+            if (a.mn) walk::get<float, W>(a.mn + at, lo);
+            if (a.mx) walk::get<float, W>(a.mx + at, hi);
+            if (a.over) walk::get<unsigned, W>(a.over + at, ov);
+            cur = e.bin;
         }
-    }
+        __device__ __forceinline__ void put()
+        {
+            const size_t at = (size_t) cur * n_pix + p0;
 #pragma unroll
-    for (int i = 0; i < W; i++) p[i] = r[i];
-}
-// the pixels p0 .. p0 + W - 1 through the list
-template <int W>
-__device__ inline void time_fold_pixels(const float *__restrict__ items, size_t n_pix, size_t p0, const FoldEntry *__restrict__ list, unsigned m, const FoldAcc &a)
-{
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    constexpr int kDepth = 4;                                       // items in flight
-    double s[W], s2[W];
-    float lo[W], hi[W];
-    unsigned ov[W];
-#pragma unroll
-    for (int i = 0; i < W; i++) { s[i] = 0.0; s2[i] = 0.0; lo[i] = 0.0f; hi[i] = 0.0f; ov[i] = 0u; }
-    unsigned cur = kNone;
-    auto get = [&](unsigned b) {
-        const size_t at = (size_t) b * n_pix + p0;
-        if (a.sum) fold_get<double, W>(a.sum + at, s);
-        if (a.sum_sq) fold_get<double, W>(a.sum_sq + at, s2);
-        if (a.mn) fold_get<float, W>(a.mn + at, lo);
-        if (a.mx) fold_get<float, W>(a.mx + at, hi);
-        if (a.over) fold_get<unsigned, W>(a.over + at, ov);
-    };
-    auto put = [&](unsigned b) {
-        const size_t at = (size_t) b * n_pix + p0;
-#pragma unroll
-        for (int i = 0; i < W; i++) { lo[i] = lo[i] + 0.0f; hi[i] = hi[i] + 0.0f; }      // (-0 -> +0)
-        if (a.sum) fold_put<double, W>(a.sum + at, s);
-        if (a.sum_sq) fold_put<double, W>(a.sum_sq + at, s2);
-        if (a.mn) fold_put<float, W>(a.mn + at, lo);
-        if (a.mx) fold_put<float, W>(a.mx + at, hi);
-        if (a.over) fold_put<unsigned, W>(a.over + at, ov);
-    };
-    for (unsigned j0 = 0; j0 < m; j0 += kDepth) {
-        float x[kDepth][W];
-#pragma unroll
-        for (int j = 0; j < kDepth; j++)
-            if (j0 + j < m) fold_get<float, W>(items + (size_t) list[j0 + j].item * n_pix + p0, x[j]);
-#pragma unroll
-        for (int j = 0; j < kDepth; j++) {
-            if (j0 + j >= m) break;
-            const unsigned b = list[j0 + j].bin;
-            if (b != cur) {
-                if (cur != kNone) put(cur);
-                get(b);
-                cur = b;
-            }
+            for (int i = 0; i < W; i++) { lo[i] = lo[i] + 0.0f; hi[i] = hi[i] + 0.0f; }      // (-0 -> +0)
+            if (a.sum) walk::put<double, W>(a.sum + at, s);
+            if (a.sum_sq) walk::put<double, W>(a.sum_sq + at, s2);
+            if (a.mn) walk::put<float, W>(a.mn + at, lo);
+            if (a.mx) walk::put<float, W>(a.mx + at, hi);
+            if (a.over) walk::put<unsigned, W>(a.over + at, ov);
+        }
+        __device__ __forceinline__ void step(const Entry &, const Items &it)
+        {
 #pragma unroll
             for (int i = 0; i < W; i++) {
-                const float v = x[j][i];
+                const float v = it.x[i];
                 const double d = (double) v;
                 s[i] = s[i] + d;
                 s2[i] = s2[i] + d * d;
@@ -418,43 +372,24 @@ __device__ inline void time_fold_pixels(const float *__restrict__ items, size_t 
                 ov[i] += v > a.threshold ? 1u : 0u;
             }
         }
-    }
-    if (cur != kNone) put(cur);
-}
-// a lane per quad of an item, then a lane per pixel of the last n_pix % 4
+    };
+};
 __global__ __launch_bounds__(256) void k_time_fold(const float *__restrict__ items, size_t n_pix, const FoldEntry *__restrict__ list, unsigned m, FoldAcc a)
 {
-    const size_t u = (size_t) blockIdx.x * blockDim.x + threadIdx.x, n4 = n_pix >> 2;
-    if (u < n4) time_fold_pixels<4>(items, n_pix, 4 * u, list, m, a);
-    else if (u - n4 < (n_pix & 3)) time_fold_pixels<1>(items, n_pix, 4 * n4 + (u - n4), list, m, a);
+    walk::lanes<TimeFold>(n_pix, list, m, items, a);
 }
 }  // namespace
 // The items of d_items [n][n_pix] (device, any 4-byte alignment) that `bin` names (host, null: all bin 0; EBCC_HIP_NO_BIN: the
-// item is not read) folded into st's accumulators, in index order within every bin.  The list goes up through the context's
-// pinned table (boxes_reserve), launches of at most kList entries follow one another on ctx's stream, which is waited for.
+// item is not read) folded into st's accumulators, in index order within every bin (binned_list, walk_list: time_walk.hpp).
 // st.count is the caller's.  Device current, the context the caller's alone, st checked (time_stats_named).
 void time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n, size_t n_pix, const uint32_t *bin, const ebcc_hip_time_stats &st)
 {
-    constexpr size_t kList = 65536;
-    std::vector<FoldEntry> list;
-    list.reserve(n);
-    for (size_t k = 0; k < n; k++)
-        if (!bin || bin[k] != EBCC_HIP_NO_BIN) list.push_back(FoldEntry{(unsigned) k, bin ? bin[k] : 0u});
+    const auto list = binned_list<FoldEntry>(n, bin, [](size_t k, uint32_t b) { return FoldEntry{(unsigned) k, b}; });
     if (list.empty()) return;
-    std::stable_sort(list.begin(), list.end(), [](const FoldEntry &p, const FoldEntry &q) { return p.bin < q.bin; });
-    boxes_reserve(ctx, list.size(), sizeof(FoldEntry));
-    memcpy(ctx->boxes.h, list.data(), list.size() * sizeof(FoldEntry));
-    EBCC_HIP_CHECK(hipMemcpyAsync(ctx->boxes.d, ctx->boxes.h, list.size() * sizeof(FoldEntry), hipMemcpyHostToDevice, ctx->stream));
     const FoldAcc a{st.d_sum, st.d_sum_sq, st.d_min, st.d_max, st.d_over, st.threshold};
-    const size_t lanes = (n_pix >> 2) + (n_pix & 3);
-    {
-        ScopedTiming timing("time_fold", ctx->stream);
-        for (size_t lo = 0; lo < list.size(); lo += kList)
-            hipLaunchKernelGGL(k_time_fold, dim3((unsigned) ((lanes + 255) / 256)), dim3(256), 0, ctx->stream, d_items, n_pix,
-                               (const FoldEntry *) ctx->boxes.d + lo, (unsigned) std::min(kList, list.size() - lo), a);
-    }
-    EBCC_HIP_LAUNCH_CHECK();
-    wait_stream(ctx->stream);
+    walk_list(ctx, "time_fold", list, [&](const FoldEntry *d_list, unsigned m, size_t) {
+        hipLaunchKernelGGL(k_time_fold, walk::grid(n_pix), dim3(256), 0, ctx->stream, d_items, n_pix, d_list, m, a);
+    });
 }
 
 // Area statistics per item (include/ebcc_hip.h: ebcc_hip_area_stat, and the order rule stated there): the weighted sums, the
@@ -685,30 +620,13 @@ bool time_stats_shape(const char *who, const ebcc_hip_time_stats *st)
         set_error("%s: d_min, d_max and d_over must be 4-byte aligned", who);
         return false;
     }
-    size_t bytes = 0;
-    if (__builtin_mul_overflow(st->rows, st->cols, &bytes) || __builtin_mul_overflow(bytes, st->n_bins, &bytes) ||
-        __builtin_mul_overflow(bytes, sizeof(double), &bytes)) { set_error("%s: the size of the accumulators overflows", who); return false; }
-    return true;
+    return accumulator_bytes_checked(who, st->rows, st->cols, st->n_bins, sizeof(double));
 }
 long time_stats_named(const char *who, size_t height, size_t width, const ebcc_hip_time_stats *st, const uint32_t *bin, size_t n_frames,
                       size_t row0, size_t col0)
 {
-    if (!time_stats_shape(who, st)) return -1;
-    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("%s: unsupported geometry %zu x %zu", who, height, width); return -1; }
-    if (row0 >= height || col0 >= width || st->rows > height - row0 || st->cols > width - col0) {
-        set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is not inside the %zu x %zu frame", who, row0, st->rows, col0, st->cols, height, width);
-        return -1;
-    }
-    if (n_frames > (size_t) LONG_MAX) { set_error("%s: too many frames", who); return -1; }
-    size_t named = 0;
-    for (size_t f = 0; f < n_frames; f++) {
-        const uint32_t b = bin ? bin[f] : 0u;
-        if (b == EBCC_HIP_NO_BIN) continue;
-        if (b >= st->n_bins) { set_error("%s: frame %zu names bin %u of %zu", who, f, b, st->n_bins); return -1; }
-        named++;
-    }
-    if (!named) { set_error("%s: no frame is named", who); return -1; }
-    return (long) named;
+    if (!time_stats_shape(who, st) || !frame_window_checked(who, height, width, row0, col0, st->rows, st->cols)) return -1;
+    return bins_named(who, "frame", n_frames, bin, st->n_bins);
 }
 
 }  // namespace ebcc

@@ -12,6 +12,8 @@
 //   time_map.hip     the time-map decode: check, list of a batch, kernel and launcher of the weighted sums over time (time_map.hpp)
 //   pair_stats.hip   the pair decode: check, kernel and launcher of the co-moments and vector magnitude of two variables (pair_stats.hpp)
 //   spell_stats.hip  the spell decode: check, kernel and launcher of the run lengths and event timing over time (spell_stats.hpp)
+//   time_walk.hpp    what the decodes over time share (the five files above, from the fold over time on): a lane's walk through
+//                    a list on the device, the list built, sent up and walked in launches, the checks of frame, window and bins
 //   h5z_filter.hip   the HDF5 filter plugin (id 308) of /root/reference/src/h5z_ebcc.c
 #pragma once
 

@@ -12,6 +12,7 @@
 #include "time_map.hpp"
 #include "pair_stats.hpp"
 #include "spell_stats.hpp"
+#include "time_walk.hpp"
 
 using namespace ebcc;
 
@@ -1166,32 +1167,50 @@ int audit(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, con
     return rc;
 }
 
+// ---- the named steps of a binned call, as the decode sees them: streams and sizes (one to a step, or an x and a y), the step's
+// number in the caller's list and its bin.  per_step(t, bin) adds the streams of step t and what else the consumer keeps of it
+// -> 1, or 0: the step is left out, or -1: refused, the message set.
+struct NamedSteps {
+    std::vector<const uint8_t *> st;
+    std::vector<size_t> sz, names;
+    std::vector<uint32_t> bn;
+    void add(const uint8_t *stream, size_t size) { st.push_back(stream); sz.push_back(size); }
+    template <class PerStep> bool fill(size_t n, const uint32_t *bin, PerStep per_step)
+    {
+        for (size_t t = 0; t < n; t++) {
+            const uint32_t b = bin ? bin[t] : 0u;
+            if (b == EBCC_HIP_NO_BIN) continue;
+            const int taken = per_step(t, b);
+            if (taken < 0) return false;
+            if (taken) { bn.push_back(b); names.push_back(t); }
+        }
+        return true;
+    }
+    void ask(DecodedAsk &a) const { a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); }
+    void add_counts(uint64_t *count) const { for (const uint32_t b : bn) count[b]++; }
+};
+
 // ---- reduce decode: statistics over time from the streams (include/ebcc_hip.h: ebcc_hip_time_stats; k_time_fold, array_stats.hip)
 // The named frames are the call the decode sees; the fold is ordered: a bin's additions are in frame order.
 int reduce_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
                  size_t row0, size_t col0, const ebcc_hip_time_stats *stats)
 {
-    std::vector<const uint8_t *> st;
-    std::vector<size_t> sz, names;
-    std::vector<uint32_t> bn;
+    NamedSteps ns;
     const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
         if (time_stats_named(who, (size_t) ctx->height, (size_t) ctx->width, stats, bin, n_frames, row0, col0) < 0) return false;
         if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
-        for (size_t f = 0; f < n_frames; f++) {
-            const uint32_t b = bin ? bin[f] : 0u;
-            if (b == EBCC_HIP_NO_BIN) continue;
-            st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b); names.push_back(f);
-        }
-        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = stats;
+        ns.fill(n_frames, bin, [&](size_t f, uint32_t) { ns.add(streams[f], sizes[f]); return 1; });
+        ns.ask(a);
+        a.names = ns.names.data(); a.out = stats;
         a.box = ebcc_hip_region{row0, col0, stats->rows, stats->cols};
         a.parsed_first = true;
         a.decode_mark = "reduce: decode";
         return true;
     }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
-        time_fold(set, decoded, k, stats->rows * stats->cols, bn.data() + lo, *stats);
+        time_fold(set, decoded, k, stats->rows * stats->cols, ns.bn.data() + lo, *stats);
         pt.mark("reduce: fold");
     });
-    if (!rc) for (const uint32_t b : bn) stats->count[b]++;
+    if (!rc) ns.add_counts(stats->count);
     return rc;
 }
 
@@ -1272,9 +1291,7 @@ int quantile_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *str
                    size_t row0, size_t col0, const ebcc_hip_time_ranks *spec)
 {
     if (!ctx) { set_error("%s: bad arguments", who); return 1; }
-    std::vector<const uint8_t *> st;
-    std::vector<size_t> sz, names;
-    std::vector<uint32_t> bn;
+    NamedSteps ns;
     RankPlan plan;
     return on_codec(ctx->device, 1, [&] {
         for (int pass = 0; pass < kRankPasses; pass++) {
@@ -1282,20 +1299,21 @@ int quantile_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *str
                 if (pass == 0) {
                     if (time_ranks_named(who, (size_t) ctx->height, (size_t) ctx->width, spec, bin, n_frames, row0, col0, &plan) < 0) return false;
                     if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
-                    for (size_t f = 0; f < n_frames; f++) {
-                        const uint32_t b = bin ? bin[f] : 0u;
-                        if (b == EBCC_HIP_NO_BIN || !plan.mask[b]) continue;
-                        st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b); names.push_back(f);
-                    }
+                    ns.fill(n_frames, bin, [&](size_t f, uint32_t b) {
+                        if (!plan.mask[b]) return 0;
+                        ns.add(streams[f], sizes[f]);
+                        return 1;
+                    });
                     a.parsed_first = true;
                     a.ready = [&] { rank_begin(ctx, plan); return true; };
                 }
-                a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = spec;
+                ns.ask(a);
+                a.names = ns.names.data(); a.out = spec;
                 a.box = ebcc_hip_region{row0, col0, spec->rows, spec->cols};
                 a.decode_mark = "quantile: decode";
                 return true;
             }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
-                rank_count(set, plan, decoded, k, bn.data() + lo, pass);
+                rank_count(set, plan, decoded, k, ns.bn.data() + lo, pass);
                 pt.mark("quantile: count");
             }, true);
             if (rc) return rc;
@@ -1345,33 +1363,31 @@ int project_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *stre
 int pair_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *x_streams, const size_t *x_sizes, const uint8_t *const *y_streams,
                const size_t *y_sizes, size_t n_steps, const uint32_t *bin, size_t row0, size_t col0, const ebcc_hip_pair_stats *stats)
 {
-    std::vector<const uint8_t *> st;
-    std::vector<size_t> sz;
-    std::vector<uint32_t> bn;
+    NamedSteps ns;
     const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
         if (pair_stats_named(who, (size_t) ctx->height, (size_t) ctx->width, stats, bin, n_steps, row0, col0) < 0) return false;
         if (!x_streams || !x_sizes || !y_streams || !y_sizes) { set_error("%s: bad arguments", who); return false; }
         if (ctx->max_frames < 2) { set_error("%s: a context of capacity 1 cannot hold the two frames of a step", who); return false; }
-        for (size_t t = 0; t < n_steps; t++) {
-            const uint32_t b = bin ? bin[t] : 0u;
-            if (b == EBCC_HIP_NO_BIN) continue;
+        const bool parsed = ns.fill(n_steps, bin, [&](size_t t, uint32_t) {
             ParsedFrame pf;
-            if (!x_streams[t] || !parse_frame(x_streams[t], x_sizes[t], pf)) { set_error("%s: step %zu: x is not a frame stream", who, t); return false; }
-            if (!y_streams[t] || !parse_frame(y_streams[t], y_sizes[t], pf)) { set_error("%s: step %zu: y is not a frame stream", who, t); return false; }
-            st.push_back(x_streams[t]); sz.push_back(x_sizes[t]);
-            st.push_back(y_streams[t]); sz.push_back(y_sizes[t]);
-            bn.push_back(b);
-        }
-        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.out = stats;
+            if (!x_streams[t] || !parse_frame(x_streams[t], x_sizes[t], pf)) { set_error("%s: step %zu: x is not a frame stream", who, t); return -1; }
+            if (!y_streams[t] || !parse_frame(y_streams[t], y_sizes[t], pf)) { set_error("%s: step %zu: y is not a frame stream", who, t); return -1; }
+            ns.add(x_streams[t], x_sizes[t]);
+            ns.add(y_streams[t], y_sizes[t]);
+            return 1;
+        });
+        if (!parsed) return false;
+        ns.ask(a);
+        a.out = stats;
         a.box = ebcc_hip_region{row0, col0, stats->rows, stats->cols};
         a.granule = 2;
         a.decode_mark = "pair: decode";
         return true;
     }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
-        pair_fold(set, decoded, decoded, true, k / 2, stats->rows * stats->cols, bn.data() + lo / 2, *stats);
+        pair_fold(set, decoded, decoded, true, k / 2, stats->rows * stats->cols, ns.bn.data() + lo / 2, *stats);
         pt.mark("pair: fold");
     });
-    if (!rc) for (const uint32_t b : bn) stats->count[b]++;
+    if (!rc) ns.add_counts(stats->count);
     return rc;
 }
 
@@ -1382,29 +1398,28 @@ int pair_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *x_strea
 int spell_shard(const char *who, ebcc_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, size_t n_frames, const uint32_t *bin,
                 const uint32_t *when, const uint8_t *fresh, size_t row0, size_t col0, const ebcc_hip_spell_stats *stats)
 {
-    std::vector<const uint8_t *> st;
-    std::vector<size_t> sz, names;
-    std::vector<uint32_t> bn, wh;
+    NamedSteps ns;
+    std::vector<uint32_t> wh;
     std::vector<uint8_t> fr;
     const int rc = consume_decoded(who, ctx, false, true, [&](DecodedAsk &a) {
         if (spell_stats_named(who, (size_t) ctx->height, (size_t) ctx->width, stats, bin, when, n_frames, row0, col0) < 0) return false;
         if (!streams || !sizes) { set_error("%s: bad arguments", who); return false; }
-        for (size_t f = 0; f < n_frames; f++) {
-            const uint32_t b = bin ? bin[f] : 0u;
-            if (b == EBCC_HIP_NO_BIN) continue;
-            st.push_back(streams[f]); sz.push_back(sizes[f]); bn.push_back(b); names.push_back(f);
+        ns.fill(n_frames, bin, [&](size_t f, uint32_t) {
+            ns.add(streams[f], sizes[f]);
             wh.push_back(when ? when[f] : (uint32_t) f); fr.push_back(fresh && fresh[f] ? 1 : 0);
-        }
-        a.streams = st.data(); a.sizes = sz.data(); a.n = st.size(); a.names = names.data(); a.out = stats;
+            return 1;
+        });
+        ns.ask(a);
+        a.names = ns.names.data(); a.out = stats;
         a.box = ebcc_hip_region{row0, col0, stats->rows, stats->cols};
         a.parsed_first = true;
         a.decode_mark = "spell: decode";
         return true;
     }, [&](ebcc_hip_ctx *set, const float *decoded, size_t lo, size_t k, PhaseTimer &pt) {
-        spell_fold(set, decoded, k, stats->rows * stats->cols, bn.data() + lo, wh.data() + lo, fr.data() + lo, *stats);
+        spell_fold(set, decoded, k, stats->rows * stats->cols, ns.bn.data() + lo, wh.data() + lo, fr.data() + lo, *stats);
         pt.mark("spell: fold");
     });
-    if (!rc) for (const uint32_t b : bn) stats->count[b]++;
+    if (!rc) ns.add_counts(stats->count);
     return rc;
 }
 
@@ -1595,6 +1610,42 @@ int encode_array_chunks(const char *who, ebcc_hip_ctx *ctx, const float *d_array
             return (const float *) d;
         });
     });
+}
+
+// ---- what the entry points of the decodes over time share
+// <x>_init: every array of `fills` that is there set to n elements of its start value - zero bytes, or a 32-bit word (elements of
+// 4 bytes) - on the context's stream, which is waited for; then count[0 .. n_count) = 0.
+struct StartValue { void *d; size_t elem; uint32_t word; };
+constexpr uint32_t kPlusInf = 0x7F800000u, kMinusInf = 0xFF800000u;
+int start_values(ebcc_hip_ctx *ctx, std::initializer_list<StartValue> fills, size_t n, uint64_t *count, size_t n_count)
+{
+    return on_device(ctx->device, 1, [&] {
+        for (const StartValue &f : fills) {
+            if (!f.d) continue;
+            if (f.word) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) f.d, (int) f.word, n, ctx->stream));
+            else EBCC_HIP_CHECK(hipMemsetAsync(f.d, 0, n * f.elem, ctx->stream));
+        }
+        wait_stream(ctx->stream);
+        std::fill_n(count, n_count, (uint64_t) 0);
+        return 0;
+    });
+}
+// <x>_fold / <x>_items: the refusal of the context and of the item arrays, check() (< 0: refused, the message set), then body()
+// on the context's device.
+template <class Check, class Body>
+int items_call(const char *who, ebcc_hip_ctx *ctx, std::initializer_list<const float *> items, size_t n_items, Check check, Body body)
+{
+    bool bad = !ctx || n_items >= 0xFFFFFFFFu;
+    for (const float *p : items) bad = bad || !p || ((uintptr_t) p & 3);
+    if (bad) { set_error("%s: bad arguments", who); return 1; }
+    if (check() < 0) return 1;
+    return on_device(ctx->device, 1, [&] { body(); return 0; });
+}
+// count[bin] += 1 for every item that `bin` names
+void count_named(size_t n, const uint32_t *bin, uint64_t *count)
+{
+    for (size_t k = 0; k < n; k++)
+        if (!bin || bin[k] != EBCC_HIP_NO_BIN) count[bin ? bin[k] : 0u]++;
 }
 
 }  // namespace
@@ -2152,30 +2203,17 @@ int ebcc_hip_time_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_stats *stats
     const char *const who = "ebcc_hip_time_stats_init";
     if (!ctx) { set_error("%s: bad arguments", who); return 1; }
     if (!time_stats_shape(who, stats)) return 1;
-    return on_device(ctx->device, 1, [&] {
-        const size_t n = stats->n_bins * stats->rows * stats->cols;
-        if (stats->d_sum) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_sum, 0, n * sizeof(double), ctx->stream));
-        if (stats->d_sum_sq) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_sum_sq, 0, n * sizeof(double), ctx->stream));
-        if (stats->d_over) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_over, 0, n * sizeof(uint32_t), ctx->stream));
-        if (stats->d_min) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_min, (int) 0x7F800000u, n, ctx->stream));     // +inf
-        if (stats->d_max) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max, (int) 0xFF800000u, n, ctx->stream));     // -inf
-        wait_stream(ctx->stream);
-        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
-        return 0;
-    });
+    return start_values(ctx, {{stats->d_sum, 8, 0}, {stats->d_sum_sq, 8, 0}, {stats->d_over, 4, 0}, {stats->d_min, 4, kPlusInf}, {stats->d_max, 4, kMinusInf}},
+                        stats->n_bins * stats->rows * stats->cols, stats->count, stats->n_bins);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_time_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const ebcc_hip_time_stats *stats)
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_time_fold";
-    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
-    if (time_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0) < 0) return 1;
-    return on_device(ctx->device, 1, [&] {
+    return items_call(who, ctx, {d_items}, n_items, [&] { return time_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0); }, [&] {
         time_fold(ctx, d_items, n_items, stats->rows * stats->cols, bin, *stats);
-        for (size_t k = 0; k < n_items; k++)
-            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
-        return 0;
+        count_named(n_items, bin, stats->count);
     });
     EBCC_API_CATCH(1)
 }
@@ -2275,17 +2313,14 @@ int ebcc_hip_rank_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items,
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_rank_items";
-    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
     RankPlan plan;
-    if (time_ranks_named(who, spec ? spec->rows : 0, spec ? spec->cols : 0, spec, bin, n_items, 0, 0, &plan) < 0) return 1;
-    return on_device(ctx->device, 1, [&] {
+    return items_call(who, ctx, {d_items}, n_items, [&] { return time_ranks_named(who, spec ? spec->rows : 0, spec ? spec->cols : 0, spec, bin, n_items, 0, 0, &plan); }, [&] {
         rank_begin(ctx, plan);
         for (int pass = 0; pass < kRankPasses; pass++) {
             rank_count(ctx, plan, d_items, n_items, bin, pass);
             rank_advance(ctx, plan, pass, spec->d_out);
         }
         std::copy(plan.count.begin(), plan.count.end(), spec->count);
-        return 0;
     });
     EBCC_API_CATCH(1)
 }
@@ -2311,16 +2346,9 @@ int ebcc_hip_pair_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_pair_stats *stats
     const char *const who = "ebcc_hip_pair_stats_init";
     if (!ctx) { set_error("%s: bad arguments", who); return 1; }
     if (!pair_stats_shape(who, stats)) return 1;
-    return on_device(ctx->device, 1, [&] {
-        const size_t n = stats->n_bins * stats->rows * stats->cols;
-        for (double *p : {stats->d_sum_x, stats->d_sum_y, stats->d_sum_xx, stats->d_sum_yy, stats->d_sum_xy, stats->d_sum_mag})
-            if (p) EBCC_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(double), ctx->stream));
-        if (stats->d_over_mag) EBCC_HIP_CHECK(hipMemsetAsync(stats->d_over_mag, 0, n * sizeof(uint32_t), ctx->stream));
-        if (stats->d_max_mag) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max_mag, (int) 0xFF800000u, n, ctx->stream));     // -inf
-        wait_stream(ctx->stream);
-        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
-        return 0;
-    });
+    return start_values(ctx, {{stats->d_sum_x, 8, 0}, {stats->d_sum_y, 8, 0}, {stats->d_sum_xx, 8, 0}, {stats->d_sum_yy, 8, 0}, {stats->d_sum_xy, 8, 0},
+                              {stats->d_sum_mag, 8, 0}, {stats->d_over_mag, 4, 0}, {stats->d_max_mag, 4, kMinusInf}},
+                        stats->n_bins * stats->rows * stats->cols, stats->count, stats->n_bins);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_pair_fold(ebcc_hip_ctx *ctx, const float *d_x_items, const float *d_y_items, size_t n_items, const uint32_t *bin,
@@ -2328,16 +2356,9 @@ int ebcc_hip_pair_fold(ebcc_hip_ctx *ctx, const float *d_x_items, const float *d
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_pair_fold";
-    if (!ctx || !d_x_items || !d_y_items || ((uintptr_t) d_x_items & 3) || ((uintptr_t) d_y_items & 3) || n_items >= 0xFFFFFFFFu) {
-        set_error("%s: bad arguments", who);
-        return 1;
-    }
-    if (pair_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0) < 0) return 1;
-    return on_device(ctx->device, 1, [&] {
+    return items_call(who, ctx, {d_x_items, d_y_items}, n_items, [&] { return pair_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, n_items, 0, 0); }, [&] {
         pair_fold(ctx, d_x_items, d_y_items, false, n_items, stats->rows * stats->cols, bin, *stats);
-        for (size_t k = 0; k < n_items; k++)
-            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
-        return 0;
+        count_named(n_items, bin, stats->count);
     });
     EBCC_API_CATCH(1)
 }
@@ -2363,18 +2384,11 @@ int ebcc_hip_spell_stats_init(ebcc_hip_ctx *ctx, const ebcc_hip_spell_stats *sta
     const char *const who = "ebcc_hip_spell_stats_init";
     if (!ctx) { set_error("%s: bad arguments", who); return 1; }
     if (!spell_stats_shape(who, stats)) return 1;
-    return on_device(ctx->device, 1, [&] {
-        const size_t n = stats->n_bins * stats->rows * stats->cols;
-        for (uint32_t *p : {stats->d_run, stats->d_longest, stats->d_spells, stats->d_spell_steps, stats->d_events})
-            if (p) EBCC_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(uint32_t), ctx->stream));
-        for (uint32_t *p : {stats->d_longest_end, stats->d_first, stats->d_last, stats->d_when_min, stats->d_when_max})
-            if (p) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) p, (int) EBCC_HIP_NO_STEP, n, ctx->stream));
-        if (stats->d_min) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_min, (int) 0x7F800000u, n, ctx->stream));     // +inf
-        if (stats->d_max) EBCC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t) stats->d_max, (int) 0xFF800000u, n, ctx->stream));     // -inf
-        wait_stream(ctx->stream);
-        std::fill_n(stats->count, stats->n_bins, (uint64_t) 0);
-        return 0;
-    });
+    constexpr uint32_t no = EBCC_HIP_NO_STEP;
+    return start_values(ctx, {{stats->d_run, 4, 0}, {stats->d_longest, 4, 0}, {stats->d_spells, 4, 0}, {stats->d_spell_steps, 4, 0}, {stats->d_events, 4, 0},
+                              {stats->d_longest_end, 4, no}, {stats->d_first, 4, no}, {stats->d_last, 4, no}, {stats->d_when_min, 4, no}, {stats->d_when_max, 4, no},
+                              {stats->d_min, 4, kPlusInf}, {stats->d_max, 4, kMinusInf}},
+                        stats->n_bins * stats->rows * stats->cols, stats->count, stats->n_bins);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_spell_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const uint32_t *bin, const uint32_t *when, const uint8_t *fresh,
@@ -2382,13 +2396,9 @@ int ebcc_hip_spell_fold(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items,
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_spell_fold";
-    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
-    if (spell_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, when, n_items, 0, 0) < 0) return 1;
-    return on_device(ctx->device, 1, [&] {
+    return items_call(who, ctx, {d_items}, n_items, [&] { return spell_stats_named(who, stats ? stats->rows : 0, stats ? stats->cols : 0, stats, bin, when, n_items, 0, 0); }, [&] {
         spell_fold(ctx, d_items, n_items, stats->rows * stats->cols, bin, when, fresh, *stats);
-        for (size_t k = 0; k < n_items; k++)
-            if (!bin || bin[k] != EBCC_HIP_NO_BIN) stats->count[bin ? bin[k] : 0u]++;
-        return 0;
+        count_named(n_items, bin, stats->count);
     });
     EBCC_API_CATCH(1)
 }
@@ -2411,29 +2421,19 @@ int ebcc_hip_time_map_init(ebcc_hip_ctx *ctx, const ebcc_hip_time_map *map)
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_time_map_init";
-    size_t bytes = 0;
     if (!ctx || !map || !map->d_acc || !map->count || ((uintptr_t) map->d_acc & 7)) { set_error("%s: bad arguments", who); return 1; }
     if (map->n_out < 1 || map->rows < 1 || map->cols < 1) { set_error("%s: n_out, rows and cols must not be zero", who); return 1; }
-    if (__builtin_mul_overflow(map->rows, map->cols, &bytes) || __builtin_mul_overflow(bytes, map->n_out, &bytes) ||
-        __builtin_mul_overflow(bytes, sizeof(double), &bytes)) { set_error("%s: the size of the accumulators overflows", who); return 1; }
-    return on_device(ctx->device, 1, [&] {
-        EBCC_HIP_CHECK(hipMemsetAsync(map->d_acc, 0, bytes, ctx->stream));
-        wait_stream(ctx->stream);
-        std::fill_n(map->count, map->n_out, (uint64_t) 0);
-        return 0;
-    });
+    if (!accumulator_bytes_checked(who, map->rows, map->cols, map->n_out, sizeof(double))) return 1;
+    return start_values(ctx, {{map->d_acc, 8, 0}}, map->n_out * map->rows * map->cols, map->count, map->n_out);
     EBCC_API_CATCH(1)
 }
 int ebcc_hip_time_map_items(ebcc_hip_ctx *ctx, const float *d_items, size_t n_items, const ebcc_hip_time_map *map)
 {
     EBCC_API_TRY
     const char *const who = "ebcc_hip_time_map_items";
-    if (!ctx || !d_items || ((uintptr_t) d_items & 3) || n_items >= 0xFFFFFFFFu) { set_error("%s: bad arguments", who); return 1; }
-    if (time_map_named(who, map ? map->rows : 0, map ? map->cols : 0, map, n_items, 0, 0) < 0) return 1;
-    return on_device(ctx->device, 1, [&] {
+    return items_call(who, ctx, {d_items}, n_items, [&] { return time_map_named(who, map ? map->rows : 0, map ? map->cols : 0, map, n_items, 0, 0); }, [&] {
         time_map(ctx, d_items, map->rows * map->cols, *map, 0, n_items, nullptr, 0);
         for (size_t o = 0; o < map->n_out; o++) map->count[o] += map->start[o + 1] - map->start[o];
-        return 0;
     });
     EBCC_API_CATCH(1)
 }

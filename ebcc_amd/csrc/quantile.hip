@@ -5,6 +5,7 @@
 #include <climits>
 #include <unordered_map>
 #include "quantile.hpp"
+#include "time_walk.hpp"
 
 namespace ebcc {
 
@@ -133,41 +134,29 @@ void rank_begin(ebcc_hip_ctx *ctx, RankPlan &pl)
     wait_stream(ctx->stream);
 }
 
-// Launches of at most kList entries (the limit of the other list walks; a run is cut with its launch) and, within a launch,
-// of kRankSlots slots each over the same items.
+// Launches of at most kWalkList entries (walk_list, time_walk.hpp; a run is cut with its launch) and, within a launch, of
+// kRankSlots slots each over the same items.
 void rank_count(ebcc_hip_ctx *set, const RankPlan &pl, const float *d_items, size_t n, const uint32_t *bin, int pass)
 {
-    constexpr size_t kList = 65536;
-    std::vector<RankEntry> list;
-    list.reserve(n);
-    for (size_t k = 0; k < n; k++) {
-        const uint32_t b = bin ? bin[k] : 0u;
-        if (b != EBCC_HIP_NO_BIN && pl.mask[b]) list.push_back(RankEntry{(unsigned) k, b, pl.mask[b], 0u});
-    }
+    // (a bin none of whose slots is in use has no entries)
+    auto list = binned_list<RankEntry>(n, bin, [&](size_t k, uint32_t b) { return RankEntry{(unsigned) k, b, pl.mask[b], 0u}; },
+                                       [&](uint32_t b) { return pl.mask[b] != 0; });
     if (list.empty()) return;
-    std::stable_sort(list.begin(), list.end(), [](const RankEntry &p, const RankEntry &q) { return p.bin < q.bin; });
-    std::vector<unsigned> used((list.size() + kList - 1) / kList, 0u);     // per launch cut: the slots its bins use
-    for (size_t lo = 0; lo < list.size(); lo += kList)
-        for (size_t e = std::min(lo + kList, list.size()); e-- > lo;) {
-            const bool last = e + 1 == std::min(lo + kList, list.size()) || list[e + 1].bin != list[e].bin;
+    std::vector<unsigned> used((list.size() + kWalkList - 1) / kWalkList, 0u);     // per launch cut: the slots its bins use
+    for (size_t lo = 0; lo < list.size(); lo += kWalkList)
+        for (size_t e = std::min(lo + kWalkList, list.size()); e-- > lo;) {
+            const bool last = e + 1 == std::min(lo + kWalkList, list.size()) || list[e + 1].bin != list[e].bin;
             list[e].run = last ? 1u : list[e + 1].run + 1u;
-            used[lo / kList] |= list[e].mask;
+            used[lo / kWalkList] |= list[e].mask;
         }
-    boxes_reserve(set, list.size(), sizeof(RankEntry));
-    memcpy(set->boxes.h, list.data(), list.size() * sizeof(RankEntry));
-    EBCC_HIP_CHECK(hipMemcpyAsync(set->boxes.d, set->boxes.h, list.size() * sizeof(RankEntry), hipMemcpyHostToDevice, set->stream));
     const RankWork w{pl.hist, pl.prefix, pl.rem, pl.n_pix, (unsigned) pl.n_ranks};
-    {
-        ScopedTiming timing("rank_count", set->stream);
-        for (size_t lo = 0; lo < list.size(); lo += kList)
-            for (unsigned slot0 = 0; slot0 < pl.n_ranks; slot0 += kRankSlots) {
-                if (!((used[lo / kList] >> slot0) & ((1u << kRankSlots) - 1u))) continue;
-                hipLaunchKernelGGL(k_rank_count, dim3((unsigned) ((pl.n_pix + 255) / 256)), dim3(256), 0, set->stream, d_items, w,
-                                   (const RankEntry *) set->boxes.d + lo, (unsigned) std::min(kList, list.size() - lo), slot0, 32 - kDigitBits * (pass + 1));
-            }
-    }
-    EBCC_HIP_LAUNCH_CHECK();
-    wait_stream(set->stream);
+    walk_list(set, "rank_count", list, [&](const RankEntry *d_list, unsigned m, size_t lo) {
+        for (unsigned slot0 = 0; slot0 < pl.n_ranks; slot0 += kRankSlots) {
+            if (!((used[lo / kWalkList] >> slot0) & ((1u << kRankSlots) - 1u))) continue;
+            hipLaunchKernelGGL(k_rank_count, dim3((unsigned) ((pl.n_pix + 255) / 256)), dim3(256), 0, set->stream, d_items, w, d_list, m, slot0,
+                               32 - kDigitBits * (pass + 1));
+        }
+    });
 }
 
 void rank_advance(ebcc_hip_ctx *ctx, const RankPlan &pl, int pass, float *d_out)
@@ -219,27 +208,12 @@ long time_ranks_named(const char *who, size_t height, size_t width, const ebcc_h
                       size_t row0, size_t col0, RankPlan *plan)
 {
     if (!time_ranks_shape(who, sp)) return -1;
-    if (height < 1 || width < 1 || height > 2047 || width > 2047) { set_error("%s: unsupported geometry %zu x %zu", who, height, width); return -1; }
-    if (row0 >= height || col0 >= width || sp->rows > height - row0 || sp->cols > width - col0) {
-        set_error("%s: the window [%zu, +%zu) x [%zu, +%zu) is not inside the %zu x %zu frame", who, row0, sp->rows, col0, sp->cols, height, width);
-        return -1;
-    }
-    if (n_frames > (size_t) LONG_MAX) { set_error("%s: too many frames", who); return -1; }
+    if (!frame_window_checked(who, height, width, row0, col0, sp->rows, sp->cols)) return -1;
     std::unordered_map<uint32_t, uint64_t> frames;                  // of the bins that are named
-    size_t named = 0;
-    if (!bin) {
-        named = n_frames;
-        if (n_frames) frames[0] = n_frames;
-    } else {
-        for (size_t f = 0; f < n_frames; f++) {
-            const uint32_t b = bin[f];
-            if (b == EBCC_HIP_NO_BIN) continue;
-            if (b >= sp->n_bins) { set_error("%s: frame %zu names bin %u of %zu", who, f, b, sp->n_bins); return -1; }
-            frames[b]++;
-            named++;
-        }
-    }
-    if (!named) { set_error("%s: no frame is named", who); return -1; }
+    const long named = bin ? bins_named(who, "frame", n_frames, bin, sp->n_bins, [&](size_t, uint32_t b) { frames[b]++; return true; })
+                           : bins_named(who, "frame", n_frames, nullptr, sp->n_bins);
+    if (named < 0) return -1;
+    if (!bin) frames[0] = (uint64_t) named;                         // (all in bin 0: not counted one by one)
     for (const auto &bf : frames)
         if (bf.second > UINT32_MAX) { set_error("%s: bin %u is given %llu frames, not fewer than 2^32", who, bf.first, (unsigned long long) bf.second); return -1; }
     size_t used = 0;
@@ -270,7 +244,7 @@ long time_ranks_named(const char *who, size_t height, size_t width, const ebcc_h
                 pl.start.push_back((unsigned) r);
             }
     }
-    return (long) named;
+    return named;
 }
 
 }  // namespace ebcc

@@ -63,6 +63,73 @@ class TimeStats(ctypes.Structure):
 NO_BIN = 0xFFFFFFFF                                               # EBCC_HIP_NO_BIN
 
 
+class _DeviceState:
+    """What the device-resident states share: the window, the arrays `fields` = [(name, dtype), ..] of `shape` on the device -
+    the pointer of each is the attribute _prefix + name of the object _held() returns -, result()'s download and close()."""
+    _prefix = ""
+
+    def _held(self):
+        return self.stats
+
+    def _begin(self, codec, n, what):
+        """the codec kept -> n, the number of bins or outputs (`what`: its name), 1 at least"""
+        self.codec, n = codec, int(n)
+        if n < 1:
+            raise ValueError(f"{what} must be at least 1")
+        return n
+
+    def _open(self, n, window):
+        """window, shape = (n, rows, cols) and count, n zeros -> rows, cols"""
+        codec = self.codec
+        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
+        row0, col0, rows, cols = self.window
+        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
+            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
+        self.shape = (n, rows, cols)
+        self.count = np.zeros(n, np.uint64)
+        return rows, cols
+
+    def _alloc(self, init, arg=None):
+        """the arrays of `fields` made on the device and set by the entry point `init` (arg: what it is given, default the
+        holder of the pointers); nothing stays allocated when either fails"""
+        codec, held = self.codec, self._held()
+        try:
+            for name, dtype in self.fields:
+                p = codec.lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
+                if not p:
+                    codec._fail("ebcc_hip_malloc")
+                setattr(held, self._prefix + name, p)
+            if getattr(codec.lib, init)(codec.ctx, ctypes.byref(held if arg is None else arg())):
+                codec._fail(init)
+        except BaseException:
+            self.close()
+            raise
+
+    def _download(self):
+        """{name: array} of the fields"""
+        got = {}
+        for name, dtype in self.fields:
+            a = np.empty(self.shape, dtype)
+            if self.codec.lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self._held(), self._prefix + name), a.nbytes):
+                self.codec._fail("ebcc_hip_memcpy_d2h")
+            got[name] = a
+        return got
+
+    def close(self):
+        held = self._held()
+        for name, _ in self.fields:
+            p = getattr(held, self._prefix + name)
+            if p:
+                self.codec.lib.ebcc_hip_free(p)
+                setattr(held, self._prefix + name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class ReduceResult:
     """Statistics over time, per bin and pixel: count (n_bins,) uint64 - the frames folded into each bin -, sum and sum_sq
     (n_bins, rows, cols) float64, min and max float32, over uint32 (None without a threshold: the frames with sample >
@@ -84,59 +151,23 @@ class ReduceResult:
             return self.sum_sq / self.count.astype(np.float64)[:, None, None] - m * m
 
 
-class ReduceState:
+class ReduceState(_DeviceState):
     """The accumulators of BatchCodec.reduce, resident on the device from call to call (BatchCodec.reduce_state makes one):
     result() downloads them, close() frees them."""
 
     def __init__(self, codec, n_bins, window, threshold):
-        self.codec, self.n_bins = codec, int(n_bins)
-        if self.n_bins < 1:
-            raise ValueError("n_bins must be at least 1")
-        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
-        row0, col0, rows, cols = self.window
-        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
-            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
-        self.shape = (self.n_bins, rows, cols)
-        self.count = np.zeros(self.n_bins, np.uint64)
+        self.n_bins = self._begin(codec, n_bins, "n_bins")
+        rows, cols = self._open(self.n_bins, window)
         self.stats = TimeStats(self.n_bins, rows, cols, None, None, None, None, None, 0.0 if threshold is None else float(threshold),
                                self.count.ctypes.data)
         self.fields = [("d_sum", np.float64), ("d_sum_sq", np.float64), ("d_min", np.float32), ("d_max", np.float32)]
         if threshold is not None:
             self.fields.append(("d_over", np.uint32))
-        lib = codec.lib
-        try:
-            for name, dtype in self.fields:
-                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
-                if not p:
-                    codec._fail("ebcc_hip_malloc")
-                setattr(self.stats, name, p)
-            if lib.ebcc_hip_time_stats_init(codec.ctx, ctypes.byref(self.stats)):
-                codec._fail("ebcc_hip_time_stats_init")
-        except BaseException:
-            self.close()
-            raise
+        self._alloc("ebcc_hip_time_stats_init")
 
     def result(self):
-        lib, got = self.codec.lib, {}
-        for name, dtype in self.fields:
-            a = np.empty(self.shape, dtype)
-            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, name), a.nbytes):
-                self.codec._fail("ebcc_hip_memcpy_d2h")
-            got[name] = a
+        got = self._download()
         return ReduceResult(self.count.copy(), got["d_sum"], got["d_sum_sq"], got["d_min"], got["d_max"], got.get("d_over"))
-
-    def close(self):
-        for name, _ in self.fields:
-            p = getattr(self.stats, name)
-            if p:
-                self.codec.lib.ebcc_hip_free(p)
-                setattr(self.stats, name, None)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class PairStats(ctypes.Structure):
@@ -191,22 +222,15 @@ class PairResult:
         return None if self.sum_mag is None else self._over_n(self.sum_mag)
 
 
-class PairState:
+class PairState(_DeviceState):
     """The accumulators of BatchCodec.pair, resident on the device from call to call (BatchCodec.pair_state makes one):
     result() downloads them, close() frees them."""
 
     def __init__(self, codec, n_bins, window, threshold, magnitude):
-        self.codec, self.n_bins = codec, int(n_bins)
-        if self.n_bins < 1:
-            raise ValueError("n_bins must be at least 1")
+        self.n_bins = self._begin(codec, n_bins, "n_bins")
         if threshold is not None and (not magnitude or np.isnan(float(threshold))):
             raise ValueError("a threshold needs magnitude=True and must not be a NaN")
-        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
-        row0, col0, rows, cols = self.window
-        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
-            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
-        self.shape = (self.n_bins, rows, cols)
-        self.count = np.zeros(self.n_bins, np.uint64)
+        rows, cols = self._open(self.n_bins, window)
         self.stats = PairStats(self.n_bins, rows, cols, None, None, None, None, None, None, None, None, 0.0 if threshold is None else float(threshold),
                                self.count.ctypes.data)
         self.fields = [(name, np.float64) for name in ("d_sum_x", "d_sum_y", "d_sum_xx", "d_sum_yy", "d_sum_xy")]
@@ -214,41 +238,12 @@ class PairState:
             self.fields += [("d_sum_mag", np.float64), ("d_max_mag", np.float32)]
         if threshold is not None:
             self.fields.append(("d_over_mag", np.uint32))
-        lib = codec.lib
-        try:
-            for name, dtype in self.fields:
-                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
-                if not p:
-                    codec._fail("ebcc_hip_malloc")
-                setattr(self.stats, name, p)
-            if lib.ebcc_hip_pair_stats_init(codec.ctx, ctypes.byref(self.stats)):
-                codec._fail("ebcc_hip_pair_stats_init")
-        except BaseException:
-            self.close()
-            raise
+        self._alloc("ebcc_hip_pair_stats_init")
 
     def result(self):
-        lib, got = self.codec.lib, {}
-        for name, dtype in self.fields:
-            a = np.empty(self.shape, dtype)
-            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, name), a.nbytes):
-                self.codec._fail("ebcc_hip_memcpy_d2h")
-            got[name] = a
+        got = self._download()
         return PairResult(self.count.copy(), got["d_sum_x"], got["d_sum_y"], got["d_sum_xx"], got["d_sum_yy"], got["d_sum_xy"], got.get("d_sum_mag"),
                           got.get("d_max_mag"), got.get("d_over_mag"))
-
-    def close(self):
-        for name, _ in self.fields:
-            p = getattr(self.stats, name)
-            if p:
-                self.codec.lib.ebcc_hip_free(p)
-                setattr(self.stats, name, None)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class SpellStats(ctypes.Structure):
@@ -289,14 +284,14 @@ class SpellResult:
         return None if a is None else np.ma.masked_equal(a, NO_STEP)
 
 
-class SpellState:
+class SpellState(_DeviceState):
     """The accumulators of BatchCodec.spells, resident on the device from call to call (BatchCodec.spell_state makes one): the
     open run of every pixel is part of them.  result() downloads them, close() frees them."""
+    _prefix = "d_"
 
     def __init__(self, codec, threshold, below, min_len, n_bins, window, what):
-        self.codec, self.n_bins, self.min_len = codec, int(n_bins), int(min_len)
-        if self.n_bins < 1:
-            raise ValueError("n_bins must be at least 1")
+        self.min_len = int(min_len)
+        self.n_bins = self._begin(codec, n_bins, "n_bins")
         what = (what,) if isinstance(what, str) else tuple(what)
         if not what or any(f not in SPELL_FAMILIES for f in what):
             raise ValueError(f"what must name some of {tuple(SPELL_FAMILIES)}")
@@ -304,12 +299,7 @@ class SpellState:
             raise ValueError("the threshold must not be a NaN")
         if not 0 <= self.min_len < NO_STEP:
             raise ValueError("min_len must be a uint32")
-        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
-        row0, col0, rows, cols = self.window
-        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
-            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
-        self.shape = (self.n_bins, rows, cols)
-        self.count = np.zeros(self.n_bins, np.uint64)
+        rows, cols = self._open(self.n_bins, window)
         self.stats = SpellStats(self.n_bins, rows, cols, float(threshold), 1 if below else 0, self.min_len)
         self.stats.count = self.count.ctypes.data
         self.fields = []
@@ -317,40 +307,10 @@ class SpellState:
             if family in what:
                 self.fields += [(name, np.float32 if name in ("min", "max") else np.uint32) for name in SPELL_FAMILIES[family]
                                 if self.min_len or name not in ("spells", "spell_steps")]
-        lib = codec.lib
-        try:
-            for name, dtype in self.fields:
-                p = lib.ebcc_hip_malloc(int(np.prod(self.shape)) * np.dtype(dtype).itemsize)
-                if not p:
-                    codec._fail("ebcc_hip_malloc")
-                setattr(self.stats, "d_" + name, p)
-            if lib.ebcc_hip_spell_stats_init(codec.ctx, ctypes.byref(self.stats)):
-                codec._fail("ebcc_hip_spell_stats_init")
-        except BaseException:
-            self.close()
-            raise
+        self._alloc("ebcc_hip_spell_stats_init")
 
     def result(self):
-        lib, got = self.codec.lib, {}
-        for name, dtype in self.fields:
-            a = np.empty(self.shape, dtype)
-            if lib.ebcc_hip_memcpy_d2h(a.ctypes.data, getattr(self.stats, "d_" + name), a.nbytes):
-                self.codec._fail("ebcc_hip_memcpy_d2h")
-            got[name] = a
-        return SpellResult(self.count.copy(), **got)
-
-    def close(self):
-        for name, _ in self.fields:
-            p = getattr(self.stats, "d_" + name)
-            if p:
-                self.codec.lib.ebcc_hip_free(p)
-                setattr(self.stats, "d_" + name, None)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return SpellResult(self.count.copy(), **self._download())
 
 
 class TimeRanks(ctypes.Structure):
@@ -486,29 +446,18 @@ class ProjectResult:
         self.values, self.count = values, count
 
 
-class MapState:
+class MapState(_DeviceState):
     """The accumulators of BatchCodec.project, resident on the device from call to call (BatchCodec.map_state makes one):
     result() downloads them, close() frees them."""
 
+    def _held(self):
+        return self
+
     def __init__(self, codec, n_out, window):
-        self.codec, self.n_out = codec, int(n_out)
-        if self.n_out < 1:
-            raise ValueError("n_out must be at least 1")
-        self.window = (0, 0, codec.h, codec.w) if window is None else tuple(int(v) for v in window)
-        row0, col0, rows, cols = self.window
-        if min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > codec.h or col0 + cols > codec.w:
-            raise ValueError(f"window {self.window} is empty or not inside the {codec.h} x {codec.w} frame")
-        self.shape = (self.n_out, rows, cols)
-        self.count = np.zeros(self.n_out, np.uint64)
-        self.d_acc = codec.lib.ebcc_hip_malloc(int(np.prod(self.shape)) * 8)
-        if not self.d_acc:
-            codec._fail("ebcc_hip_malloc")
-        try:
-            if codec.lib.ebcc_hip_time_map_init(codec.ctx, ctypes.byref(self.map(None, None, None))):
-                codec._fail("ebcc_hip_time_map_init")
-        except BaseException:
-            self.close()
-            raise
+        self.n_out = self._begin(codec, n_out, "n_out")
+        self._open(self.n_out, window)
+        self.d_acc, self.fields = None, [("d_acc", np.float64)]
+        self._alloc("ebcc_hip_time_map_init", lambda: self.map(None, None, None))
 
     def map(self, start, frame, weight):
         """the ebcc_hip_time_map of these accumulators with the terms of one call (arrays the caller keeps alive)"""
@@ -516,21 +465,7 @@ class MapState:
                        self.d_acc, self.count.ctypes.data)
 
     def result(self):
-        a = np.empty(self.shape, np.float64)
-        if self.codec.lib.ebcc_hip_memcpy_d2h(a.ctypes.data, self.d_acc, a.nbytes):
-            self.codec._fail("ebcc_hip_memcpy_d2h")
-        return ProjectResult(a, self.count.copy())
-
-    def close(self):
-        if self.d_acc:
-            self.codec.lib.ebcc_hip_free(self.d_acc)
-            self.d_acc = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return ProjectResult(self._download()["d_acc"], self.count.copy())
 
 
 def _terms_of_range(terms, lo, hi):
@@ -672,6 +607,21 @@ def _box_array(boxes):
     if b.ndim != 2 or b.shape[1] != 3 or b.shape[0] < 1 or b.dtype.kind not in "iu":
         raise ValueError("boxes must be a non-empty integer array of shape (k, 3): frame, row0, col0")
     return b.astype(np.int64)
+
+
+def _bin_table(bins, n, n_bins, per, none_named):
+    """`bins` of a call over n streams or steps (None: all bin 0, -1: skipped) -> (b, table): the bins as int64 and the uint32
+    table the engine takes, NO_BIN where one is skipped.  ValueError with the texts of the call: `per` - "stream" / "step" -
+    and none_named, the message when every entry is skipped."""
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
+        raise ValueError(f"bins must be {n} integers, one per {per}")
+    b = b.astype(np.int64)
+    if b.min() < -1 or b.max() >= n_bins:
+        raise ValueError(f"bins must lie in [-1, {n_bins})")
+    if not (b >= 0).any():
+        raise ValueError(none_named)
+    return b, np.where(b < 0, NO_BIN, b).astype(np.uint32)
 
 
 def _read_chunks(dset, frames):
@@ -833,15 +783,7 @@ class BatchCodec:
         if own:
             state = ReduceState(self, n_bins, window, threshold)
         try:
-            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
-                raise ValueError(f"bins must be {n} integers, one per stream")
-            b = b.astype(np.int64)
-            if b.min() < -1 or b.max() >= state.n_bins:
-                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
-            if not (b >= 0).any():
-                raise ValueError("no frame is named")
-            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            b, table = _bin_table(bins, n, state.n_bins, "stream", "no frame is named")
             streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.nonzero(b >= 0)[0]))
             row0, col0 = state.window[:2]
             if self.lib.ebcc_hip_reduce_shard(self.ctx, ptrs, sizes, n, table.ctypes.data, row0, col0, ctypes.byref(state.stats)):
@@ -874,15 +816,7 @@ class BatchCodec:
         if own:
             state = PairState(self, n_bins, window, threshold, magnitude)
         try:
-            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
-                raise ValueError(f"bins must be {n} integers, one per step")
-            b = b.astype(np.int64)
-            if b.min() < -1 or b.max() >= state.n_bins:
-                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
-            if not (b >= 0).any():
-                raise ValueError("no step is named")
-            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            b, table = _bin_table(bins, n, state.n_bins, "step", "no step is named")
             named = set(int(f) for f in np.nonzero(b >= 0)[0])
             keep_x, ptrs_x, sizes_x = _stream_arrays(streams_x, named=named)
             keep_y, ptrs_y, sizes_y = (keep_x, ptrs_x, sizes_x) if streams_y is streams_x else _stream_arrays(streams_y, named=named)
@@ -918,15 +852,7 @@ class BatchCodec:
         if own:
             state = SpellState(self, threshold, below, min_len, n_bins, window, what)
         try:
-            b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-            if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
-                raise ValueError(f"bins must be {n} integers, one per stream")
-            b = b.astype(np.int64)
-            if b.min() < -1 or b.max() >= state.n_bins:
-                raise ValueError(f"bins must lie in [-1, {state.n_bins})")
-            if not (b >= 0).any():
-                raise ValueError("no step is named")
-            table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
+            b, table = _bin_table(bins, n, state.n_bins, "stream", "no step is named")
             labels = None
             if when is not None:
                 labels = np.asarray(when)
@@ -970,14 +896,7 @@ class BatchCodec:
         row0, col0, rows, cols = (0, 0, self.h, self.w) if window is None else tuple(int(v) for v in window)
         if n_bins < 1 or min(row0, col0) < 0 or rows < 1 or cols < 1 or row0 + rows > self.h or col0 + cols > self.w:
             raise ValueError(f"n_bins {n_bins} or window {(row0, col0, rows, cols)} does not fit the {self.h} x {self.w} frame")
-        b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-        if n < 1 or b.shape != (n,) or b.dtype.kind not in "iu":
-            raise ValueError(f"bins must be {n} integers, one per stream")
-        b = b.astype(np.int64)
-        if b.min() < -1 or b.max() >= n_bins:
-            raise ValueError(f"bins must lie in [-1, {n_bins})")
-        if not (b >= 0).any():
-            raise ValueError("no frame is named")
+        b, table = _bin_table(bins, n, n_bins, "stream", "no frame is named")
         m = np.bincount(b[b >= 0], minlength=n_bins)
         rules = [[quantile_rule(v, int(m[k]), method) for v in qs] if m[k] else None for k in range(n_bins)]
         slots = [sorted({r for lo, hi, _ in rule for r in (lo, hi)}) if rule else [] for rule in rules]
@@ -989,7 +908,6 @@ class BatchCodec:
             rank[k, :len(s)] = s
         count = np.zeros(n_bins, np.uint64)
         planes = np.empty((n_bins, n_ranks, rows, cols), np.float32)
-        table = np.where(b < 0, NO_BIN, b).astype(np.uint32)
         streams, ptrs, sizes = _stream_arrays(streams, named=set(int(f) for f in np.nonzero(b >= 0)[0]))
         d_out = self.lib.ebcc_hip_malloc(planes.nbytes)
         if not d_out:
@@ -1466,31 +1384,63 @@ def read_frames(dset, batch=256, codec=None, rows=None, cols=None):
     with held_codec(h, w, min(batch, n), codec=codec) as codec:
         step = _SUPER * codec.max_frames
 
-        def fetch(lo, box):
+        def read(lo):
+            t0 = time.perf_counter()
             try:
-                box.append(_read_chunks(dset, range(lo, min(n, lo + step))))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
-        box = []
-        t0 = time.perf_counter()
-        fetch(0, box)
-        if os.environ.get("EBCC_H5_TIMING"):
-            print(f"h5_batch.read_frames: first {min(n, step)} chunks fetched in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
-        for lo in range(0, n, step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < n:
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                codec.decode(raw, out=out[lo:lo + len(raw)], window=window)
+                return _read_chunks(dset, range(lo, min(n, lo + step)))
             finally:
-                if t:
-                    t.join()
+                if lo == 0 and os.environ.get("EBCC_H5_TIMING"):
+                    print(f"h5_batch.read_frames: first {min(n, step)} chunks fetched in {1e3 * (time.perf_counter() - t0):.1f} ms", file=sys.stderr, flush=True)
+
+        def work(lo, raw):
+            codec.decode(raw, out=out[lo:lo + len(raw)], window=window)
+
+        _prefetched(read, n, step, work)
     return out.reshape(tuple(lead) + (nrows, ncols))
+
+
+def _lead_bins(lead, bins, n_bins, noun):
+    """`bins` of a dataset with the leading axes `lead` (None: everything in bin 0, -1: skipped) -> (b, named, n_bins): the
+    bins in C order as int64, the indices of those that are named, and n_bins (None: the largest bin + 1).  noun: "frame" /
+    "step", for the messages."""
+    n = int(np.prod(lead)) if lead else 1
+    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
+    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
+        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
+    b = b.astype(np.int64).reshape(-1)
+    named = np.nonzero(b >= 0)[0]
+    if len(named) < 1 or b.min() < -1:
+        raise ValueError(f"bins must name at least one {noun}, and -1 is the only negative value")
+    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
+    if b.max() >= n_bins:
+        raise ValueError(f"a {noun} names bin {int(b.max())} of {n_bins}")
+    return b, named, n_bins
+
+
+def _prefetched(read, n, step, work):
+    """work(lo, read(lo)) for lo = 0, step, .. below n, one after the other: while a call works, the next one's chunks are read
+    on a helper thread, which is joined before the call returns; a failure of a read is raised on the caller's thread."""
+    def fetch(lo, box):
+        try:
+            box.append(read(lo))
+        except BaseException as e:                                  # (handed to the caller's thread)
+            box.append(e)
+
+    box = []
+    fetch(0, box)
+    for lo in range(0, n, step):
+        raw = box[0]
+        if isinstance(raw, BaseException):
+            raise raw
+        box, t = [], None
+        if lo + step < n:
+            t = threading.Thread(target=fetch, args=(lo + step, box))
+            t.start()
+        try:
+            work(lo, raw)
+        finally:
+            if t:
+                t.join()
 
 
 def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=None, batch=256, codec=None):
@@ -1503,44 +1453,17 @@ def reduce_frames(dset, bins=None, n_bins=None, rows=None, cols=None, threshold=
     not fit into host memory."""
     h, w = dset.shape[-2:]
     lead = dset.shape[:-2]
-    n = int(np.prod(lead)) if lead else 1
     (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
-    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
-        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
-    b = b.astype(np.int64).reshape(-1)
-    named = np.nonzero(b >= 0)[0]
-    if len(named) < 1 or b.min() < -1:
-        raise ValueError("bins must name at least one frame, and -1 is the only negative value")
-    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
-    if b.max() >= n_bins:
-        raise ValueError(f"a frame names bin {int(b.max())} of {n_bins}")
+    b, named, n_bins = _lead_bins(lead, bins, n_bins, "frame")
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
         step = _SUPER * codec.max_frames
-
-        def fetch(lo, box):
-            try:
-                box.append(_read_chunks(dset, named[lo:lo + step]))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
-        box = []
-        fetch(0, box)
         state = stack.enter_context(codec.reduce_state(n_bins, (row0, col0, nrows, ncols), threshold))
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                codec.reduce(raw, bins=b[named[lo:lo + step]], state=state)
-            finally:
-                if t:
-                    t.join()
+
+        def work(lo, raw):
+            codec.reduce(raw, bins=b[named[lo:lo + step]], state=state)
+
+        _prefetched(lambda lo: _read_chunks(dset, named[lo:lo + step]), len(named), step, work)
         return state.result()
 
 
@@ -1556,44 +1479,17 @@ def pair_frames(dset_x, dset_y, bins=None, n_bins=None, rows=None, cols=None, th
         raise ValueError(f"the datasets have the shapes {tuple(dset_x.shape)} and {tuple(dset_y.shape)}")
     h, w = dset_x.shape[-2:]
     lead = dset_x.shape[:-2]
-    n = int(np.prod(lead)) if lead else 1
     (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
-    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
-        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
-    b = b.astype(np.int64).reshape(-1)
-    named = np.nonzero(b >= 0)[0]
-    if len(named) < 1 or b.min() < -1:
-        raise ValueError("bins must name at least one step, and -1 is the only negative value")
-    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
-    if b.max() >= n_bins:
-        raise ValueError(f"a step names bin {int(b.max())} of {n_bins}")
+    b, named, n_bins = _lead_bins(lead, bins, n_bins, "step")
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, max(2, min(batch, 2 * len(named))), codec=codec))
         step = _SUPER * max(1, codec.max_frames // 2)                   # (steps a call: two frames each)
-
-        def fetch(lo, box):
-            try:
-                box.append((_read_chunks(dset_x, named[lo:lo + step]), _read_chunks(dset_y, named[lo:lo + step])))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
-        box = []
-        fetch(0, box)
         state = stack.enter_context(codec.pair_state(n_bins, (row0, col0, nrows, ncols), threshold, magnitude))
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                codec.pair(raw[0], raw[1], bins=b[named[lo:lo + step]], state=state)
-            finally:
-                if t:
-                    t.join()
+
+        def work(lo, raw):
+            codec.pair(raw[0], raw[1], bins=b[named[lo:lo + step]], state=state)
+
+        _prefetched(lambda lo: (_read_chunks(dset_x, named[lo:lo + step]), _read_chunks(dset_y, named[lo:lo + step])), len(named), step, work)
         return state.result()
 
 
@@ -1610,16 +1506,7 @@ def spell_frames(dset, threshold, below=False, min_len=1, bins=None, when=None, 
     lead = dset.shape[:-2]
     n = int(np.prod(lead)) if lead else 1
     (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
-    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
-        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
-    b = b.astype(np.int64).reshape(-1)
-    named = np.nonzero(b >= 0)[0]
-    if len(named) < 1 or b.min() < -1:
-        raise ValueError("bins must name at least one step, and -1 is the only negative value")
-    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
-    if b.max() >= n_bins:
-        raise ValueError(f"a step names bin {int(b.max())} of {n_bins}")
+    b, named, n_bins = _lead_bins(lead, bins, n_bins, "step")
     labels = np.arange(n, dtype=np.int64) if when is None else np.asarray(when)
     if labels.dtype.kind not in "iu" or labels.size != n or (when is not None and tuple(labels.shape) != tuple(lead)):
         raise ValueError(f"when must be an integer array of shape {tuple(lead)}")
@@ -1631,30 +1518,13 @@ def spell_frames(dset, threshold, below=False, min_len=1, bins=None, when=None, 
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
         step = _SUPER * codec.max_frames
-
-        def fetch(lo, box):
-            try:
-                box.append(_read_chunks(dset, named[lo:lo + step]))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
-        box = []
-        fetch(0, box)
         state = stack.enter_context(codec.spell_state(threshold, below, min_len, n_bins, (row0, col0, nrows, ncols), what))
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                part = named[lo:lo + step]
-                codec.spells(raw, None, bins=b[part], when=labels[part], fresh=flags[part], state=state)
-            finally:
-                if t:
-                    t.join()
+
+        def work(lo, raw):
+            part = named[lo:lo + step]
+            codec.spells(raw, None, bins=b[part], when=labels[part], fresh=flags[part], state=state)
+
+        _prefetched(lambda lo: _read_chunks(dset, named[lo:lo + step]), len(named), step, work)
         return state.result()
 
 
@@ -1667,18 +1537,8 @@ def quantile_frames(dset, q, bins=None, n_bins=None, rows=None, cols=None, metho
     therefore must hold them (not the decoded frames)."""
     h, w = dset.shape[-2:]
     lead = dset.shape[:-2]
-    n = int(np.prod(lead)) if lead else 1
     (row0, nrows), (col0, ncols) = _box(rows, h, "rows"), _box(cols, w, "cols")
-    b = np.zeros(n, np.int64) if bins is None else np.asarray(bins)
-    if b.dtype.kind not in "iu" or b.size != n or (bins is not None and tuple(b.shape) != tuple(lead)):
-        raise ValueError(f"bins must be an integer array of shape {tuple(lead)}")
-    b = b.astype(np.int64).reshape(-1)
-    named = np.nonzero(b >= 0)[0]
-    if len(named) < 1 or b.min() < -1:
-        raise ValueError("bins must name at least one frame, and -1 is the only negative value")
-    n_bins = int(b.max()) + 1 if n_bins is None else int(n_bins)
-    if b.max() >= n_bins:
-        raise ValueError(f"a frame names bin {int(b.max())} of {n_bins}")
+    b, named, n_bins = _lead_bins(lead, bins, n_bins, "frame")
     with held_codec(h, w, min(batch, len(named)), codec=codec) as codec:
         raw = _read_chunks(dset, named)
         return codec.quantiles(raw, q, bins=b[named], n_bins=n_bins, window=(row0, col0, nrows, ncols), method=method)
@@ -1701,32 +1561,15 @@ def project_frames(dset, weights, rows=None, cols=None, batch=256, codec=None):
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
         step = _SUPER * codec.max_frames
-
-        def fetch(lo, box):
-            try:
-                box.append(_read_chunks(dset, named[lo:lo + step]))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
-        box = []
-        fetch(0, box)
         state = stack.enter_context(codec.map_state(len(terms[0]) - 1, (row0, col0, nrows, ncols)))
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                # the call's streams are the named frames of this step alone: its terms, with their frames counted among them
-                start, frame, weight = _terms_of_range(terms, int(named[lo]), int(named[lo:lo + step][-1]) + 1)
-                at = np.searchsorted(named[lo:lo + step], frame.astype(np.int64) + int(named[lo])).astype(np.uint32)
-                codec.project(raw, (start, at, weight), state=state)
-            finally:
-                if t:
-                    t.join()
+
+        def work(lo, raw):
+            # the call's streams are the named frames of this step alone: its terms, with their frames counted among them
+            start, frame, weight = _terms_of_range(terms, int(named[lo]), int(named[lo:lo + step][-1]) + 1)
+            at = np.searchsorted(named[lo:lo + step], frame.astype(np.int64) + int(named[lo])).astype(np.uint32)
+            codec.project(raw, (start, at, weight), state=state)
+
+        _prefetched(lambda lo: _read_chunks(dset, named[lo:lo + step]), len(named), step, work)
         return state.result()
 
 
@@ -1746,30 +1589,14 @@ def series_frames(dset, regions, frames=None, w_row=None, w_pix=None, threshold=
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
         step = _SUPER * codec.max_frames
-
-        def fetch(lo, box):
-            try:
-                box.append(_read_chunks(dset, named[lo:lo + step]))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
         area = _Area(codec, regions, w_row, w_pix, threshold)
         stack.callback(area.close)
-        box, parts = [], []
-        fetch(0, box)
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                parts.append(area.run(raw))
-            finally:
-                if t:
-                    t.join()
+        parts = []
+
+        def work(lo, raw):
+            parts.append(area.run(raw))
+
+        _prefetched(lambda lo: _read_chunks(dset, named[lo:lo + step]), len(named), step, work)
         return SeriesResult(np.concatenate(parts), area.weight())
 
 
@@ -1788,29 +1615,12 @@ def read_regridded(dset, row_map, col_map, frames=None, batch=256, codec=None):
     with contextlib.ExitStack() as stack:
         codec = stack.enter_context(held_codec(h, w, min(batch, len(named)), codec=codec))
         step = _SUPER * codec.max_frames
-
-        def fetch(lo, box):
-            try:
-                box.append(_read_chunks(dset, named[lo:lo + step]))
-            except BaseException as e:                              # (handed to the caller's thread)
-                box.append(e)
-
         out = np.empty((len(named), row_map.n_out, col_map.n_out), np.float32)
-        box = []
-        fetch(0, box)
-        for lo in range(0, len(named), step):
-            raw = box[0]
-            if isinstance(raw, BaseException):
-                raise raw
-            box, t = [], None
-            if lo + step < len(named):
-                t = threading.Thread(target=fetch, args=(lo + step, box))
-                t.start()
-            try:
-                codec.regrid(raw, row_map, col_map, out=out[lo:lo + len(raw)])
-            finally:
-                if t:
-                    t.join()
+
+        def work(lo, raw):
+            codec.regrid(raw, row_map, col_map, out=out[lo:lo + len(raw)])
+
+        _prefetched(lambda lo: _read_chunks(dset, named[lo:lo + step]), len(named), step, work)
         return out
 
 

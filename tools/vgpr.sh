@@ -11,6 +11,7 @@
 #   tools/vgpr.sh 'time_map'                               the two instances of the time-map decode's kernel (time_map.hip)
 #   tools/vgpr.sh 'pair_fold'                              the three instances of the pair decode's kernel (pair_stats.hip)
 #   tools/vgpr.sh 'spell_fold'                             the seven instances of the spell decode's kernel (spell_stats.hip)
+#   tools/vgpr.sh 'time_fold|time_map|pair_fold|spell_fold'    every kernel whose body is the walk of time_walk.hpp
 # Compiled with the Makefile's code-generation flags; run it at two commits to compare their register use.
 pat="${1:-t1_}"
 cd "$(dirname "$0")/../ebcc_amd/csrc"
